@@ -63,7 +63,61 @@ def parse():
     ap.add_argument("--no-solo", action="store_true", help="skip the cache-cold solo replays of the captured launches")
     ap.add_argument("--cpu-rays", type=int, default=1024)
     ap.add_argument("--cpu-samples", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the run, write what the timed path's step computes on the timed region's last ray batch from a "
+                         "seeded state (rank 0) as DIR/<name>.npy: see main() and step_outputs()")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64 << 20       # bytes of all --dump-outputs arrays together
+DUMP_SAMPLES_PER_RAY = 128   # per-sample results are written as each ray's first samples, up to this many
+
+
+def per_ray(x, rays_a, n_rays, k):
+    """(total samples, ...) -> (n_rays, k, ...): row r holds the first k samples of ray r (rays_a rows: ray, first
+    sample, sample count) in marching order, zeros past its count — a shape that does not depend on how many samples
+    the step marched, and sample j of ray r in the same place whatever the other rays marched"""
+    out = np.zeros((n_rays, k) + x.shape[1:], x.dtype)
+    if len(x) == 0:
+        return out
+    ray, start, cnt = (rays_a[:, i].astype(np.int64) for i in range(3))
+    j = np.arange(k)
+    valid = j[None, :] < cnt[:, None]
+    rows = x[np.where(valid, start[:, None] + j[None, :], 0)]
+    out[ray] = np.where(valid.reshape(valid.shape + (1,) * (x.ndim - 1)), rows, 0)
+    return out
+
+
+def step_outputs(loss, res, batch):
+    """Host copies of what one training step (NGPTrainer.step) handed its caller — the loss and every tensor of the
+    results dict — and of the ray batch it was given (rays_o, rays_d, rgb_gt).  The per-sample results (one row per
+    marched sample) are laid out per ray by per_ray(), with as many samples per ray as DUMP_BUDGET leaves room for, at
+    most DUMP_SAMPLES_PER_RAY: every shape follows from the arguments alone.  Float tensors become float32, integer ones
+    float64 (exact); scalars have shape (1,)."""
+    def host(t):
+        t = t.detach()
+        a = t.cpu().numpy().astype(np.float32 if t.is_floating_point() or t.dtype == torch.bool else np.float64)
+        return a.reshape(1) if a.ndim == 0 else a
+    out = {"loss": host(loss), "rays_o": host(batch[0]), "rays_d": host(batch[1]), "rgb_gt": host(batch[2])}
+    per_sample = {}
+    n_samples = res["xyzs"].shape[0]
+    for k, v in res.items():
+        if torch.is_tensor(v):
+            (per_sample if v.dim() > 0 and v.shape[0] == n_samples else out)[k] = host(v)
+    n_rays = len(batch[0])
+    row_bytes = n_rays * sum(a.itemsize * int(np.prod(a.shape[1:])) for a in per_sample.values())
+    k = min(DUMP_SAMPLES_PER_RAY, (DUMP_BUDGET - sum(a.nbytes for a in out.values())) // max(row_bytes, 1))
+    assert k >= 1, "--dump-outputs: the per-ray arrays alone exceed DUMP_BUDGET"
+    out.update({name: per_ray(a, out["rays_a"], n_rays, k) for name, a in per_sample.items()})
+    return out
+
+
+def dump_outputs(arrays, out_dir):
+    """writes every array as out_dir/<name>.npy; returns the bytes written"""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def _host_cpu():
@@ -243,23 +297,27 @@ def main():
     from ngp_amd.metrics import psnr
 
     seed = 20220806
-    torch.manual_seed(seed)  # identical initial weights on every rank
-    np.random.seed(seed)
-    model = NGP(scale=0.5).to(dev)
-    G = model.grid_size
-    model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=dev))
-    coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=dev)] * 3, indexing="ij"), -1)
-    model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
-    model.grid_rng = torch.Generator(device=dev).manual_seed(seed)  # same grid updates on all ranks
-
     scene = LegoProxy(n_images=100, img_wh=(800, 800), device=dev, seed=seed)
-    trainer = NGPTrainer(model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, exp_step_factor=0.0)
-    if args.analytic_init:
-        model.density_grid.copy_(scene.occupancy_from_analytic(model))
-        ngp_amd.vren.packbits(model.density_grid.view(-1), 0.5, model.density_bitfield)
-        trainer.global_step = 1024  # past the all-cells warm-up; grid keeps updating every 16 steps
-        trainer.warmup_steps = 0
-    trainer.broadcast_state(0)
+
+    def seeded_trainer(analytic_init):
+        torch.manual_seed(seed)  # identical initial weights on every rank
+        np.random.seed(seed)
+        model = NGP(scale=0.5).to(dev)
+        G = model.grid_size
+        model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=dev))
+        coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=dev)] * 3, indexing="ij"), -1)
+        model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
+        model.grid_rng = torch.Generator(device=dev).manual_seed(seed)  # same grid updates on all ranks
+        trainer = NGPTrainer(model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, exp_step_factor=0.0)
+        if analytic_init:
+            model.density_grid.copy_(scene.occupancy_from_analytic(model))
+            ngp_amd.vren.packbits(model.density_grid.view(-1), 0.5, model.density_bitfield)
+            trainer.global_step = 1024  # past the all-cells warm-up; grid keeps updating every 16 steps
+            trainer.warmup_steps = 0
+        trainer.broadcast_state(0)
+        return model, trainer
+
+    model, trainer = seeded_trainer(args.analytic_init)
 
     ray_gen = torch.Generator(device=dev).manual_seed(shard_seed(seed, rank))
 
@@ -630,6 +688,23 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, scene, args.cpu_rays, args.cpu_samples)
         print(json.dumps(out))
+    if args.dump_outputs:
+        # The timed region starts from hundreds of training steps whose gradient scatters add with float atomics, in an
+        # order that varies; Adam turns the last-bit differences of near-zero gradients into visible ones, so that state
+        # differs from run to run.  The dump therefore runs the timed path's step (NGPTrainer.step, the same options)
+        # from a seeded state — fresh weights, the analytic steady-state occupancy (--analytic-init) — on the timed
+        # region's last two batches, the first marching the second ahead as in the timed region: its outputs are a
+        # function of the arguments and the build, to rounding.  Every rank takes part (collectives of the N > 1 path).
+        _, d_trainer = seeded_trainer(True)
+        d_trainer.adam_width = trainer.adam_width or d_trainer.adam_candidates[0]   # (the result does not depend on it)
+        i = args.warmup + args.steps - 1
+        prev, cur = batches[(i - 1) % len(batches)], batches[i % len(batches)]
+        d_trainer.step(*prev, next_rays=None if args.no_march_ahead else cur[:2])
+        loss, res = d_trainer.step(*cur)
+        torch.cuda.synchronize()
+        if rank == 0:
+            nbytes = dump_outputs(step_outputs(loss, res, cur), args.dump_outputs)
+            print(f"dumped the timed path's step ({nbytes / 1e6:.1f} MB) to {args.dump_outputs}", file=sys.stderr)
     if world > 1 or solo_group:
         dist.barrier()
         dist.destroy_process_group()

@@ -371,3 +371,40 @@ def test_adam_width_measurement_state_machine(ngp, monkeypatch):
     tr = NGPTrainer.__new__(NGPTrainer)                               # a fixed width is never measured
     tr.adam_width = 384
     assert tr._adam_width_now(None) == 384
+
+
+def test_bench_dump_shapes_follow_the_arguments_only(tmp_path):
+    """bench.py --dump-outputs: two steps on the same ray batch that march different numbers of samples write arrays of
+    the same shapes (per-sample results laid out per ray, zero-padded), float32 / float64 only, within 64 MiB"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = np.random.default_rng(5)
+    n_rays = 512
+    batch = tuple(torch.rand(n_rays, 3) for _ in range(3))
+
+    def step(max_count):
+        cnt = g.integers(0, max_count, n_rays)
+        cnt[7] = bench.DUMP_SAMPLES_PER_RAY + 40            # longer than what is kept per ray
+        order = g.permutation(n_rays)                        # segments need not be in ray order
+        start = np.zeros(n_rays, np.int64)
+        start[order] = np.concatenate([[0], np.cumsum(cnt[order])[:-1]])
+        n = int(cnt.sum())
+        rays_a = torch.from_numpy(np.stack([np.arange(n_rays), start, cnt], 1))
+        res = {"rays_a": rays_a, "total_samples": torch.tensor(n), "xyzs": torch.randn(n, 3), "ws": torch.rand(n),
+               "rgb": torch.rand(n_rays, 3), "opacity": torch.rand(n_rays)}
+        return bench.step_outputs(torch.tensor(0.25), res, batch), res
+
+    (a, res_a), (b, _) = step(40), step(90)
+    assert int(res_a["total_samples"]) != int(b["total_samples"][0])
+    assert {k: v.shape for k, v in a.items()} == {k: v.shape for k, v in b.items()}
+    assert all(v.dtype in (np.float32, np.float64) and v.size > 0 for v in a.values())
+    assert a["xyzs"].shape == (n_rays, bench.DUMP_SAMPLES_PER_RAY, 3) and a["ws"].shape == (n_rays, bench.DUMP_SAMPLES_PER_RAY)
+    assert a["loss"].shape == a["total_samples"].shape == (1,) and a["rays_a"].shape == (n_rays, 3)
+    xyzs, ra = res_a["xyzs"].numpy(), res_a["rays_a"].numpy()
+    for r, s, c in ra:
+        k = min(c, bench.DUMP_SAMPLES_PER_RAY)
+        assert np.array_equal(a["xyzs"][r, :k], xyzs[s:s + k]) and not a["xyzs"][r, k:].any()
+    assert bench.dump_outputs(a, str(tmp_path)) <= 64 << 20
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{k}.npy" for k in a)
