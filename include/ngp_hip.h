@@ -516,6 +516,34 @@ int ngp_sumsq_if(const float* x, int64_t n, float* out, const int32_t* flag, voi
 int ngp_clip_coef_if(const float* sumsq, float max_norm, float extra_scale, float* coef, const int32_t* flag,
                      void* stream);
 
+/* ------------------------------------------------------------------------
+ * M1  marching cubes on a dense lattice (mesh export; replaces the reference's extract_mesh.py:
+ *     skimage.measure.marching_cubes, which has no native counterpart there)
+ * volume (nx, ny, nz) f32, C order (z fastest, meshgrid indexing='ij').  A corner is inside iff v > level (NaN and
+ * v == level are outside).  Every lattice point owns its edges toward +x, +y, +z; each owned edge whose ends classify
+ * differently carries exactly one vertex, numbered point-major then x < y < z edge (welded, no atomics: the output is
+ * the same from run to run), at origin + (idx + t*e_axis) * spacing with t = (level-v0)/(v1-v0) clamped by
+ * fmaxf/fminf to [0,1] (NaN -> 0: on its edge even for non-finite inputs).  Triangles are cell-major, in table order
+ * within a cell, wound so that (v1-v0) x (v2-v0) points from inside to outside (toward lower density).  The case
+ * table resolves every ambiguous face by one face-local rule (inside corners are separated): surfaces that do not
+ * touch the volume boundary are closed, consistently oriented 2-manifolds.
+ * Two calls: ngp_mc_count leaves totals[0] = V, totals[1] = F on the device (-1: more than INT32_MAX, and the emit
+ * then writes nothing) and, in workspace (ngp_mc_workspace(nx, ny, nz) int32 elements, host-only query), what
+ * ngp_mc_emit needs; the caller reads the totals back to size verts (V, 3) f32 and faces (F, 3) i32.  origin3 and
+ * spacing3 are HOST arrays of 3 floats.  A lattice with a dimension < 2 is empty (NGP_OK before any pointer is
+ * looked at, nothing written); a negative dimension or nx*ny*nz >= 2^31 is NGP_EINVAL.
+ * ngp_mc_tables (host-only) copies out the case table the kernels use: tri_table (256, 16) edge triples, -1
+ * terminated; tri_count (256) triangles per case; edge_corner (12, 2) the corners each edge joins (low end first).
+ * Corner c of a cell sits at offset (c & 1, c >> 1 & 1, c >> 2 & 1); bit c of the case index is corner c inside.
+ * ---------------------------------------------------------------------- */
+int64_t ngp_mc_workspace(int nx, int ny, int nz);
+int ngp_mc_tables(int8_t* tri_table, int8_t* tri_count, int8_t* edge_corner);
+int ngp_mc_count(const float* volume, int nx, int ny, int nz, float level, int32_t* workspace, int32_t* totals,
+                 void* stream);
+int ngp_mc_emit(const float* volume, int nx, int ny, int nz, float level, const float* origin3 /* host */,
+                const float* spacing3 /* host */, const int32_t* workspace, float* verts, int32_t* faces,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

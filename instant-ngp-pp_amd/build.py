@@ -19,12 +19,13 @@ LIB_ID = LIB + ".id"
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "ngp_hip.h")]
 
 # (source, extra flags).  ray_kernels.hip is compiled without FMA contraction so that the
-# marcher / intersector are bit-identical to the CPU oracle (see the file header).
+# marcher / intersector are bit-identical to the CPU oracle (see the file header); mesh_kernels.hip likewise.
 SOURCES = [
     ("ray_kernels.hip", ["-ffp-contract=off"]),
     ("composite_kernels.hip", []),
     ("grid_kernels.hip", []),
     ("mlp_kernels.hip", []),
+    ("mesh_kernels.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
