@@ -4,9 +4,7 @@ sources so that it travels with the repository snapshot to the GPU box.
 Staleness is decided by CONTENT, not by mtime (a snapshot copy does not keep mtimes in order): every
 object remembers the digest of (source + headers + flags) it was compiled from, and the library carries the
 digest of all of them (`ngp_build_id()`, also written to libngp_hip.so.id) which `_lib.load()` checks against
-the sources it finds — a stale library is rebuilt when hipcc is there and refused when it is not.
-
-NGP_AB_VARIANTS=1 in the environment compiles the superseded kernel variants in as well (tools/*microbench*)."""
+the sources it finds — a stale library is rebuilt when hipcc is there and refused when it is not."""
 import hashlib
 import os
 import shutil
@@ -28,12 +26,6 @@ SOURCES = [
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
-
-
-def _flags():
-    # NGP_EXTRA_DEFS="-DNAME=VALUE ...": compile-time tuning constants for experiments (part of the build id)
-    extra = os.environ.get("NGP_EXTRA_DEFS", "").split()
-    return COMMON + (["-DNGP_AB_VARIANTS"] if os.environ.get("NGP_AB_VARIANTS") else []) + extra
 
 
 def _hipcc():
@@ -61,7 +53,7 @@ def _digest(paths, extra=()):
 def source_id():
     """digest of everything the library is built from (what ngp_build_id() of an up-to-date library returns)"""
     srcs = [os.path.join(CSRC, s) for s, _ in SOURCES] + [os.path.join(CSRC, "build_id.cpp")]
-    extra = _flags() + [f for _, fl in SOURCES for f in fl]
+    extra = COMMON + [f for _, fl in SOURCES for f in fl]
     return _digest(srcs + HEADERS, extra)
 
 
@@ -98,12 +90,12 @@ def _build_locked(want, objdir, force, verbose):
     for src, extra, defs in units:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
-        d = _digest([s] + HEADERS, _flags() + extra + defs)
+        d = _digest([s] + HEADERS, COMMON + extra + defs)
         stamp = o + ".sha"
         have = open(stamp).read().strip() if os.path.exists(stamp) and os.path.exists(o) else None
         if force or have != d:
             tmp_o = o + f".{os.getpid()}.tmp"
-            cmd = [hipcc] + _flags() + extra + defs + ["-c", s, "-o", tmp_o]
+            cmd = [hipcc] + COMMON + extra + defs + ["-c", s, "-o", tmp_o]
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)

@@ -11,17 +11,6 @@
 // and B[k=l>>5][j=l&31]; C/D is col=l&31, row=(r&3)+8*(r>>2)+4*(l>>5).
 // Layers with n_out <= 4 (the density head, networks.py:57) use VALU kernels instead.
 #include "common.h"
-#include <stdlib.h>
-
-// Tuning switches for A/B timing exist in the A/B build only (-DNGP_AB_VARIANTS); the product build reads no environment
-// variable and keeps no other hidden state.
-#ifdef NGP_AB_VARIANTS
-static inline bool ab_flag(const char* name) { return getenv(name) != nullptr; }
-static inline long ab_long(const char* name, long dflt) { const char* e = getenv(name); const long v = e ? atol(e) : 0; return v > 0 ? v : dflt; }
-#else
-static inline constexpr bool ab_flag(const char*) { return false; }
-static inline constexpr long ab_long(const char*, long dflt) { return dflt; }
-#endif
 
 namespace {
 
@@ -52,10 +41,6 @@ struct GemmArgs {
     const float* xf_W2; int64_t xf_ldw2;
     int xf_nout, xf_act;
     float* xf_dW2; int64_t xf_lddw2; float* xf_db2;   // XF WGRAD: also dW2 += dz2^T . hidden, db2 += colsum(dz2)
-#ifdef NGP_AB_VARIANTS
-    int exp;   // diagnostic switches of the streaming weight-gradient kernel (NGP_WGRAD_EXP): 1 no hand-over / atomics,
-               // 4 no operand transform (dz1 := hidden)
-#endif
 };
 
 // softplus(v) = log(1+e^v) with the hardware exp/log (v_exp_f32 / v_log_f32, ~1e-6 relative):
@@ -926,10 +911,7 @@ __global__ void __launch_bounds__(512) mlp_stream_wgrad_kernel(GemmArgs p, int64
     // meet in LDS before the atomics — the 128 x n_in atomic adds per workgroup are a fixed cost (~55 us
     // per launch with two 4-wave workgroups per CU), one 8-wave workgroup per CU halves it at the same occupancy
     extern __shared__ float lds[];
-#ifndef NGP_WGRAD_D
-#define NGP_WGRAD_D 8
-#endif
-    constexpr int D = NGP_WGRAD_D;     // steps (of two samples) the operand loads run ahead of the MFMAs
+    constexpr int D = 8;     // steps (of two samples) the operand loads run ahead of the MFMAs
     // (wave and group numbers as scalars: the chunk bounds, the loop counter and the base pointers then live in SGPRs)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) & 3)),
               grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
@@ -1032,11 +1014,6 @@ __global__ void __launch_bounds__(512) mlp_stream_wgrad_kernel(GemmArgs p, int64
         }
         *d_slot = (t0 + d_s < kend) ? td : 0.0f;
     };
-#ifdef NGP_AB_VARIANTS
-    const int EXP = p.exp;
-#else
-    constexpr int EXP = 0;
-#endif
     issue_turn(kbeg);   // (an empty group reads the clamped row kend - 1 >= 0 and never uses it)
     for (int64_t s0 = kbeg; s0 < kend; s0 += 2 * D) {
         commit_turn(s0);
@@ -1067,9 +1044,6 @@ __global__ void __launch_bounds__(512) mlp_stream_wgrad_kernel(GemmArgs p, int64
 #pragma unroll
             for (int o = 0; o < XF; o++) sum = fmaf(dz[o], w2[o], sum);
             float a = sum * act_grad_fast(hid, ACT1);
-#ifdef NGP_AB_VARIANTS
-            a = (EXP & 4) ? hid : a;
-#endif
             if (W2G) {
 #pragma unroll
                 for (int o = 0; o < XF; o++) {
@@ -1084,17 +1058,6 @@ __global__ void __launch_bounds__(512) mlp_stream_wgrad_kernel(GemmArgs p, int64
         }
     }
     __syncthreads();   // the staging tiles lie inside the regions the hand-over below writes
-    if (EXP & 1) {   // diagnostic: the loop alone (one store keeps the sums alive)
-        float t = gb1;
-#pragma unroll
-        for (int tn = 0; tn < TN; tn++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) t += acc[tn][r];
-#pragma unroll
-        for (int o = 0; o < XF; o++) t += gw[o] + gb2[o];
-        if (t == 123.456f) p.C[lane] = t;
-        return;
-    }
     // ---- the second group hands its sums to the first, lane for lane
     if (two) {
         float* comb = lds + (wave * (TN * 16 + 2 * XF + 1)) * 64 + lane;
@@ -1478,12 +1441,12 @@ __global__ void __launch_bounds__(256) mlp_hidden_bwd_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------- optimizer
-template <int U>   // 16-byte quads per lane and trip
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, float step_size, float beta1, float beta2,
                                                    float eps, float bc2_sqrt, float weight_decay,
                                                    const float* __restrict__ grad_scale, int zero_grad, bool sparse_zero)
 {
+    constexpr int U = 2;   // 16-byte quads per lane and trip
     const float gs = grad_scale ? *grad_scale : 1.0f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t n4 = n >> 2;
@@ -1709,7 +1672,7 @@ void launch_wgrad(GemmArgs p, hipStream_t st)
     const int64_t n = p.K;
     const bool big_m = p.M > 32, big_n = p.N > 32;
     const int64_t tiles = (int64_t)ngp_blocks(p.M, big_m ? 128 : 32) * ngp_blocks(p.N, big_n ? 128 : 32);
-    static const int target_blocks = (int)ab_long("NGP_WGRAD_BLOCKS", 768); // 3 workgroups per CU x 256 CUs
+    constexpr int target_blocks = 768;   // 3 workgroups per CU x 256 CUs
     int64_t splits = target_blocks / (tiles > 0 ? tiles : 1);
     if (splits < 1) splits = 1;
     int64_t chunk = (n + splits - 1) / splits;
@@ -1808,12 +1771,8 @@ static int mlp2_fwd_impl(const float* x, int64_t ldx, const float* W1, int64_t l
     p.f2_W2 = W2; p.f2_ldw2 = ldw2; p.f2_b2 = b2; p.f2_out = out; p.f2_ldo = ldo; p.f2_nout = n_out; p.f2_act = act2;
     p.f2_dact = dact;
     dim3 grid(ngp_blocks(n, 128), 1);
-    static const bool stream_ok = !ab_flag("NGP_MLP_NO_STREAM");
-    const bool wide_ok = H == 128 && (n_in == 128 || n_in == 144 || n_in == 160);
-    // the 32-wide heads are HBM-bound either way (0.062 ms streaming, 0.060 ms tiled): opt-in only
-    static const bool stream_heads = ab_flag("NGP_MLP_STREAM_HEADS");
-    const bool head_ok = stream_heads && H == 32 && n_in == 128;
-    if (stream_ok && (wide_ok || head_ok) && p.vecA && p.vecB &&
+    // (the 32-wide heads are HBM-bound either way, 0.062 ms streaming against 0.060 ms tiled: they take the tiled kernel)
+    if (H == 128 && (n_in == 128 || n_in == 144 || n_in == 160) && p.vecA && p.vecB &&
         (act1 == NGP_ACT_RELU || act1 == NGP_ACT_SOFTPLUS) && aligned16(hidden) && ldh % 4 == 0 &&
         n <= (int64_t)32 * 0x7fffff00) {
         // streaming kernel: W1 resident in LDS, workgroups of 8 waves, 32-row tiles per wave.
@@ -1821,7 +1780,7 @@ static int mlp2_fwd_impl(const float* x, int64_t ldx, const float* W1, int64_t l
         // sits in (the test-time renderer's two loops are compared bit for bit)
         const int n_tiles = (int)((n + 31) / 32);
         const int f2 = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);
-        static const int nw = (int)ab_long("NGP_MLP_NW_FWD", ab_long("NGP_MLP_NW", 8));   // waves per workgroup (A/B: 4)
+        constexpr int nw = 8;   // waves per workgroup
         const size_t lds = (size_t)(H * (n_in + 4) + f2 * H + H + 8 + nw * 1024) * sizeof(float);
         static int n_cu = 0;
         if (!n_cu) {
@@ -1830,9 +1789,7 @@ static int mlp2_fwd_impl(const float* x, int64_t ldx, const float* W1, int64_t l
             if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
             n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         }
-        // one workgroup per CU for the 128-wide layers (W1 takes half the LDS), two for the 32-wide heads
-        static const int wg_rounds_f = (int)ab_long("NGP_MLP_WG_ROUNDS_FWD", ab_long("NGP_MLP_WG_ROUNDS", 1));   // A/B: k workgroups per CU, one after the other
-        const int max_blocks = n_cu * (H == 128 ? 1 : 2) * wg_rounds_f;
+        const int max_blocks = n_cu;   // one workgroup per CU (W1 takes half the LDS)
         const int blocks = (n_tiles + nw - 1) / nw < max_blocks ? (n_tiles + nw - 1) / nw : max_blocks;
 #define LAUNCH_STREAM(F2V, KQV, ACTV, TNV)                                                                              \
     do {                                                                                                                \
@@ -1852,8 +1809,7 @@ static int mlp2_fwd_impl(const float* x, int64_t ldx, const float* W1, int64_t l
     } while (0)
 #define LAUNCH_STREAM_K(F2V)                                                                                            \
     do {                                                                                                                \
-        if (H == 32) LAUNCH_STREAM_A(F2V, 16, 1);                                                                       \
-        else if (n_in == 128) LAUNCH_STREAM_A(F2V, 16, 4);                                                              \
+        if (n_in == 128) LAUNCH_STREAM_A(F2V, 16, 4);                                                                   \
         else if (n_in == 144) LAUNCH_STREAM_A(F2V, 18, 4);                                                              \
         else LAUNCH_STREAM_A(F2V, 20, 4);                                                                               \
     } while (0)
@@ -1987,8 +1943,7 @@ int ngp_mlp_bwd_input(const float* dz2, int64_t lddz2, const float* W2, int64_t 
     p.M = n; p.N = n_in; p.K = H; p.accumulate = accumulate;
     p.vecA = aligned16(hidden) && (ldh % 4 == 0); p.vecB = aligned16(W1) && (ldw1 % 4 == 0);
     p.xf_dz2 = dz2; p.xf_lddz2 = lddz2; p.xf_W2 = W2; p.xf_ldw2 = ldw2; p.xf_nout = n_out; p.xf_act = act1;
-    static const bool stream_ok = !ab_flag("NGP_MLP_NO_STREAM");
-    if (stream_ok && H == 128 && n_in == 128 && !accumulate && p.vecA && aligned16(dx) && lddx % 4 == 0 &&
+    if (H == 128 && n_in == 128 && !accumulate && p.vecA && aligned16(dx) && lddx % 4 == 0 &&
         (act1 == NGP_ACT_RELU || act1 == NGP_ACT_SOFTPLUS) && n <= (int64_t)32 * 0x7fffff00) {
         // streaming kernel (chosen by shape only, see ngp_mlp2_fwd); out-of-range xf_nout columns read as zero,
         // but the dz2 prefetch reads XF floats per row: stay inside the row
@@ -2001,9 +1956,8 @@ int ngp_mlp_bwd_input(const float* dz2, int64_t lddz2, const float* W2, int64_t 
             if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
             n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         }
-        static const int nw = (int)ab_long("NGP_MLP_NW_DGRAD", ab_long("NGP_MLP_NW", 8));
-        static const int wg_rounds_d = (int)ab_long("NGP_MLP_WG_ROUNDS_DGRAD", ab_long("NGP_MLP_WG_ROUNDS", 1));
-        const int cap_d = n_cu * wg_rounds_d;
+        constexpr int nw = 8;   // waves per workgroup, one workgroup per CU
+        const int cap_d = n_cu;
         const int blocks = (n_tiles + nw - 1) / nw < cap_d ? (n_tiles + nw - 1) / nw : cap_d;
 #define LAUNCH_SD(XFV, ACTV)                                                                                            \
     do {                                                                                                                \
@@ -2051,12 +2005,7 @@ int ngp_mlp_bwd_weight(const float* dz2, int64_t lddz2, const float* W2, int64_t
     p.vecA = aligned16(hidden) && (ldh % 4 == 0); p.vecB = aligned16(x) && (ldx % 4 == 0);
     p.xf_dz2 = dz2; p.xf_lddz2 = lddz2; p.xf_W2 = W2; p.xf_ldw2 = ldw2; p.xf_nout = n_out; p.xf_act = act1;
     p.xf_dW2 = dW2; p.xf_lddw2 = lddw2; p.xf_db2 = db2;
-#ifdef NGP_AB_VARIANTS
-    static const int wgrad_exp = getenv("NGP_WGRAD_EXP") ? atoi(getenv("NGP_WGRAD_EXP")) : 0;
-    p.exp = wgrad_exp;
-#endif
-    static const bool stream_ok = !ab_flag("NGP_MLP_NO_STREAM") && !ab_flag("NGP_MLP_NO_STREAM_WGRAD");
-    if (stream_ok && H == 128 && (n_in == 128 || n_in == 144 || n_in == 160) && p.vecA && p.vecB &&
+    if (H == 128 && (n_in == 128 || n_in == 144 || n_in == 160) && p.vecA && p.vecB &&
         (act1 == NGP_ACT_RELU || act1 == NGP_ACT_SOFTPLUS)) {
         hipStream_t st = (hipStream_t)stream;
         static int n_cu = 0;
@@ -2071,12 +2020,10 @@ int ngp_mlp_bwd_weight(const float* dz2, int64_t lddz2, const float* W2, int64_t
         // samples one turn of the prefetch ring covers
         // ONE 4-wave workgroup per CU (a wave per SIMD): alone the kernel is ~10 % slower than with 8 waves per CU
         // (0.38 -> 0.41-0.43 ms in the step), but it runs beside the gradient scatter, and what the scatter's waves
-        // get of the CU is worth more to the step (-2.5 %, profiles/r03_occupancy_shaping.txt); NGP_WGRAD_WPC=9: the
-        // round's earlier shape (8 waves per CU) for the A/B
-        static const int wpc_env = (int)ab_long("NGP_WGRAD_WPC", 1);
-        const int wpc = wpc_env == 9 ? 0 : wpc_env;
-        const int threads = (n_in == 128 && !wpc) ? 512 : 256;
-        int64_t blocks = (int64_t)n_cu * (wpc ? wpc : (threads == 512 ? 1 : 2));
+        // get of the CU is worth more to the step (-2.5 %, profiles/r03_occupancy_shaping.txt)
+        constexpr int threads = 256;
+        const size_t lds = (size_t)4 * 2048 * sizeof(float);   // the 4-wave workgroup's staging tiles
+        int64_t blocks = n_cu;
         int64_t chunk = ((n + blocks - 1) / blocks + 31) / 32 * 32;
         if (chunk < 128) chunk = 128;
         {   // the kernel addresses a chunk with 32-bit byte offsets: keep (chunk + 32) rows of the widest operand below 2^31
@@ -2090,7 +2037,6 @@ int ngp_mlp_bwd_weight(const float* dz2, int64_t lddz2, const float* W2, int64_t
 #define LAUNCH_SW2(XFV, ACTV, TNV, W2GV)                                                                                \
     do {                                                                                                                \
         static bool attr_set = false;                                                                                   \
-        const size_t lds = (size_t)4 * (threads == 512 ? (TNV * 16 + 2 * XFV + 1) * 64 : 2048) * sizeof(float);         \
         if (!attr_set) {                                                                                                \
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_stream_wgrad_kernel<XFV, ACTV, TNV, W2GV>),      \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)               \
@@ -2156,25 +2102,12 @@ int ngp_adam_step_width(float* param, float* grad, float* exp_avg, float* exp_av
     // takes 1.5-1.7 instead of 1.1-1.4 ms, the colour chain follows alone).  Which is faster per step depends on the loop and
     // the box (+-3 %: profiles/r03_occupancy_shaping.txt (1), (9)), so the caller may name the width:
     // NGPTrainer times both in its own loop and keeps the faster one.
-    static const int64_t cap_default = ab_long("NGP_ADAM_BLOCKS", 512);
-    const int64_t cap = workgroups > 0 ? workgroups : cap_default;
+    const int64_t cap = workgroups > 0 ? workgroups : 512;
     int64_t blocks = ((n >> 2) + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > cap) blocks = cap;
-    static const bool sparse_zero = !ab_flag("NGP_ADAM_DENSE_ZERO");
-    static const int unroll = (int)ab_long("NGP_ADAM_UNROLL", 2);
-#define LAUNCH_ADAM(U)                                                                                                  \
-    hipLaunchKernelGGL(adam_kernel<U>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, \
-                       exp_avg_sq, n, step_size, beta1, beta2, eps, bc2_sqrt, weight_decay, grad_scale, zero_grad,      \
-                       sparse_zero)
-#ifdef NGP_AB_VARIANTS
-    if (unroll == 4) LAUNCH_ADAM(4);
-    else if (unroll == 3) LAUNCH_ADAM(3);
-    else
-#endif
-        LAUNCH_ADAM(2);
-    (void)unroll;
-#undef LAUNCH_ADAM
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                       exp_avg_sq, n, step_size, beta1, beta2, eps, bc2_sqrt, weight_decay, grad_scale, zero_grad, true);
     return ngp_check_launch();
 }
 

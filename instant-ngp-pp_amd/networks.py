@@ -72,31 +72,20 @@ class _LinearAct(Function):
 
 _RELU, _NONE = 1, 0
 
-import os as _os
-
-_OVERLAP = _os.environ.get("NGP_NO_OVERLAP", "0") != "1"
-_HEADS_BESIDE = _os.environ.get("NGP_NO_HEADS_BESIDE", "0") != "1"   # A/B switch: the two heads on a stream of their own beside rgb_net (-0.03 ms/step)
-_FUSED_FWD = _os.environ.get("NGP_NO_FUSED_FWD", "0") != "1"   # A/B switch for ngp_mlp2_fwd
-_FUSED_BWD = _os.environ.get("NGP_NO_FUSED_BWD", "0") != "1"   # A/B switch for the operand-transform products
-# the library's streaming weight-gradient kernel (mlp_stream_wgrad_kernel) is on unless one of its A/B switches is set
-_SORT_GRID_SAMPLES = _os.environ.get("NGP_NO_SORT_GRID_SAMPLES", "0") != "1"   # A/B: Morton-sorted occupancy-update points
-_REUSE_DSIG_DFEAT = _os.environ.get("NGP_NO_REUSE_DFEAT", "0") != "1"           # A/B: second data-gradient product of the density head
-_FUSED_GRID_UPDATE = _os.environ.get("NGP_GRID_UPDATE_TORCH", "0") != "1"       # A/B: the torch-op route of the sampled update
-_STREAM_WGRAD = not (_os.environ.get("NGP_MLP_NO_STREAM") or _os.environ.get("NGP_MLP_NO_STREAM_WGRAD"))
 # widest second layer that takes the fused route (tools/mlp_bwd_microbench.py, n = 433 k, MI355X):
 # density head 0.54 -> 0.49 ms, rgb_net 0.60 -> 0.57 ms, 32-wide headers 0.22 -> 0.22 ms
-_FUSED_BWD_MAX_OUT = int(_os.environ.get("NGP_FUSED_BWD_MAX_OUT", "3"))
+_FUSED_BWD_MAX_OUT = 3
+# Per-device default streams of the field: the colour branch of the forward (_SIDE_FWD), the backward's table scatters
+# (_SIDE) and the two 32-wide heads of the forward (_HEADS).  A model that carries its own `_side_stream` /
+# `_heads_stream` (NGPTrainer sets them) uses those instead.
 _SIDE = {}
 _SIDE_FWD = {}
-_FWD_OVERLAP = _os.environ.get("NGP_NO_FWD_OVERLAP", "0") != "1"   # A/B: the colour branch of the forward on its own stream
 # Colour branch on the live samples only (those up to their ray's early-termination point).  Exact and tested, but
 # OFF by default: on the proxy scene 19 % of the samples are behind a stop, the step gains 0.05 ms in steady state
 # (the forward gains nothing — the colour branch cannot start before sigma is known and becomes the longer chain —
 # the backward loses 19 % of its colour-branch work) and the whole 20k-step schedule loses 1-4 % (no ray stops early
-# in the first epochs, the host-side count and the three index launches cost the same).  NGP_COMPACT=1 or
+# in the first epochs, the host-side count and the three index launches cost the same).
 # model.compact_dead_samples = True switches it on: scenes with solid interiors have far more dead samples.
-_COMPACT = _os.environ.get("NGP_COMPACT", "0") == "1"
-_SCATTER_AFTER_DGRAD = _os.environ.get("NGP_SCATTER_AFTER_DGRAD", "0") == "1"   # A/B: density scatter held back behind the colour data gradient
 
 
 _PINNED = {}
@@ -134,7 +123,7 @@ def _side_stream(dev):
     key = torch.device(dev).index
     st = _SIDE.get(key)
     if st is None:
-        st = _SIDE[key] = torch.cuda.Stream(device=dev, priority=int(_os.environ.get("NGP_SIDE_PRIO", "0")))
+        st = _SIDE[key] = torch.cuda.Stream(device=dev)
     return st
 
 
@@ -153,7 +142,7 @@ class _Mlp2Bwd:
         n = hidden.shape[0]
         dev = hidden.device
         self.n = n
-        self.fused = bool(_FUSED_BWD and n_out <= _FUSED_BWD_MAX_OUT and d_out.stride(0) == n_out and ld_out == n_out)
+        self.fused = bool(n_out <= _FUSED_BWD_MAX_OUT and d_out.stride(0) == n_out and ld_out == n_out)
         self.dz1 = None
         self.dw2_done = False
         if self.fused:
@@ -196,7 +185,7 @@ class _Mlp2Bwd:
         if self.fused:
             dz2 = self.dz2
             # the first-layer weight product streams dz2 and hidden anyway: it also leaves dW2 / db2
-            if wide and _STREAM_WGRAD and H == 128 and n_in in (144, 160) and act1 in (_RELU, _SOFTPLUS):
+            if wide and H == 128 and n_in in (144, 160) and act1 in (_RELU, _SOFTPLUS):
                 # the streaming kernel takes all 144 / 160 input columns (and dW2 / db2) in one pass
                 call("mlp_bwd_weight", dz2, n_out, W2, H, hidden, H, act1, x_in, ld_in, n, n_in, H, n_out, dW1, ldw1, db1,
                      dW2, H, db2)
@@ -310,7 +299,7 @@ class _FieldFn(Function):
         # word while the device works on the analytic normals.
         live = getattr(model, "_live_ctx", None)
         want = getattr(model, "compact_dead_samples", None)
-        compact = bool((_COMPACT if want is None else want) and live is not None and n > 0 and embed_a is None
+        compact = bool(want and live is not None and n > 0 and embed_a is None
                        and x.is_cuda and not ctx.needs_input_grad[1])
         # every buffer comes from the caller's stream (the allocator then knows them as that stream's; the colour
         # stream below only launches into them and is joined before anything is returned)
@@ -322,8 +311,7 @@ class _FieldFn(Function):
         rgb_o = torch.empty(n, 3, dtype=_f32, device=dev)
         np_o = torch.empty(n, 3, dtype=_f32, device=dev)
         sem_o = torch.empty(n, C, dtype=_f32, device=dev)
-        dz2 = torch.empty(n, 1, dtype=_f32, device=dev) if _FUSED_BWD else None
-        dz1 = None if _FUSED_BWD else torch.empty(n, 128, dtype=_f32, device=dev)
+        dz2 = torch.empty(n, 1, dtype=_f32, device=dev)
         net = model.rgb_net
         bufs = {}
 
@@ -357,12 +345,13 @@ class _FieldFn(Function):
                 rgb_in[:, 144:K] = embed_a
             if Kp > K:
                 rgb_in[:, K:] = 1.0
-            heads = None
-            if _HEADS_BESIDE and _FUSED_FWD and C <= 8 and x.is_cuda:
+            if C <= 8 and x.is_cuda:
                 # the two 32-wide heads read the same rows as rgb_net: on a stream of their own their 256-thread
-                # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU
+                # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU (-0.03 ms/step)
                 cur = torch.cuda.current_stream()
-                heads = _heads_stream(dev)
+                heads = getattr(model, "_heads_stream", None)
+                if heads is None:
+                    heads = _heads_stream(dev)
                 heads.wait_stream(cur)
                 with torch.cuda.stream(heads):
                     call("mlp2_fwd", feat_rgb, Kp, nrm_p, 128, None, _RELU, nrm_p[32 * 128:], 32, None, _NONE,
@@ -372,24 +361,17 @@ class _FieldFn(Function):
                 call("mlp2_fwd", rgb_in, Kp, rgb_p, Kp, None, _RELU, rgb_p[128 * Kp:], 128, None, net.output_activation,
                      n, Kp, 128, 3, a_r, 128, rgb_o, 3)
                 cur.wait_stream(heads)
-            elif _FUSED_FWD:
+            else:
                 call("mlp2_fwd", rgb_in, Kp, rgb_p, Kp, None, _RELU, rgb_p[128 * Kp:], 128, None, net.output_activation,
                      n, Kp, 128, 3, a_r, 128, rgb_o, 3)
                 call("mlp2_fwd", feat_rgb, Kp, nrm_p, 128, None, _RELU, nrm_p[32 * 128:], 32, None, _NONE,
                      n, 128, 32, 3, a_n, 32, np_o, 3)
-            else:
-                call("linear_fwd", rgb_in, Kp, rgb_p, Kp, None, n, Kp, 128, _RELU, a_r, 128, None)
-                call("linear_fwd", a_r, 128, rgb_p[128 * Kp:], 128, None, n, 128, 3, net.output_activation, rgb_o, 3, None)
-                call("linear_fwd", feat_rgb, Kp, nrm_p, 128, None, n, 128, 32, _RELU, a_n, 32, None)
-                call("linear_fwd", a_n, 32, nrm_p[32 * 128:], 32, None, n, 32, 3, _NONE, np_o, 3, None)
-            if heads is not None:
-                pass
-            elif _FUSED_FWD and C <= 8:
-                call("mlp2_fwd", feat_rgb, Kp, sem_p, 128, None, _RELU, sem_p[32 * 128:], 32, None, _NONE,
-                     n, 128, 32, C, a_s, 32, sem_o, C)
-            else:
-                call("linear_fwd", feat_rgb, Kp, sem_p, 128, None, n, 128, 32, _RELU, a_s, 32, None)
-                call("linear_fwd", a_s, 32, sem_p[32 * 128:], 32, None, n, 32, C, _NONE, sem_o, C, None)
+                if C <= 8:
+                    call("mlp2_fwd", feat_rgb, Kp, sem_p, 128, None, _RELU, sem_p[32 * 128:], 32, None, _NONE,
+                         n, 128, 32, C, a_s, 32, sem_o, C)
+                else:   # (the fused forward's epilogue takes at most 8 outputs)
+                    call("linear_fwd", feat_rgb, Kp, sem_p, 128, None, n, 128, 32, _RELU, a_s, 32, None)
+                    call("linear_fwd", a_s, 32, sem_p[32 * 128:], 32, None, n, 32, C, _NONE, sem_o, C, None)
             if compact:   # back to sample order, zeros behind the stops
                 call("spread_rows3", rgb_o, 3, bufs["rgb_o"], np_o, 3, bufs["np_o"], sem_o, C, bufs["sem_o"],
                      bufs["inv_idx"], bufs["n_full"])
@@ -400,7 +382,7 @@ class _FieldFn(Function):
         # path and the analytic normals (which are stretched beyond that piece's end on one stream).  (Compacted: it
         # also needs the list of live rows, i.e. sigma — it starts behind the density head, beside the normals.)
         main = torch.cuda.current_stream()
-        side = _fwd_stream(dev) if (_FWD_OVERLAP and x.is_cuda) else None
+        side = _fwd_stream(dev) if x.is_cuda else None
         if side is not None and not compact:
             colour_buffers(n)
             side.wait_stream(main)
@@ -411,16 +393,10 @@ class _FieldFn(Function):
         if ev_p is not None:
             ev_p.wait()
         call("grid_fwd", xe.desc, xyz_table, xn, n, feat, 128)
-        if _FUSED_FWD and _FUSED_BWD:
-            # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
-            # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
-            call("mlp2_fwd_dact", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig, 1,
-                 dz2)
-        elif _FUSED_FWD:
-            call("mlp2_fwd", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig, 1)
-        else:
-            call("linear_fwd", feat, 128, W1, 128, b1, n, 128, 128, _SOFTPLUS, a1, 128, None)
-            call("linear_fwd", a1, 128, W2, 128, b2, n, 128, 1, _SOFTPLUS, sig, 1, None)
+        # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
+        # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
+        call("mlp2_fwd_dact", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig, 1,
+             dz2)
         live_ev = None
         if compact:
             rays_a, deltas, T_thr = live
@@ -439,14 +415,7 @@ class _FieldFn(Function):
             live_ev = torch.cuda.Event()
             live_ev.record(main)
         # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
-        if _FUSED_BWD:
-            if not _FUSED_FWD:
-                call("act_bwd", None, sig, n, _SOFTPLUS, dz2)      # upstream gradient = ones
-            call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
-        else:
-            call("mlp_hidden_bwd", None, 0, sig, 1, _SOFTPLUS, W2, 128, a1, 128, _SOFTPLUS, n, 128, 1, None, 0, dz1, 128,
-                 None, 0, None)
-            call("linear_bwd_input", dz1, 128, W1, 128, n, 128, 128, dfeat, 128, 0)
+        call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
         call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, grads)
         # dfeat = d(sigma)/d(features) is kept: the density head has ONE output, so the gradient the backward
         # sends into the density encoder is d_sigma[s] * dfeat[s] — no second data-gradient product there
@@ -513,7 +482,9 @@ class _FieldFn(Function):
         # The density scatter can start at once: its input is d_sigma[s] * d(sigma)/d(features)[s], and the second
         # factor was computed (and kept) by the forward pass for the analytic normals.
         main = torch.cuda.current_stream()
-        side = _side_stream(dev) if _OVERLAP else None
+        side = getattr(model, "_side_stream", None)
+        if side is None:
+            side = _side_stream(dev)
         forked = False
         ev = getattr(model, "_acc_zeroed", None)   # the trainer clears its norm accumulators behind the Adam launches
         if ev is not None:
@@ -537,7 +508,7 @@ class _FieldFn(Function):
                 return buf, buf
             return buf, None
 
-        reuse = d_sig is not None and _REUSE_DSIG_DFEAT and not need[1]
+        reuse = d_sig is not None and not need[1]
         if reuse and need[4]:
             d_sig_c = d_sig.contiguous()
             buf, g_xyz = table_buffer(xe, xyz_table)
@@ -554,16 +525,14 @@ class _FieldFn(Function):
             # One GPU: the density scatter leads on the side stream and is let loose at once.  It becomes ready together
             # with the colour branch's data gradient, and whichever reaches the CUs first keeps them (the product takes
             # 0.15 ms when its 256 large workgroups are placed first, 0.4-0.6 ms behind the scatter's thousands of
-            # small ones).  Holding the scatter back behind the product (NGP_SCATTER_AFTER_DGRAD=1) makes that
-            # deterministic and is still the slower schedule: +0.04 ms/step (A/B, 3 alternations of 100 steps), the
-            # scatters are the longer path and every microsecond they start later is lost.
-            density_after_dgrad = not density_later and d_rgb is not None and _SCATTER_AFTER_DGRAD
-            if not density_later and not density_after_dgrad:
+            # small ones).  Holding the scatter back behind the product makes that deterministic and is the slower
+            # schedule: +0.04 ms/step (3 alternations of 100 steps), the scatters are the longer path and every
+            # microsecond they start later is lost.
+            if not density_later:
                 on_side(density_scatter)
                 density_scatter = None
         else:
             density_scatter = None
-            density_after_dgrad = False
 
         # ---- colour branch (rgb_net + the two heads): data gradients w.r.t. [grid features | appearance code] first
         # (compacted forward: the branch's activations hold the live rows only; the upstream gradients are brought
@@ -612,9 +581,6 @@ class _FieldFn(Function):
             else:
                 g_sem = g_p
 
-        if density_after_dgrad and density_scatter is not None:
-            on_side(density_scatter)
-            density_scatter = None
         if dfeat_rgb is not None and need[9]:
             buf_c, g_rgbt = table_buffer(re, rgb_table)
 
@@ -907,12 +873,11 @@ class NGP(nn.Module):
             indices2 = torch.where(n_occ > 0, pos.clamp(max=occ.numel() - 1), indices1)
             coords2 = vren.morton3D_invert(indices2.int())
             indices, coords = torch.cat([indices1, indices2]), torch.cat([coords1, coords2])
-            if _SORT_GRID_SAMPLES:
-                # Morton order: neighbouring points share hash-grid cells at the coarse levels, so the 1 M
-                # point gather of density() runs out of L2 instead of HBM (which cell receives which jitter
-                # draw changes, their distribution does not)
-                indices, perm = torch.sort(indices)
-                coords = coords[perm]
+            # Morton order: neighbouring points share hash-grid cells at the coarse levels, so the 1 M
+            # point gather of density() runs out of L2 instead of HBM (which cell receives which jitter
+            # draw changes, their distribution does not)
+            indices, perm = torch.sort(indices)
+            coords = coords[perm]
             cells += [(indices, coords)]
         return cells
 
@@ -978,7 +943,7 @@ class NGP(nn.Module):
 
     @torch.no_grad()
     def update_density_grid(self, density_threshold, warmup=False, decay=0.95, erode=False):
-        if not warmup and not erode and _FUSED_GRID_UPDATE and self.density_grid.is_cuda:
+        if not warmup and not erode and self.density_grid.is_cuda:
             return self._update_density_grid_sampled(density_threshold, decay)
         density_grid_tmp = torch.zeros_like(self.density_grid)
         if warmup:

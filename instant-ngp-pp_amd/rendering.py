@@ -60,7 +60,7 @@ class MarchAhead:
     was marched with (the trainer does not march across a density-grid update)."""
 
     def __init__(self, device):
-        self.stream = torch.cuda.Stream(device=device, priority=int(_os.environ.get("NGP_MARCH_PRIO", "0")))
+        self.stream = torch.cuda.Stream(device=device)
         self.count_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.pending = None
 
@@ -144,15 +144,11 @@ def render_dense(model, rays_o, rays_d, z_vals, **kwargs):
     return out
 
 
-import os as _os
-
-_REFERENCE_TEST_LOOP = _os.environ.get("NGP_REFERENCE_TEST_LOOP", "0") == "1"
-# NGP_DEVICE_ROUNDS=1 / render(..., device_rounds=True): loop head, alive compaction and sample count on the device, no
-# host round trip per round (volume_render_device_rounds).  Off by default: an 800x800 frame is 34 rounds of ~1.7 ms of
-# field kernels each (tools/rounds_probe.py), the one host sync per round costs ~2 % of the frame, and without the exact
-# row count on the host the field evaluates up to N_rays rows per round instead of N_alive * N_samples (measured 61.6 ms
-# per frame against 55.3 for the host-driven loop).
-_DEVICE_ROUNDS = _os.environ.get("NGP_DEVICE_ROUNDS", "0") == "1"
+# render(..., device_rounds=True): loop head, alive compaction and sample count on the device, no host round trip per
+# round (volume_render_device_rounds).  Off by default: an 800x800 frame is 34 rounds of ~1.7 ms of field kernels each
+# (tools/rounds_probe.py), the one host sync per round costs ~2 % of the frame, and without the exact row count on the
+# host the field evaluates up to N_rays rows per round instead of N_alive * N_samples (measured 61.6 ms per frame against
+# 55.3 for the host-driven loop).
 
 
 def volume_render(model, rays_o, rays_d, hits_t, opacity, depth, rgb, normal_pred, normal_raw, sem, **kwargs):
@@ -166,11 +162,11 @@ def volume_render(model, rays_o, rays_d, hits_t, opacity, depth, rgb, normal_pre
     padding rows are zeros, 6 % of the slots on the proxy scene, the compositor reads the first
     N_eff samples of a ray only, and a field row does not depend on the other rows of the batch, so
     every per-ray result is bit-identical — which leaves ~25 launches and one sync per round.
-    `volume_render_reference` keeps the literal loop (NGP_REFERENCE_TEST_LOOP=1 selects it)."""
-    if _REFERENCE_TEST_LOOP or kwargs.get('reference_test_loop', False):
+    `volume_render_reference` keeps the literal loop (reference_test_loop=True selects it)."""
+    if kwargs.get('reference_test_loop', False):
         return volume_render_reference(model, rays_o, rays_d, hits_t, opacity, depth, rgb, normal_pred, normal_raw,
                                        sem, **kwargs)
-    if (_DEVICE_ROUNDS or kwargs.get('device_rounds', False)) and rays_o.is_cuda and len(rays_o) > 0:
+    if kwargs.get('device_rounds', False) and rays_o.is_cuda and len(rays_o) > 0:
         return volume_render_device_rounds(model, rays_o, rays_d, hits_t, opacity, depth, rgb, normal_pred, normal_raw,
                                            sem, **kwargs)
     N_rays = len(rays_o)
@@ -223,7 +219,7 @@ def volume_render_device_rounds(model, rays_o, rays_d, hits_t, opacity, depth, r
     marcher / compositor take the exact sizes from the device, and the field evaluates the (few) padding rows beyond
     N_alive * N_samples on zero inputs whose results nobody reads.  Per-ray results are bit-identical to the host-driven
     loop above and to volume_render_reference (same schedule, same samples, row results independent of the batch).
-    Opt-in (see _DEVICE_ROUNDS): the frame is bound by its field kernels, not by the round trips."""
+    Opt-in (see the note above volume_render): the frame is bound by its field kernels, not by the round trips."""
     N_rays = len(rays_o)
     device = rays_o.device
     exp_step_factor = kwargs.get('exp_step_factor', 0.)

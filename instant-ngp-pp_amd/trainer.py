@@ -177,8 +177,8 @@ class NGPTrainer:
         self.loss_kwargs = dict(loss_kwargs or {})
         optional = any(self.loss_kwargs.get(k) for k in ("normal_ref", "normal_mono", "semantic", "depth_mono", "embed_msk"))
         self.fused_loss = not optional   # default recipe (rgb + opacity + distortion); False -> NeRFLoss module
-        # NGP_NO_FUSED_TAIL=1 (A/B): the launch-per-operation tail (normals, softmax, compositor, RefLoss, distortion, loss)
-        self.fused_tail = os.environ.get("NGP_NO_FUSED_TAIL", "0") != "1" 
+        # False: the launch-per-operation tail (normals, softmax, compositor, RefLoss, distortion, loss)
+        self.fused_tail = True
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -198,23 +198,18 @@ class NGPTrainer:
         self._tune_events, self._tune_widths = [], []
         self._grad_zeroed = None
         self._flatten()
-        # NGP_SERIAL_OPT=1 (A/B): clip + Adam on the caller's stream instead of the optimizer stream
-        serial = os.environ.get("NGP_SERIAL_OPT", "0") == "1"
-        self._opt_stream = (torch.cuda.current_stream(self.flat_param.device) if serial
-                            else torch.cuda.Stream(device=self.flat_param.device,
-                                                   priority=int(os.environ.get("NGP_OPT_PRIO", "0")))
-                            ) if self.flat_param.is_cuda else None
+        self._opt_stream = torch.cuda.Stream(device=self.flat_param.device) if self.flat_param.is_cuda else None
         self._march_ahead = MarchAhead(self.flat_param.device) if self.flat_param.is_cuda else None
-        if self.flat_param.is_cuda and not serial and not self.sharded and os.environ.get("NGP_SIX_STREAMS", "0") != "1":
+        if self.flat_param.is_cuda and not self.sharded:
             # Four streams, one per hardware queue of the HIP runtime's default pool: the caller's, the colour forward's, the
-            # optimizer's and the march-ahead's.  The backward's table scatters go on the optimizer stream (clip + Adam follow them
-            # there anyway) and the two heads on the march-ahead stream (idle in the middle of the forward) instead of streams of
-            # their own: with six streams two pairs share a queue, and which pairs depends on the order the streams were created
-            # in — the scatter behind the caller's MLP kernels would cost 0.4 ms per step.  Same speed as the six-stream layout
-            # that happened to come out right (profiles/r03_occupancy_shaping.txt (12); NGP_SIX_STREAMS=1 for the A/B).
-            from . import networks
-            networks._SIDE[self.flat_param.device.index] = self._opt_stream
-            networks._HEADS[self.flat_param.device.index] = self._march_ahead.stream
+            # optimizer's and the march-ahead's.  The backward's table scatters of THIS trainer's model go on the optimizer
+            # stream (clip + Adam follow them there anyway) and its two heads on the march-ahead stream (idle in the middle of
+            # the forward) instead of streams of their own: with six streams two pairs share a queue, and which pairs depends
+            # on the order the streams were created in — the scatter behind the caller's MLP kernels would cost 0.4 ms per
+            # step.  Same speed as the six-stream layout that happened to come out right (profiles/r03_occupancy_shaping.txt
+            # (12)).
+            model._side_stream = self._opt_stream
+            model._heads_stream = self._march_ahead.stream
 
     # ------------------------------------------------------------------ flat parameter store
     def _flatten(self):
@@ -268,8 +263,7 @@ class NGPTrainer:
         # the field's weight products accumulate straight into these views of the flat gradient
         # (networks._FieldFn.backward); autograd then has nothing to add for them
         m = self.model
-        import os as _os
-        if hasattr(m, "xyz_net") and hasattr(m, "rgb_net") and _os.environ.get("NGP_NO_GRAD_SINKS", "0") != "1":
+        if hasattr(m, "xyz_net") and hasattr(m, "rgb_net"):
             lin1, lin2 = m.xyz_net[0], m.xyz_net[2]
             m._grad_sinks = {"W1": lin1.weight.grad, "b1": lin1.bias.grad, "W2": lin2.weight.grad, "b2": lin2.bias.grad,
                              "rgb_p": m.rgb_net.params.grad, "nrm_p": m.norm_pred_header.params.grad,
@@ -284,8 +278,7 @@ class NGPTrainer:
         if self.hooked0:
             self.model.rgb_encoder.on_grad_ready = lambda: self.buckets.reduce_scatter_bucket(0, self.grad_shard[0])
             self.model.rgb_encoder.grad_ready_is_collective = True   # the field's backward then scatters colour first
-        elif (hasattr(self.model, "rgb_encoder") and b0 and dev.type == "cuda" and not self.sharded
-              and os.environ.get("NGP_NO_EARLY_NORM", "0") != "1"):
+        elif hasattr(self.model, "rgb_encoder") and b0 and dev.type == "cuda" and not self.sharded:
             # one GPU: the colour table's share of the gradient norm (77 % of the entries) is summed
             # right behind its scatter, beside the density head's backward, instead of on the path
             # between the last scatter and Adam
@@ -294,8 +287,7 @@ class NGPTrainer:
         self._mlp_lo = 0
         if self.names[:2] == ["rgb_encoder.params", "xyz_encoder.params"] and len(self.names) > 2:
             self._mlp_lo = self.slices[self.names[2]][0]
-        self.norm_bound = bool(self._mlp_lo and dev.type == "cuda" and not self.sharded and hasattr(self.model, "xyz_net")
-                               and os.environ.get("NGP_NO_NORM_BOUND", "0") != "1")
+        self.norm_bound = bool(self._mlp_lo and dev.type == "cuda" and not self.sharded and hasattr(self.model, "xyz_net"))
         self._bound_step = False
         self._norm_share_armed = False   # step() arms it: exactly one backward per optimizer step
         self._norm_share_fired = 0

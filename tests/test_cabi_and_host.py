@@ -311,13 +311,34 @@ def test_product_build_asm_loads_are_covered(ngp, tmp_path):
 
 
 def test_product_library_reads_no_environment(ngp):
-    """include/ngp_hip.h: "the product build reads NO environment variable" — the shared object must not even import
-    getenv (A/B switches are compiled in with -DNGP_AB_VARIANTS only)."""
-    if os.environ.get("NGP_AB_VARIANTS"):
-        pytest.skip("A/B build")
+    """include/ngp_hip.h: "the library reads no environment variable" — the shared object must not even import getenv."""
     ngp._lib.load()
     out = subprocess.check_output(["nm", "-D", ngp._lib.LIB_PATH], text=True)
     assert "getenv" not in out
+
+
+def test_sources_have_one_code_path_per_job():
+    """No compile-time or environment switch selects between kernel variants, and the package's Python reads only the
+    environment variables of the distributed launch (torch.distributed's and NGP_DIST_BACKEND / NGP_FORCE_SHARDED, which
+    bench.py and the data-parallel tests set) and NGP_ADAM_WIDTH."""
+    import re
+    native = [os.path.join(d, f) for d in (os.path.join(ROOT, "instant-ngp-pp_amd", "csrc"), os.path.join(ROOT, "include"))
+              for f in sorted(os.listdir(d))]
+    for path in native:
+        src = open(path).read()
+        assert "getenv" not in src and "NGP_AB_VARIANTS" not in src, path
+    keep = {"NGP_FORCE_SHARDED", "NGP_DIST_BACKEND", "NGP_ADAM_WIDTH",
+            "MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"}
+    pkg = os.path.join(ROOT, "instant-ngp-pp_amd")
+    py = [os.path.join(ROOT, "ngp_amd.py")] + [os.path.join(r, f) for r, _, fs in os.walk(pkg) for f in fs if f.endswith(".py")]
+    read = set()
+    for path in py:
+        src = open(path).read()
+        keys = re.findall(r"""(?:environ\.get|environ\.setdefault|environ\.pop|getenv)\(\s*["']([^"']+)["']|environ\[\s*["']([^"']+)["']""", src)
+        # every mention of the environment is a read of a literal key the pattern above sees
+        assert len(keys) == len(re.findall(r"\b(?:environ|getenv)\b", src)), path
+        read |= {a or b for a, b in keys}
+    assert read <= keep, sorted(read - keep)
 
 
 def test_adam_width_measurement_state_machine(ngp, monkeypatch):

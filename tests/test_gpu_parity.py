@@ -1287,6 +1287,36 @@ def test_trainer_steps_reduce_loss(ngp):
     assert model.rgb_encoder.params.data_ptr() == tr.flat_param.data_ptr()
 
 
+def test_trainer_streams_belong_to_its_model(ngp, monkeypatch):
+    """Each NGPTrainer hands its optimizer stream (the backward's table scatters) and its march-ahead stream (the two
+    32-wide heads of the forward) to ITS model only: a second trainer on the same device does not take over the first
+    model's launches, and the first model still trains."""
+    from ngp_amd import networks
+    from ngp_amd.synthetic import LegoProxy
+    from ngp_amd.trainer import NGPTrainer
+    model_a, model_b = _grid_model(ngp, seed=3), _grid_model(ngp, seed=4)
+    tr_a = NGPTrainer(model_a, lr=1e-2)
+    tr_b = NGPTrainer(model_b, lr=1e-2)
+    launches = []
+    real_call = networks.call
+
+    def recording_call(name, *args):
+        launches.append((name, torch.cuda.current_stream().cuda_stream))
+        return real_call(name, *args)
+    monkeypatch.setattr(networks, "call", recording_call)
+    scene = LegoProxy(n_images=20, img_wh=(200, 200), device=DEV)
+    img, pix = scene.sample_batch(1024, generator=torch.Generator(device=DEV).manual_seed(5))
+    o, d = scene.rays(img, pix)
+    gt, _ = scene.ground_truth(o, d, n_quad=64)
+    loss, _ = tr_a.step(o, d, gt)
+    tr_a.wait()
+    torch.cuda.synchronize()
+    assert torch.isfinite(loss) and torch.isfinite(tr_a.flat_param).all()
+    assert {st for name, st in launches if name.startswith("grid_bwd_param")} == {tr_a._opt_stream.cuda_stream}
+    assert tr_a._march_ahead.stream.cuda_stream in {st for name, st in launches if name == "mlp2_fwd"}
+    assert not {tr_b._opt_stream.cuda_stream, tr_b._march_ahead.stream.cuda_stream} & {st for _, st in launches}
+
+
 def test_trainer_march_ahead_matches_inline(ngp):
     """Marching batch k+1 on the side stream under step k (MarchAhead) gives the same training run
     as marching every batch inside its own step: identical sample counts (the marcher is
@@ -2321,7 +2351,7 @@ def test_fused_sampled_grid_update_matches_torch_formulas(ngp):
         diff = np.unpackbits(mine ^ bits, bitorder="little").astype(bool)
         assert not (diff & ~near).any(), int((diff & ~near).sum())
         assert (N(want) < 0).sum() > 1000 and np.array_equal(N(model.density_grid[0])[N(want) < 0], N(want)[N(want) < 0])
-    # the torch-op route (NGP_GRID_UPDATE_TORCH=1) and the fused one agree on what an update does to the statistics
+    # the torch-op route (warmup / erode) and the fused one agree on what an update does to the statistics
     frac_fused = float((model.density_grid > min(float(model.density_grid[model.density_grid > 0].mean()), thr0)).float().mean())
     assert 0.0 < frac_fused < 1.0
 
@@ -2704,7 +2734,7 @@ def test_live_rows_match_compositor_stops(ngp, full_batch):
 
 
 def test_compacted_colour_branch_matches_full(ngp, full_batch):
-    """render() with the colour branch on the live samples only (model.compact_dead_samples / NGP_COMPACT=1) against
+    """render() with the colour branch on the live samples only (model.compact_dead_samples) against
     the same step with it on every sample (the default): identical per-ray results — a row's bits do not depend on its position in the batch —
     and gradients equal up to the summation order of the weight products and the atomics."""
     from ngp_amd.rendering import render

@@ -4,7 +4,6 @@ training steps with the switch off / on (box-to-box and run-to-run spread of ben
 changes are worth; alternating inside one process removes it).
 
     python tools/ab_step.py fused_tail            # NGPTrainer attribute toggled False / True
-    python tools/ab_step.py env:NGP_X             # os.environ switch toggled unset / "1" (only for switches read per call)
     AB_WINDOWS=12 AB_STEPS=40 python tools/ab_step.py fused_tail"""
 import os
 import sys
@@ -47,13 +46,7 @@ for _ in range(int(os.environ.get("AB_PRETRAIN", "600"))):
 
 
 def set_switch(on):
-    if what.startswith("env:"):
-        if on:
-            os.environ[what[4:]] = "1"
-        else:
-            os.environ.pop(what[4:], None)
-    else:
-        setattr(tr, what, on)
+    setattr(tr, what, on)
 
 
 def window(i0):

@@ -70,7 +70,7 @@ def seq(*fs):
 
 
 ts, tg, ta = timeit(scatter), timeit(gemms), timeit(adam)
-print(f"NGP_ADAM_BLOCKS={os.environ.get('NGP_ADAM_BLOCKS', '2048')}: scatter {ts:.3f}  wgrad+dgrad {tg:.3f}  adam {ta:.3f} ms")
+print(f"scatter {ts:.3f}  wgrad+dgrad {tg:.3f}  adam {ta:.3f} ms")
 print(f"  scatter || adam          : {timeit(par(scatter, adam)):.3f} ms  (sequential {ts+ta:.3f})")
 print(f"  gemms   || adam          : {timeit(par(gemms, adam)):.3f} ms  (sequential {tg+ta:.3f})")
 print(f"  gemms+scatter || adam    : {timeit(par(seq(gemms, scatter), adam)):.3f} ms  (sequential {tg+ts+ta:.3f})")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """2-layer MLP forward: linear_fwd (MFMA) + linear_fwd (skinny) against ngp_mlp2_fwd, with a check
-against fp64.  NGP_MLP_NO_STREAM=1 selects the tiled kernel instead of the streaming one.  GPU only."""
+against fp64.  GPU only."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""ngp_mlp_bwd_weight (fused hidden-layer weight gradient + dW2 / db2 / db1) against fp64, with timing.
-NGP_MLP_NO_STREAM=1 selects the tiled kernels instead of the streaming one.  GPU only."""
+"""ngp_mlp_bwd_weight (fused hidden-layer weight gradient + dW2 / db2 / db1) against fp64, with timing.  GPU only."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

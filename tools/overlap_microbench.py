@@ -54,7 +54,5 @@ def both():
     main.wait_stream(side)
 
 
-for cap in ("0", "20000", "40000", "60000", "80000", "120000"):
-    os.environ["NGP_SCATTER_LDS"] = cap
-    ts, tg, tb = timeit(scatter), timeit(gemms), timeit(both)
-    print(f"lds_cap={cap:>6s}: scatter {ts:.3f} ms, 3 gemms {tg:.3f} ms, sequential {ts+tg:.3f} ms, overlapped {tb:.3f} ms")
+ts, tg, tb = timeit(scatter), timeit(gemms), timeit(both)
+print(f"scatter {ts:.3f} ms, 3 gemms {tg:.3f} ms, sequential {ts+tg:.3f} ms, overlapped {tb:.3f} ms")

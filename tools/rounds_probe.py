@@ -1,5 +1,5 @@
 import os, sys, time, json
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, ngp_amd
 from ngp_amd.networks import NGP
 from ngp_amd.synthetic import LegoProxy

@@ -45,7 +45,7 @@ dev = torch.device("cuda", 0)
 torch.manual_seed(20220806)
 steps = int(os.environ.get("CAP_STEPS", "400"))
 reps = int(os.environ.get("REPS", "5"))
-cap_file = os.environ.get("CAP_FILE")   # captured launches are kept here: later runs (other variants) only replay
+cap_file = os.environ.get("CAP_FILE")   # captured launches are kept here: later runs only replay
 
 
 def replay(launches):
