@@ -10,8 +10,11 @@ grids with T=2^19 (density) / 2^21 (colour), fp32.  Data parallel = weak scaling
 its own 8192 rays).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed inside the timed region) and, at N=1, `cpu_baseline` (the CPU oracle's noCUDA
-render path on the host cores).
+HIP-event timed inside the timed region).  A plain run does only set-up, warm-up, the timed steps and
+--dump-outputs.  With --full it then measures what takes runs of its own: the other kernels over
+untimed steps after the timed region (`mlp_mfma`, `comm`), further windows of the same steps, cache-cold
+solo replays of the captured launches and, at N=1, `cpu_baseline` (the CPU oracle's noCUDA render path
+on the host cores).
 """
 import argparse
 import json
@@ -55,12 +58,15 @@ def parse():
     ap.add_argument("--pretrain", type=int, default=600,
                     help="untimed training steps run during setup so that the occupancy grid and the field are in "
                          "the steady-state regime the reference spends >98 %% of its 20k steps in")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need: the other kernels, "
+                         "further windows, solo replays, communication and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-march-ahead", action="store_true", help="march every batch inside its own step")
     ap.add_argument("--step-times", action="store_true", help="print the host time of every timed step to stderr")
     ap.add_argument("--windows", type=int, default=5,
-                    help="further untimed-by-contract windows of --steps steps after the timed region (spread of the figure)")
-    ap.add_argument("--no-solo", action="store_true", help="skip the cache-cold solo replays of the captured launches")
+                    help="(--full) further untimed-by-contract windows of --steps steps after the timed region (spread of the figure)")
+    ap.add_argument("--no-solo", action="store_true", help="(--full) skip the cache-cold solo replays of the captured launches")
     ap.add_argument("--cpu-rays", type=int, default=1024)
     ap.add_argument("--cpu-samples", type=int, default=64)
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -379,7 +385,8 @@ def main():
     # HIP events around EVERY library call of the step cost 2.4 % of the step (measured A/B): inside the timed region only
     # the candidates for "dominant kernel" are bracketed — the two hash-grid gathers (3 launches per step), the table
     # scatter (2) and the clip + Adam sweep (2): 7 of ~55 launches, 14 events per step.  Whichever took most device time per
-    # step in the timed region is the `roofline` kernel; the MLP products' figures come from a short untimed pass after it.
+    # step in the timed region is the `roofline` kernel; the MLP products' figures come from a short untimed pass after it
+    # (--full).
     LIVE = ("grid_fwd", "grid_bwd_input", "grid_bwd_param", "adam_step")   # "grid_bwd_param" collects both scatter entry points
     prof_keys = ("linear_fwd", "linear_bwd_input", "linear_bwd_weight", "mlp_bwd_input", "mlp_bwd_weight", "mlp2_fwd",
                  "mlp2_fwd_dact", "sumsq")   # (mlp2_fwd_dact = the density head's forward: the same kernel, one more output)
@@ -392,93 +399,94 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    prof_live, _lib.PROFILE = _lib.PROFILE, {k: [] for k in prof_keys}
+    prof_live, _lib.PROFILE = _lib.PROFILE, None
     updates_in_region = sum(1 for g in range(step_at_start, step_at_start + args.steps) if g % trainer.update_interval == 0)
-    post_steps = min(8, args.steps)
-    trainer.buckets.trace = []
-    run(post_steps, args.warmup + args.steps, False)
-    torch.cuda.synchronize()
-    comm_trace, trainer.buckets.trace = trainer.buckets.trace, None
-    prof, _lib.PROFILE = _lib.PROFILE, None      # the windows and replays below are timed on their own
-    # the timed region is short (K steps of ~4 ms): further windows of the same K steps, each between two device
-    # synchronisations, say how the region's figure sits in the run-to-run spread (reported, never the `value`)
-    windows = []
-    pos = args.warmup + args.steps + post_steps
-    for _ in range(args.windows):
+    prof, post_steps, windows, solo, comm = {}, 0, [], {}, None
+    if args.full:
+        _lib.PROFILE = {k: [] for k in prof_keys}
+        post_steps = min(8, args.steps)
+        trainer.buckets.trace = []
+        run(post_steps, args.warmup + args.steps, False)
         torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        tw = time.perf_counter()
-        run(args.steps, pos, False)
-        torch.cuda.synchronize()
-        windows.append((time.perf_counter() - tw) / args.steps * 1e3)
-        pos += args.steps
-    # SOLO rates: one more untimed step with the arguments of the gather / scatter / MLP launches captured, then every one
-    # of them replayed alone on an idle device.  In the step these kernels share the memory system with whatever runs on
-    # the other streams (the scatters run beside the MLP weight products, the density gather beside the Adam sweep), so
-    # their in-step durations say how the schedule shares the device, the solo ones what the kernel itself does.  Every
-    # repetition is timed on its own behind a 1 GiB fill: tables (174 / 588 MB) and activations start in HBM, not in the
-    # 256 MiB Infinity Cache (back-to-back replays of one launch read above the HBM peak).
-    solo_keys = SCATTER_CALLS + ("mlp_bwd_input", "mlp_bwd_weight", "mlp2_fwd", "mlp2_fwd_dact", "grid_fwd", "grid_bwd_input")
-    solo = {}
-    if world == 1 and not args.no_solo:
-        extra = 0
-        if trainer.global_step % trainer.update_interval == 0:   # not a step that starts with an occupancy update
-            run(1, pos, False)
-            extra = 1
-        _lib.CAPTURE = {k: [] for k in solo_keys}
-        run(1, pos + extra, False)
-        trainer.wait()
-        torch.cuda.synchronize()
-        cap, _lib.CAPTURE = _lib.CAPTURE, None
-        flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)   # 1 GiB
-        for name, calls in cap.items():
-            for a in calls:
-                _lib.call(name, *a)               # once untimed (code / TLB warm)
-                reps = []
-                for _ in range(3):
-                    flush.fill_(1.0)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    _lib.call(name, *a)
-                    e1.record()
-                    torch.cuda.synchronize()
-                    reps.append(e0.elapsed_time(e1))
-                key = "grid_bwd_param" if name in SCATTER_CALLS else ("mlp2_fwd" if name == "mlp2_fwd_dact" else name)
-                solo.setdefault(key, []).append((sorted(reps)[1], tuple(x for x in a if isinstance(x, int))))
-        del flush
-    # multi-GPU readiness: what every rank sent through the backend per step, and behind which HIP stream
-    main_stream = torch.cuda.current_stream().cuda_stream
-    per_step = {}
-    for ev in comm_trace:
-        key = (ev["op"], ev["bucket"], ev["stream"])
-        acc = per_step.setdefault(key, [0.0, 0.0, 0])
-        acc[0] += ev["bytes"] / post_steps
-        if "events" in ev:
-            acc[1] += ev["events"][0].elapsed_time(ev["events"][1])
-            acc[2] += 1
-    comm = {"backend": (dist.get_backend() if dist.is_initialized() else None), "world_size": world,
-            "sharded_optimizer": bool(trainer.sharded),
-            "per_step": [{"op": op, "bucket": b, "MB": round(v[0] / 1e6, 3),
-                          "ms": (round(v[1] / v[2], 4) if v[2] else None),
-                          # payload / time, and the bus bandwidth of a ring / direct reduce-scatter or all-gather of that payload
-                          "GBps": (round(v[0] * post_steps / v[2] / (v[1] / v[2] * 1e-3) / 1e9, 2) if v[2] and v[1] > 0 else None),
-                          "bus_GBps": (round((world - 1) / max(world, 1) * v[0] * post_steps / v[2] / (v[1] / v[2] * 1e-3) / 1e9, 2)
-                                       if v[2] and v[1] > 0 else None),
-                          "enqueued_behind": "main stream" if st == main_stream else f"side stream {st:#x}"}
-                         for (op, b, st), v in sorted(per_step.items())],
-            "note": "ms: HIP events on the issuing stream around each collective in the traced steps behind the timed region, "
-                    "where every collective is waited for at once (its own duration, not the overlapped schedule)"}
-    if world > 1 or solo_group:
-        try:
-            rccl = ".".join(str(v) for v in torch.cuda.nccl.version()) if backend == "nccl" else "n/a"
-        except Exception:
-            rccl = "unknown"
-        print(f"[rank {rank}] {comm['backend']} world size {dist.get_world_size()} (RCCL {rccl}), "
-              f"sharded optimizer {trainer.sharded}; per step: " +
-              "; ".join(f"{c['op']} bucket {c['bucket']} {c['MB']} MB {c['ms']} ms ({c['bus_GBps']} GB/s bus) behind {c['enqueued_behind']}"
-                        for c in comm["per_step"]),
-              file=sys.stderr, flush=True)
+        comm_trace, trainer.buckets.trace = trainer.buckets.trace, None
+        prof, _lib.PROFILE = _lib.PROFILE, None      # the windows and replays below are timed on their own
+        # the timed region is short (K steps of ~4 ms): further windows of the same K steps, each between two device
+        # synchronisations, say how the region's figure sits in the run-to-run spread (reported, never the `value`)
+        pos = args.warmup + args.steps + post_steps
+        for _ in range(args.windows):
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            tw = time.perf_counter()
+            run(args.steps, pos, False)
+            torch.cuda.synchronize()
+            windows.append((time.perf_counter() - tw) / args.steps * 1e3)
+            pos += args.steps
+        # SOLO rates: one more untimed step with the arguments of the gather / scatter / MLP launches captured, then every one
+        # of them replayed alone on an idle device.  In the step these kernels share the memory system with whatever runs on
+        # the other streams (the scatters run beside the MLP weight products, the density gather beside the Adam sweep), so
+        # their in-step durations say how the schedule shares the device, the solo ones what the kernel itself does.  Every
+        # repetition is timed on its own behind a 1 GiB fill: tables (174 / 588 MB) and activations start in HBM, not in the
+        # 256 MiB Infinity Cache (back-to-back replays of one launch read above the HBM peak).
+        solo_keys = SCATTER_CALLS + ("mlp_bwd_input", "mlp_bwd_weight", "mlp2_fwd", "mlp2_fwd_dact", "grid_fwd", "grid_bwd_input")
+        if world == 1 and not args.no_solo:
+            extra = 0
+            if trainer.global_step % trainer.update_interval == 0:   # not a step that starts with an occupancy update
+                run(1, pos, False)
+                extra = 1
+            _lib.CAPTURE = {k: [] for k in solo_keys}
+            run(1, pos + extra, False)
+            trainer.wait()
+            torch.cuda.synchronize()
+            cap, _lib.CAPTURE = _lib.CAPTURE, None
+            flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)   # 1 GiB
+            for name, calls in cap.items():
+                for a in calls:
+                    _lib.call(name, *a)               # once untimed (code / TLB warm)
+                    reps = []
+                    for _ in range(3):
+                        flush.fill_(1.0)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        _lib.call(name, *a)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        reps.append(e0.elapsed_time(e1))
+                    key = "grid_bwd_param" if name in SCATTER_CALLS else ("mlp2_fwd" if name == "mlp2_fwd_dact" else name)
+                    solo.setdefault(key, []).append((sorted(reps)[1], tuple(x for x in a if isinstance(x, int))))
+            del flush
+        # multi-GPU readiness: what every rank sent through the backend per step, and behind which HIP stream
+        main_stream = torch.cuda.current_stream().cuda_stream
+        per_step = {}
+        for ev in comm_trace:
+            key = (ev["op"], ev["bucket"], ev["stream"])
+            acc = per_step.setdefault(key, [0.0, 0.0, 0])
+            acc[0] += ev["bytes"] / post_steps
+            if "events" in ev:
+                acc[1] += ev["events"][0].elapsed_time(ev["events"][1])
+                acc[2] += 1
+        comm = {"backend": (dist.get_backend() if dist.is_initialized() else None), "world_size": world,
+                "sharded_optimizer": bool(trainer.sharded),
+                "per_step": [{"op": op, "bucket": b, "MB": round(v[0] / 1e6, 3),
+                              "ms": (round(v[1] / v[2], 4) if v[2] else None),
+                              # payload / time, and the bus bandwidth of a ring / direct reduce-scatter or all-gather of that payload
+                              "GBps": (round(v[0] * post_steps / v[2] / (v[1] / v[2] * 1e-3) / 1e9, 2) if v[2] and v[1] > 0 else None),
+                              "bus_GBps": (round((world - 1) / max(world, 1) * v[0] * post_steps / v[2] / (v[1] / v[2] * 1e-3) / 1e9, 2)
+                                           if v[2] and v[1] > 0 else None),
+                              "enqueued_behind": "main stream" if st == main_stream else f"side stream {st:#x}"}
+                             for (op, b, st), v in sorted(per_step.items())],
+                "note": "ms: HIP events on the issuing stream around each collective in the traced steps behind the timed region, "
+                        "where every collective is waited for at once (its own duration, not the overlapped schedule)"}
+        if world > 1 or solo_group:
+            try:
+                rccl = ".".join(str(v) for v in torch.cuda.nccl.version()) if backend == "nccl" else "n/a"
+            except Exception:
+                rccl = "unknown"
+            print(f"[rank {rank}] {comm['backend']} world size {dist.get_world_size()} (RCCL {rccl}), "
+                  f"sharded optimizer {trainer.sharded}; per step: " +
+                  "; ".join(f"{c['op']} bucket {c['bucket']} {c['MB']} MB {c['ms']} ms ({c['bus_GBps']} GB/s bus) behind {c['enqueued_behind']}"
+                            for c in comm["per_step"]),
+                  file=sys.stderr, flush=True)
     prof.update(prof_live)
     # the field calls the scaled entry point, other callers the plain one: one kernel, one entry in the tables
     prof["grid_bwd_param"] = [ev for k in SCATTER_CALLS for ev in prof.pop(k, [])]
@@ -554,11 +562,11 @@ def main():
             kern[name]["ms_per_step"] = kern[name]["total_ms"] / kern[name]["steps"]
         grid_names = [k for k in kern if k.startswith("grid")]
         # dominant kernel = most device time per step among the kernels bracketed INSIDE the timed region (the gathers,
-        # the scatter, the clip + Adam sweep); `heaviest_kernel_per_step` is the same maximum over every kernel measured
-        # (the MLP products come from the post-region pass) — the two must agree, and the line says so
+        # the scatter, the clip + Adam sweep); with --full, `heaviest_kernel_per_step` is the same maximum over every kernel
+        # measured (the MLP products come from the post-region pass) — the two must agree, and the line says so
         live = [k for k in LIVE if k in kern]
         dom = max(live, key=lambda k: kern[k]["ms_per_step"])
-        heaviest = max(kern, key=lambda k: kern[k]["ms_per_step"])
+        heaviest = max(kern, key=lambda k: kern[k]["ms_per_step"]) if args.full else None
         # HBM traffic per launch from the committed rocprofv3 --pmc passes over this same command
         # (profiles/rNN_pmc_traffic.json, tools/pmc_traffic.py), ONE definition everywhere: 2 x FETCH_SIZE + WRITE_SIZE
         # (MI355X_MICROARCH.md §HBM: gfx950 tallies 128-byte read requests at 64 bytes; WRITE_SIZE is exact for fp32
@@ -685,7 +693,7 @@ def main():
             "comm": comm,
             "kernels": kern,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, scene, args.cpu_rays, args.cpu_samples)
         print(json.dumps(out))
     if args.dump_outputs:

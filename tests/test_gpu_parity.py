@@ -1875,16 +1875,16 @@ def test_one_rank_rccl_sharded_training_matches_unsharded():
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the fields the driver and the judge read (a short run:
+    """bench.py --full prints ONE JSON line with the fields the driver and the judge read (a short run:
     20 set-up steps, 1 warm-up, 3 timed; the CPU baseline leg included with a small sample), and
-    --dump-outputs writes the timed path's step as float32 / float64 arrays, at most 64 MiB in all, that a second run
-    with the same arguments reproduces to rounding."""
+    --dump-outputs writes the timed path's step as float32 / float64 arrays, at most 64 MiB in all, that a plain
+    run (headline figures only, otherwise the same arguments) reproduces to rounding."""
     import json
     import subprocess
     dump = tmp_path / "outputs"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--pretrain", "20",
-           "--cpu-rays", "64", "--cpu-samples", "16", "--dump-outputs"]
-    out = subprocess.run(cmd + [str(dump)], capture_output=True, text=True, timeout=600)
+           "--cpu-rays", "64", "--cpu-samples", "16"]
+    out = subprocess.run(cmd + ["--full", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1917,8 +1917,15 @@ def test_bench_line_contract(tmp_path):
     full = counts <= arrays["ws"].shape[1]          # rays whose samples all fit: their weights sum to the opacity
     np.testing.assert_allclose(arrays["ws"][full].sum(1), arrays["opacity"][full], rtol=1e-4, atol=1e-5)
     again = tmp_path / "again"
-    out = subprocess.run(cmd + [str(again)], capture_output=True, text=True, timeout=600)
+    out = subprocess.run(cmd + ["--dump-outputs", str(again)], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    p = json.loads(lines[0])
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+        assert p[k] == d[k], k
+    assert p["value"] > 0 and abs(p["value"] - 8192 * 3 / (p["ms_per_step"] * 3e-3)) < 1e-3 * p["value"]
+    assert "cpu_baseline" not in p and p["mlp_mfma"] is None and p["ms_per_step_windows"] == []
     assert sorted(os.listdir(again)) == sorted(os.listdir(dump))
     for name, a in arrays.items():
         b = np.load(again / f"{name}.npy")

@@ -5,7 +5,7 @@ duration, queue and the idle gap on the device before it.  Also prints the busy/
 
 usage: timeline.py <kernel_trace.csv> [steps_from_end=3]
        timeline.py <kernel_trace.csv> region <K> [skip]   per-kernel time over K steps ending `skip` steps before the end
-                                                          (bench.py: 40 timed steps, then 8 untimed ones with all kernels bracketed)
+                                                          (bench.py --full: 40 timed steps, then 8 untimed ones with all kernels bracketed)
        timeline.py <kernel_trace.csv> update [skip]  the last step that contains a density-grid update (packbits), at least
                                                      `skip` steps before the end (bench.py's trailing steps are bracketed
                                                      with events and the very last one follows a device synchronisation:
