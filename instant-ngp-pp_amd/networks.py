@@ -80,24 +80,6 @@ _FUSED_BWD_MAX_OUT = 3
 # `_heads_stream` (NGPTrainer sets them) uses those instead.
 _SIDE = {}
 _SIDE_FWD = {}
-# Colour branch on the live samples only (those up to their ray's early-termination point).  Exact and tested, but
-# OFF by default: on the proxy scene 19 % of the samples are behind a stop, the step gains 0.05 ms in steady state
-# (the forward gains nothing — the colour branch cannot start before sigma is known and becomes the longer chain —
-# the backward loses 19 % of its colour-branch work) and the whole 20k-step schedule loses 1-4 % (no ray stops early
-# in the first epochs, the host-side count and the three index launches cost the same).
-# model.compact_dead_samples = True switches it on: scenes with solid interiors have far more dead samples.
-
-
-_PINNED = {}
-
-
-def _pinned_word(dev):
-    """one pinned int32 per device: the landing place of a device-side count the host has to read"""
-    key = torch.device(dev).index
-    t = _PINNED.get(key)
-    if t is None:
-        t = _PINNED[key] = torch.zeros(1, dtype=torch.int32).pin_memory()
-    return t
 
 
 def _fwd_stream(dev):
@@ -292,15 +274,6 @@ class _FieldFn(Function):
         # for a piece where it first reads that piece's parameters
         ev_p, ev_c = getattr(model, "_params_ready", None), getattr(model, "_rgb_params_ready", None)
         model._params_ready = model._rgb_params_ready = None
-        # Samples behind their ray's early-termination point take no part in the image and get no gradient: when the
-        # renderer hands over the rays' segments (model._live_ctx), the colour branch and its backward run on the
-        # live samples only.  The density head needs every sample (the stop depends on sigma); the list of live rows
-        # comes from the compositor's own bookkeeping (ngp_live_rows), its length reaches the host through a pinned
-        # word while the device works on the analytic normals.
-        live = getattr(model, "_live_ctx", None)
-        want = getattr(model, "compact_dead_samples", None)
-        compact = bool(want and live is not None and n > 0 and embed_a is None
-                       and x.is_cuda and not ctx.needs_input_grad[1])
         # every buffer comes from the caller's stream (the allocator then knows them as that stream's; the colour
         # stream below only launches into them and is joined before anything is returned)
         feat = torch.empty(n, 128, dtype=_f32, device=dev)
@@ -312,29 +285,15 @@ class _FieldFn(Function):
         np_o = torch.empty(n, 3, dtype=_f32, device=dev)
         sem_o = torch.empty(n, C, dtype=_f32, device=dev)
         dz2 = torch.empty(n, 1, dtype=_f32, device=dev)
+        rgb_in = torch.empty(n, Kp, dtype=_f32, device=dev)
+        a_r = torch.empty(n, 128, dtype=_f32, device=dev)
+        a_n = torch.empty(n, 32, dtype=_f32, device=dev)
+        a_s = torch.empty(n, 32, dtype=_f32, device=dev)
         net = model.rgb_net
-        bufs = {}
-
-        def colour_buffers(m):
-            bufs["rgb_in"] = torch.empty(m, Kp, dtype=_f32, device=dev)
-            bufs["a_r"] = torch.empty(m, 128, dtype=_f32, device=dev)
-            bufs["a_n"] = torch.empty(m, 32, dtype=_f32, device=dev)
-            bufs["a_s"] = torch.empty(m, 32, dtype=_f32, device=dev)
-            if compact:   # compacted outputs; rgb_o / np_o / sem_o are filled from them
-                bufs["rgb_c"] = torch.empty(m, 3, dtype=_f32, device=dev)
-                bufs["np_c"] = torch.empty(m, 3, dtype=_f32, device=dev)
-                bufs["sem_c"] = torch.empty(m, C, dtype=_f32, device=dev)
 
         def colour_branch():
             # [SH(16) | rgb grid features (128) | appearance code (E) | ones-padding] -> rgb_net, the two heads
-            n, rgb_in, a_r, a_n, a_s = bufs["n"], bufs["rgb_in"], bufs["a_r"], bufs["a_n"], bufs["a_s"]
             feat_rgb = rgb_in[:, 16:144]
-            if compact:   # (positions and directions came over with the list, see ngp_live_rows)
-                xn, d = bufs["xn_c"][:n], bufs["d_c"][:n]
-                rgb_o, np_o, sem_o = bufs["rgb_c"], bufs["np_c"], bufs["sem_c"]
-            else:
-                xn, d = bufs["xn_full"], bufs["d_full"]
-                rgb_o, np_o, sem_o = bufs["rgb_o"], bufs["np_o"], bufs["sem_o"]
             call("sh_fwd_dirs", d, n, 4, rgb_in, Kp)
             if ev_c is not None:
                 ev_c.wait()   # the colour table's piece (the stream this runs on waits for it)
@@ -372,19 +331,13 @@ class _FieldFn(Function):
                 else:   # (the fused forward's epilogue takes at most 8 outputs)
                     call("linear_fwd", feat_rgb, Kp, sem_p, 128, None, n, 128, 32, _RELU, a_s, 32, None)
                     call("linear_fwd", a_s, 32, sem_p[32 * 128:], 32, None, n, 32, C, _NONE, sem_o, C, None)
-            if compact:   # back to sample order, zeros behind the stops
-                call("spread_rows3", rgb_o, 3, bufs["rgb_o"], np_o, 3, bufs["np_o"], sem_o, C, bufs["sem_o"],
-                     bufs["inv_idx"], bufs["n_full"])
 
-        bufs.update(xn_full=xn, d_full=d, rgb_o=rgb_o, np_o=np_o, sem_o=sem_o, n_full=n, n=n)
         # The colour branch needs the positions and the colour table, nothing of the density path: it runs on a
         # stream of its own from the moment the colour table's Adam piece is done, beside the rest of the density
-        # path and the analytic normals (which are stretched beyond that piece's end on one stream).  (Compacted: it
-        # also needs the list of live rows, i.e. sigma — it starts behind the density head, beside the normals.)
+        # path and the analytic normals (which are stretched beyond that piece's end on one stream).
         main = torch.cuda.current_stream()
         side = _fwd_stream(dev) if x.is_cuda else None
-        if side is not None and not compact:
-            colour_buffers(n)
+        if side is not None:
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 colour_branch()
@@ -397,54 +350,19 @@ class _FieldFn(Function):
         # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
         call("mlp2_fwd_dact", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig, 1,
              dz2)
-        live_ev = None
-        if compact:
-            rays_a, deltas, T_thr = live
-            n_rays = rays_a.shape[0]
-            offsets = torch.empty(n_rays, dtype=torch.int32, device=dev)
-            bufs["live_idx"] = torch.empty(n, dtype=torch.int32, device=dev)
-            # -1 = "not in the list": ngp_live_rows writes only the rows its rays_a segments cover, the spread kernels read all n
-            bufs["inv_idx"] = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            n_live_dev = torch.empty(1, dtype=torch.int32, device=dev)
-            bufs["xn_c"] = torch.empty(n, 3, dtype=_f32, device=dev)   # the first n_live rows are used
-            bufs["d_c"] = torch.empty(n, 3, dtype=_f32, device=dev)
-            call("live_rows", sig, deltas.contiguous(), rays_a, float(T_thr), n_rays, offsets, bufs["live_idx"],
-                 bufs["inv_idx"], n_live_dev, xn, bufs["xn_c"], d, bufs["d_c"])
-            n_live_host = _pinned_word(dev)
-            n_live_host.copy_(n_live_dev, non_blocking=True)
-            live_ev = torch.cuda.Event()
-            live_ev.record(main)
         # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
         call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
         call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, grads)
         # dfeat = d(sigma)/d(features) is kept: the density head has ONE output, so the gradient the backward
         # sends into the density encoder is d_sigma[s] * dfeat[s] — no second data-gradient product there
 
-        if compact:
-            # the host learns the number of live rows while the device is busy with the normals (and the optimizer
-            # stream with the colour table); the colour branch is then enqueued with exactly that many rows
-            live_ev.synchronize()
-            n_c = int(n_live_host[0])
-            bufs["n"] = n_c
-            colour_buffers(n_c)
-            if side is not None:
-                side.wait_event(live_ev)
-                with torch.cuda.stream(side):
-                    colour_branch()
-            else:
-                colour_branch()
         if side is not None:
             main.wait_stream(side)
-        elif not compact:
-            colour_buffers(n)
+        else:
             colour_branch()
-        rgb_in, a_r, a_n, a_s = bufs["rgb_in"], bufs["a_r"], bufs["a_n"], bufs["a_s"]
 
         ctx.model = model
         ctx.E, ctx.K, ctx.Kp, ctx.C = E, K, Kp, C
-        ctx.compact = compact
-        if compact:
-            ctx.live = (bufs["live_idx"], bufs["xn_c"][:bufs["n"]], bufs["rgb_c"], bufs["np_c"], bufs["sem_c"], bufs["n"])
         ctx.save_for_backward(xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
                               xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dfeat)
         ctx.mark_non_differentiable(grads)
@@ -513,7 +431,7 @@ class _FieldFn(Function):
             d_sig_c = d_sig.contiguous()
             buf, g_xyz = table_buffer(xe, xyz_table)
 
-            def density_scatter(n=n):   # (bound now: the colour branch below may work on fewer rows)
+            def density_scatter():
                 call("grid_bwd_param_scaled", xe.desc, xn, dsig_dfeat, 128, d_sig_c, n, buf)
                 cb = getattr(xe, "on_grad_ready", None)
                 if cb is not None:
@@ -535,21 +453,6 @@ class _FieldFn(Function):
             density_scatter = None
 
         # ---- colour branch (rgb_net + the two heads): data gradients w.r.t. [grid features | appearance code] first
-        # (compacted forward: the branch's activations hold the live rows only; the upstream gradients are brought
-        # into that order, rows behind a stop carry exact zeros anyway)
-        xn_col, n_col = xn, n
-        if ctx.compact:
-            live_idx, xn_col, rgb_c, np_c, sem_c, n_col = ctx.live
-            rgb_o, np_o, sem_o = rgb_c, np_c, sem_c
-
-            def to_live(t, cols):
-                if t is None:
-                    return None
-                out = torch.empty(n_col, cols, dtype=_f32, device=dev)
-                call("gather_rows", t.contiguous(), cols, cols, live_idx, n_col, out, cols)
-                return out
-            d_rgb, d_np, d_sem = to_live(d_rgb, 3), to_live(d_np, 3), to_live(d_sem, C)
-        n_full, n = n, n_col
         dfeat_rgb = None
         W_cols = 128 + E
         stages = []
@@ -585,7 +488,7 @@ class _FieldFn(Function):
             buf_c, g_rgbt = table_buffer(re, rgb_table)
 
             def colour_scatter():
-                call("grid_bwd_param", re.desc, xn_col, dfeat_rgb, W_cols, n, buf_c)
+                call("grid_bwd_param", re.desc, xn, dfeat_rgb, W_cols, n, buf_c)
                 cb = getattr(re, "on_grad_ready", None)
                 if cb is not None:
                     cb()
@@ -603,7 +506,6 @@ class _FieldFn(Function):
                 call("grid_bwd_input", re.desc, rgb_table, xn, dfeat_rgb, W_cols, n, g_x)
         for st in stages:
             st.weight_products()
-        n = n_full
 
         # ---- density head
         if d_sig is not None:

@@ -177,8 +177,6 @@ class NGPTrainer:
         self.loss_kwargs = dict(loss_kwargs or {})
         optional = any(self.loss_kwargs.get(k) for k in ("normal_ref", "normal_mono", "semantic", "depth_mono", "embed_msk"))
         self.fused_loss = not optional   # default recipe (rgb + opacity + distortion); False -> NeRFLoss module
-        # False: the launch-per-operation tail (normals, softmax, compositor, RefLoss, distortion, loss)
-        self.fused_tail = True
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -348,7 +346,7 @@ class NGPTrainer:
             marched = ahead.take(rays_o, rays_d, self.exp_step_factor)
         default_recipe = bool(self.fused_loss and not loss_kwargs and not target)
         extra = {}
-        if default_recipe and self.fused_tail and rays_o.is_cuda:
+        if default_recipe and rays_o.is_cuda:
             # render + loss + the loss's gradients as one launch behind the field (rendering._RenderLossFn)
             extra['_fused_loss'] = (rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion)
         results = render(model, rays_o, rays_d, exp_step_factor=self.exp_step_factor,

@@ -3,8 +3,8 @@
 training steps with the switch off / on (box-to-box and run-to-run spread of bench.py is +-3 %, more than most single
 changes are worth; alternating inside one process removes it).
 
-    python tools/ab_step.py fused_tail            # NGPTrainer attribute toggled False / True
-    AB_WINDOWS=12 AB_STEPS=40 python tools/ab_step.py fused_tail"""
+    python tools/ab_step.py fused_loss            # NGPTrainer attribute toggled False / True
+    AB_WINDOWS=12 AB_STEPS=40 python tools/ab_step.py fused_loss"""
 import os
 import sys
 import time
