@@ -488,6 +488,39 @@ int ngp_mc_emit(const float* volume, int nx, int ny, int nz, float level, const 
                 const float* spacing3 /* host */, const int32_t* workspace, float* verts, int32_t* faces,
                 void* stream);
 
+/* ------------------------------------------------------------------------
+ * M2  connected components and compaction of a triangle mesh (mesh cleaning: keep the large pieces, drop floaters;
+ *     the reference's family keeps the largest cluster on the CPU)
+ * faces (n_faces, 3) int32 over n_verts vertices; every index must lie in [0, n_verts) (the caller checks it).  Two
+ * faces are connected when they share a vertex.
+ * Labels: ngp_mesh_labels_init writes labels[v] = v; each ngp_mesh_labels_round (two launches: hook the faces'
+ * corner labels to their minimum with atomicMin, then pointer jumping) only lowers labels, and writes changed[0] = 1
+ * when it lowered one (the caller zeroes the word).  The caller repeats rounds until one leaves the word at 0; then
+ * labels[v] is the smallest vertex index of v's component (a vertex in no face keeps its own), whatever the thread
+ * order.  No launch waits on another workgroup's stores.
+ * ngp_mesh_face_counts: face_counts[r] = faces of the component whose label is r (0 elsewhere); zeroes it itself.
+ * Compaction, two calls: ngp_mesh_compact_count flags the kept faces (keep[labels[corner]] != 0, keep a (n_verts)
+ * uint8 array indexed by label) and the kept vertices (those some kept face uses), and leaves totals[0] = kept
+ * vertices, totals[1] = kept faces on the device with what the emits need in workspace
+ * (ngp_mesh_clean_workspace(n_verts, n_faces) int32 elements, host-only query; NGP_EINVAL for a negative size or
+ * n_faces > INT32_MAX / 3).  ngp_mesh_compact_rows copies the kept rows of any per-vertex array (row_bytes bytes per
+ * vertex: positions, normals, colours) in their original order; ngp_mesh_compact_faces writes the kept faces in their
+ * original order with their corners renumbered.  Empty inputs return NGP_OK before any pointer is looked at.
+ * ---------------------------------------------------------------------- */
+int64_t ngp_mesh_clean_workspace(int n_verts, int n_faces);
+int ngp_mesh_labels_init(int32_t* labels, int n_verts, void* stream);
+int ngp_mesh_labels_round(const int32_t* faces, int n_faces, int n_verts, int32_t* labels, int32_t* changed,
+                          void* stream);
+int ngp_mesh_face_counts(const int32_t* faces, int n_faces, int n_verts, const int32_t* labels, int32_t* face_counts,
+                         void* stream);
+int ngp_mesh_compact_count(const int32_t* faces, int n_faces, int n_verts, const int32_t* labels,
+                           const int32_t* face_counts, const uint8_t* keep, int32_t* workspace, int32_t* totals,
+                           void* stream);
+int ngp_mesh_compact_rows(const void* src, int row_bytes, int n_verts, int n_faces, const int32_t* workspace,
+                          void* dst, void* stream);
+int ngp_mesh_compact_faces(const int32_t* faces, int n_faces, int n_verts, const int32_t* workspace,
+                           int32_t* faces_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

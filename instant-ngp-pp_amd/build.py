@@ -24,6 +24,7 @@ SOURCES = [
     ("grid_kernels.hip", []),
     ("mlp_kernels.hip", []),
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
+    ("mesh_clean_kernels.hip", []),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -4,7 +4,10 @@ own.
 
   marching_cubes(volume, level, spacing, origin) -> verts (V,3) f32, faces (F,3) i32 on the volume's device
   extract_mesh(model, ...)                        -> the same for NGP.density sampled on a dense lattice
-  write_ply(path, verts, faces, normals) / read_ply(path)
+  mesh_components(faces, n_verts)                 -> per-vertex component labels and faces per component (M2)
+  clean_mesh(verts, faces, keep_largest=, min_faces=) -> the mesh without its small disconnected pieces (M2)
+  vertex_colors(model, verts, normals, offset)    -> (V,3) uint8 colours rendered by the test-time marcher
+  write_ply(path, verts, faces, normals, colors) / read_ply(path, colors=False)
 
 Triangles are wound so that (v1-v0) x (v2-v0) points toward lower density (out of the object).  Ambiguous cell faces
 are resolved by one face-local rule (inside corners are separated), so closed surfaces come out as closed 2-manifolds;
@@ -103,7 +106,7 @@ def vertex_normals(model, verts, chunk=128 ** 3):
 
 
 def extract_mesh(model, xyz_min=None, xyz_max=None, resolution=512, level=10.0, chunk=128 ** 3, normals=False,
-                 reference_spacing=False):
+                 reference_spacing=False, keep_largest=None, min_faces=None, colors=False, color_offset=None):
     """Mesh of the level set {sigma = level} of `model` (an NGP) -> verts (V,3), faces (F,3) [, normals (V,3)].
 
     The lattice spans [xyz_min, xyz_max] (default: the model's own box) with `resolution` (an int or (nx, ny, nz))
@@ -115,21 +118,205 @@ def extract_mesh(model, xyz_min=None, xyz_max=None, resolution=512, level=10.0, 
     (v - lo) * (n-1)/n).  Its own call is xyz_min=(-1,-0.3,-1), xyz_max=(1,0.15,1), resolution=(512,128,512),
     level=10.
 
-    normals=True adds per-vertex unit normals -grad(sigma)/|grad(sigma)| (pointing out of the object)."""
+    normals=True adds per-vertex unit normals -grad(sigma)/|grad(sigma)| (pointing out of the object).
+
+    keep_largest / min_faces remove small disconnected pieces (clean_mesh) before normals and colours are computed.
+    colors=True adds per-vertex uint8 RGB (vertex_colors) rendered from color_offset (default: twice the largest
+    lattice spacing) outside each vertex.  The result is (verts, faces[, normals][, colors])."""
     lo = _vec3(model.xyz_min if xyz_min is None else xyz_min)
     hi = _vec3(model.xyz_max if xyz_max is None else xyz_max)
     vol = density_volume(model, lo, hi, resolution, chunk)
-    verts, faces = marching_cubes(vol, level, lattice_spacing(lo, hi, vol.shape, reference_spacing), lo)
+    spacing = lattice_spacing(lo, hi, vol.shape, reference_spacing)
+    verts, faces = marching_cubes(vol, level, spacing, lo)
+    del vol
+    if keep_largest is not None or min_faces is not None:
+        verts, faces = clean_mesh(verts, faces, keep_largest=keep_largest, min_faces=min_faces)
+    out = [verts, faces]
+    nrm = vertex_normals(model, verts, chunk) if normals or colors else None
     if normals:
-        return verts, faces, vertex_normals(model, verts, chunk)
-    return verts, faces
+        out.append(nrm)
+    if colors:
+        out.append(vertex_colors(model, verts, nrm, 2 * max(spacing) if color_offset is None else color_offset))
+    return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------- cleaning (M2)
+def _check_faces(faces, n_verts):
+    check_input(faces, "faces")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be an (F, 3) int32 tensor, got {tuple(faces.shape)} {faces.dtype}")
+    n_verts = int(n_verts)
+    if n_verts < 0 or n_verts > 2 ** 31 - 1 or faces.shape[0] > (2 ** 31 - 1) // 3:
+        raise ValueError(f"unsupported mesh size: {n_verts} vertices, {faces.shape[0]} faces")
+    if faces.shape[0]:
+        lo, hi = torch.aminmax(faces)
+        if int(lo) < 0 or int(hi) >= n_verts:
+            raise ValueError(f"face indices span [{int(lo)}, {int(hi)}], outside [0, {n_verts})")
+    return n_verts
+
+
+def label_round_bound(n_verts):
+    """the most label rounds component_labels runs before it gives up (each round at least halves the longest label
+    chain of a path; the margin covers what hooking adds)"""
+    return 64 + 2 * int(n_verts).bit_length()
+
+
+def component_labels(faces, n_verts, max_rounds=None):
+    """faces (F,3) int32 CUDA tensor over n_verts vertices -> (labels (V,) int32, rounds): labels[v] is the smallest
+    vertex index of v's component (faces sharing a vertex are connected; a vertex in no face keeps its own index), the
+    same from run to run.  Runs ngp_mesh_labels_round until a round changes nothing, reading one word back per round;
+    raises RuntimeError if that takes more than max_rounds (default label_round_bound(n_verts)) rounds."""
+    n_verts = _check_faces(faces, n_verts)
+    n_faces = faces.shape[0]
+    labels = torch.empty(n_verts, dtype=torch.int32, device=faces.device)
+    if n_verts == 0:
+        return labels, 0
+    call("mesh_labels_init", labels, n_verts)
+    if n_faces == 0:
+        return labels, 0
+    bound = label_round_bound(n_verts) if max_rounds is None else int(max_rounds)
+    changed = torch.zeros(max(bound, 1), dtype=torch.int32, device=faces.device)
+    for r in range(bound):
+        call("mesh_labels_round", faces, n_faces, n_verts, labels, changed[r:])
+        if not int(changed[r]):
+            return labels, r + 1
+    raise RuntimeError(f"connected components of {n_verts} vertices / {n_faces} faces did not settle in {bound} rounds")
+
+
+def mesh_components(faces, n_verts):
+    """-> labels (V,) int32 (component_labels) and face_counts (V,) int32: the faces of each component at its label's
+    slot, 0 at every other slot"""
+    labels, _ = component_labels(faces, n_verts)
+    counts = torch.zeros_like(labels)
+    if labels.numel():
+        call("mesh_face_counts", faces, faces.shape[0], labels.numel(), labels, counts)
+    return labels, counts
+
+
+def select_components(face_counts, keep_largest=None, min_faces=None):
+    """-> keep (V,) uint8 indexed by label: 1 for each component with faces that meets every criterion given
+    (keep_largest=k: among the k components with the most faces, ties to the smaller label; min_faces=m: at least m
+    faces)"""
+    keep = face_counts > 0
+    if min_faces is not None:
+        if int(min_faces) < 0:
+            raise ValueError(f"min_faces must be >= 0, got {min_faces}")
+        keep &= face_counts >= int(min_faces)
+    if keep_largest is not None:
+        if int(keep_largest) < 0:
+            raise ValueError(f"keep_largest must be >= 0, got {keep_largest}")
+        roots = torch.nonzero(face_counts > 0).squeeze(1)                 # ascending labels
+        c = face_counts[roots].cpu().numpy()                               # C components: ranked on the host
+        order = np.lexsort((np.arange(c.size), -c.astype(np.int64)))[:int(keep_largest)]
+        top = torch.zeros_like(keep)
+        top[roots[torch.from_numpy(order).to(roots.device)]] = True
+        keep &= top
+    return keep.to(torch.uint8)
+
+
+def clean_mesh(verts, faces, *, normals=None, colors=None, keep_largest=None, min_faces=None, stats=None):
+    """Drops the components that fail the criteria of select_components -> (verts, faces[, normals][, colors]).
+
+    Labels, sizes and compaction run in libngp_hip.so (M2): kept vertices (those some kept face uses) and kept faces
+    keep their original order, faces are renumbered, and normals / colors rows (any (V, ...) tensors) follow their
+    vertices.  With no criterion, every component with a face is kept (only vertices no face uses go).  A dict passed
+    as `stats` receives rounds, components (those with faces), components_kept, V_removed and F_removed."""
+    check_input(verts, "verts")
+    if verts.dtype != _f32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts must be a (V, 3) float32 tensor, got {tuple(verts.shape)} {verts.dtype}")
+    n_verts, n_faces = verts.shape[0], faces.shape[0]
+    attrs = [a for a in (normals, colors) if a is not None]
+    for name, a in (("normals", normals), ("colors", colors)):
+        if a is not None:
+            check_input(a, name)
+            if a.shape[0] != n_verts:
+                raise ValueError(f"{name} has {a.shape[0]} rows for {n_verts} vertices")
+    labels, rounds = component_labels(faces, n_verts)
+    counts = torch.zeros_like(labels)
+    if n_verts:
+        call("mesh_face_counts", faces, n_faces, n_verts, labels, counts)
+    keep = select_components(counts, keep_largest, min_faces)
+    ws = torch.empty(call_host("mesh_clean_workspace", n_verts, n_faces), dtype=torch.int32, device=verts.device)
+    totals = torch.zeros(2, dtype=torch.int32, device=verts.device)
+    if n_verts:
+        call("mesh_compact_count", faces, n_faces, n_verts, labels, counts, keep, ws, totals)
+    n_v, n_f = totals.tolist()
+    out = [torch.empty(n_v, 3, dtype=_f32, device=verts.device)]
+    out += [torch.empty((n_v,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device) for a in attrs]
+    for src, dst in zip([verts] + attrs, out):
+        if n_v:
+            row_bytes = src[0].numel() * src.element_size()
+            call("mesh_compact_rows", src, row_bytes, n_verts, n_faces, ws, dst)
+    f_out = torch.empty(n_f, 3, dtype=torch.int32, device=faces.device)
+    if n_f:
+        call("mesh_compact_faces", faces, n_faces, n_verts, ws, f_out)
+    if stats is not None:
+        stats.update(rounds=rounds, components=int((counts > 0).sum()), components_kept=int(keep.sum()),
+                     V_removed=n_verts - n_v, F_removed=n_faces - n_f)
+    return (out[0], f_out, *out[1:])
+
+
+# ------------------------------------------------------------------------------------------------- vertex colours
+FALLBACK_DIR = (0.0, 0.0, -1.0)   # view direction of the colour network where no ray sees the surface (from above)
+MIN_OPACITY = 1e-3
+
+
+def vertex_rays(verts, normals, offset):
+    """the ray of each vertex: from v + offset*n toward -n over t in [0, 2*offset] -> rays_o, rays_d, hits_t (V,2)"""
+    offset = float(offset)
+    rays_o = (verts + offset * normals).contiguous()
+    rays_d = (-normals).contiguous()
+    hits_t = torch.tensor([0.0, 2 * offset], dtype=_f32, device=verts.device).expand(verts.shape[0], 2).contiguous()
+    return rays_o, rays_d, hits_t
+
+
+@torch.no_grad()
+def vertex_colors(model, verts, normals, offset, chunk=1 << 20, quantize=True, **render_kwargs):
+    """Per-vertex colour of the trained appearance field -> (V,3) uint8 (quantize=False: the float colour in [0,1]).
+
+    Each vertex with a non-zero normal casts the ray of vertex_rays through rendering.volume_render (the HIP marcher,
+    field and compositor; hits_t is set directly, with no near clamp), `chunk` rays at a time; its colour is
+    rgb / opacity clamped to [0,1] where opacity >= MIN_OPACITY.  Where the ray sees nothing, or the normal vanished,
+    the colour is the colour network at the vertex itself viewed along FALLBACK_DIR.  Quantised as floor(255*c + 0.5).
+    render_kwargs (exp_step_factor, embedding_a, ...) pass through to volume_render and the field."""
+    from .rendering import volume_render
+    n = verts.shape[0]
+    dev = verts.device
+    col = torch.zeros(n, 3, dtype=_f32, device=dev)
+    seen = torch.zeros(n, dtype=torch.bool, device=dev)
+    rows = torch.nonzero(normals.abs().amax(1) > 0).squeeze(1) if n else torch.zeros(0, dtype=torch.int64, device=dev)
+    classes = render_kwargs.get('num_classes', 7)
+    for s in range(0, rows.numel(), chunk):
+        idx = rows[s:s + chunk]
+        m = idx.numel()
+        rays_o, rays_d, hits_t = vertex_rays(verts[idx], normals[idx], offset)
+        opacity = torch.zeros(m, device=dev)
+        rgb = torch.zeros(m, 3, device=dev)
+        volume_render(model, rays_o, rays_d, hits_t, opacity, torch.zeros(m, device=dev), rgb,
+                      torch.zeros(m, 3, device=dev), torch.zeros(m, 3, device=dev),
+                      torch.zeros(m, classes, device=dev), **render_kwargs)
+        ok = opacity >= MIN_OPACITY
+        col[idx] = torch.where(ok[:, None], (rgb / opacity.clamp_min(MIN_OPACITY)[:, None]).clamp(0, 1), col[idx])
+        seen[idx] = ok
+    rest = torch.nonzero(~seen).squeeze(1)
+    for s in range(0, rest.numel(), chunk):
+        idx = rest[s:s + chunk]
+        d = torch.tensor(FALLBACK_DIR, dtype=_f32, device=dev).expand(idx.numel(), 3).contiguous()
+        col[idx] = model.forward_test(verts[idx].contiguous(), d, **render_kwargs)[1].float().clamp(0, 1)
+    if not quantize:
+        return col
+    return torch.floor(255 * col + 0.5).to(torch.uint8)
 
 
 # ---------------------------------------------------------------------------------------------------------------- PLY
-def _ply_header(n_v, n_f, normals):
+_RGB = ("red", "green", "blue")
+
+
+def _ply_header(n_v, n_f, normals, colors=False):
     props = ["x", "y", "z"] + (["nx", "ny", "nz"] if normals else [])
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n_v}"]
     lines += [f"property float {p}" for p in props]
+    lines += [f"property uchar {p}" for p in _RGB] if colors else []
     lines += [f"element face {n_f}", "property list uchar int vertex_indices", "end_header"]
     return ("\n".join(lines) + "\n").encode("ascii")
 
@@ -137,26 +324,35 @@ def _ply_header(n_v, n_f, normals):
 _FACE = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])   # 13 bytes per face, unaligned as in the file
 
 
-def write_ply(path, verts, faces, normals=None):
+def _np(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def write_ply(path, verts, faces, normals=None, colors=None):
     """binary little-endian PLY with the element / property names the reference writes through plyfile:
-    vertex (float x y z [nx ny nz]), face (list uchar int vertex_indices)"""
-    v = verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else np.asarray(verts)
-    f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    vertex (float x y z [nx ny nz] [uchar red green blue]), face (list uchar int vertex_indices)"""
+    v = _np(verts)
+    f = _np(faces)
     v = v.astype("<f4").reshape(-1, 3)
     if normals is not None:
-        nm = normals.detach().cpu().numpy() if isinstance(normals, torch.Tensor) else np.asarray(normals)
-        v = np.concatenate([v, nm.astype("<f4").reshape(-1, 3)], 1)
+        v = np.concatenate([v, _np(normals).astype("<f4").reshape(-1, 3)], 1)
+    if colors is not None:
+        rec_v = np.empty(v.shape[0], [("f", "<f4", (v.shape[1],)), ("rgb", "u1", (3,))])   # packed, as in the file
+        rec_v["f"] = v
+        rec_v["rgb"] = _np(colors).reshape(-1, 3)
+        v = rec_v
     rec = np.empty(f.shape[0], _FACE)
     rec["n"] = 3
     rec["idx"] = f.reshape(-1, 3)
     with open(path, "wb") as fh:
-        fh.write(_ply_header(v.shape[0], rec.shape[0], normals is not None))
+        fh.write(_ply_header(v.shape[0], rec.shape[0], normals is not None, colors is not None))
         fh.write(np.ascontiguousarray(v).tobytes())
         fh.write(rec.tobytes())
 
 
-def read_ply(path):
-    """-> (verts (V,3) f32, faces (F,3) int32, normals (V,3) f32 or None) of a file write_ply wrote"""
+def read_ply(path, colors=False):
+    """-> (verts (V,3) f32, faces (F,3) int32, normals (V,3) f32 or None) of a file write_ply wrote;
+    colors=True appends the (V,3) uint8 red / green / blue rows, or None"""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -170,15 +366,21 @@ def read_ply(path):
             elem = w[1]
             counts[elem] = int(w[2])
         elif w[0] == "property" and elem == "vertex":
-            if w[1] != "float":
+            if w[1] != "float" and not (w[1] == "uchar" and w[2] in _RGB):
                 raise ValueError(f"{path}: vertex property {line!r} is not supported")
-            props.append(w[2])
+            props.append((w[2], "<f4" if w[1] == "float" else "u1"))
         elif w[0] == "property" and line != "property list uchar int vertex_indices":
             raise ValueError(f"{path}: face property {line!r} is not supported")
-    n_v, n_f, k = counts["vertex"], counts["face"], len(props)
-    v = np.frombuffer(data, "<f4", n_v * k, end).reshape(n_v, k)
-    rec = np.frombuffer(data, _FACE, n_f, end + 4 * n_v * k)
+    n_v, n_f = counts["vertex"], counts["face"]
+    vt = np.dtype(props)
+    rv = np.frombuffer(data, vt, n_v, end)
+    rec = np.frombuffer(data, _FACE, n_f, end + vt.itemsize * n_v)
     if n_f and (rec["n"] != 3).any():
         raise ValueError(f"{path}: only triangles are supported")
-    nrm = v[:, 3:6].astype(np.float32) if props[3:6] == ["nx", "ny", "nz"] else None
-    return v[:, :3].astype(np.float32), rec["idx"].astype(np.int32), nrm
+    names = [p for p, _ in props]
+
+    def cols(keys, dtype):
+        return np.stack([rv[k] for k in keys], 1).astype(dtype) if set(keys) <= set(names) else None
+    out = (cols(("x", "y", "z"), np.float32).reshape(n_v, 3), rec["idx"].astype(np.int32),
+           cols(("nx", "ny", "nz"), np.float32))
+    return out + (cols(_RGB, np.uint8),) if colors else out

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Extracts a triangle mesh from a trained checkpoint and writes it as binary PLY (the reference's extract_mesh.py:
 density on a dense lattice, marching cubes, PLY).  GPU only.  Prints one JSON line: V, F and the milliseconds of the
-density pass, marching cubes, the device->host copy and the PLY write (each timed around a device synchronise).
+density pass, marching cubes, the cleaning, the normals, the colours, the device->host copy and the PLY write (each
+timed around a device synchronise), and what the cleaning found and removed.
 
   python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --resolution 256 --normals
+  python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --keep_largest 1 --colors
 """
 import argparse
 import json
@@ -38,6 +40,11 @@ def main(argv=None):
     ap.add_argument("--normals", action="store_true", help="per-vertex normals -grad(sigma)/|grad(sigma)|")
     ap.add_argument("--reference_spacing", action="store_true",
                     help="place vertices as the reference does (spacing extent/n instead of extent/(n-1))")
+    ap.add_argument("--keep_largest", type=int, metavar="K",
+                    help="keep only the K connected pieces with the most faces (floater removal)")
+    ap.add_argument("--min_faces", type=int, metavar="M", help="keep only the connected pieces with at least M faces")
+    ap.add_argument("--colors", action="store_true",
+                    help="per-vertex RGB rendered from the trained appearance field (PLY red green blue)")
     ap.add_argument("--chunk", type=int, default=128 ** 3)
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
@@ -55,23 +62,35 @@ def main(argv=None):
     vol = mesh.density_volume(model, lo, hi, res, args.chunk)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    verts, faces = mesh.marching_cubes(vol, args.level, mesh.lattice_spacing(lo, hi, vol.shape, args.reference_spacing),
-                                       lo)
+    spacing = mesh.lattice_spacing(lo, hi, vol.shape, args.reference_spacing)
+    verts, faces = mesh.marching_cubes(vol, args.level, spacing, lo)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    nrm = mesh.vertex_normals(model, verts, args.chunk) if args.normals else None
+    stats = {"components": None, "V_removed": 0, "F_removed": 0}
+    if args.keep_largest is not None or args.min_faces is not None:
+        verts, faces = mesh.clean_mesh(verts, faces, keep_largest=args.keep_largest, min_faces=args.min_faces,
+                                       stats=stats)
+    torch.cuda.synchronize()
+    t_c = time.perf_counter()
+    nrm = mesh.vertex_normals(model, verts, args.chunk) if args.normals or args.colors else None
     torch.cuda.synchronize()
     t_n = time.perf_counter()
+    rgb = mesh.vertex_colors(model, verts, nrm, 2 * max(spacing)) if args.colors else None
+    torch.cuda.synchronize()
+    t_k = time.perf_counter()
     v, f = verts.cpu(), faces.cpu()
-    nrm = None if nrm is None else nrm.cpu()
+    nrm = None if nrm is None or not args.normals else nrm.cpu()
+    rgb = None if rgb is None else rgb.cpu()
     torch.cuda.synchronize()
     t3 = time.perf_counter()
-    mesh.write_ply(args.out, v, f, nrm)
+    mesh.write_ply(args.out, v, f, nrm, rgb)
     t4 = time.perf_counter()
-    times = {"density_ms": 1e3 * (t1 - t0), "mc_ms": 1e3 * (t2 - t1), "normals_ms": 1e3 * (t_n - t2),
-             "d2h_ms": 1e3 * (t3 - t_n), "ply_ms": 1e3 * (t4 - t3)}
+    times = {"density_ms": 1e3 * (t1 - t0), "mc_ms": 1e3 * (t2 - t1), "normals_ms": 1e3 * (t_n - t_c),
+             "d2h_ms": 1e3 * (t3 - t_k), "ply_ms": 1e3 * (t4 - t3), "clean_ms": 1e3 * (t_c - t2),
+             "colors_ms": 1e3 * (t_k - t_n)}
     print(json.dumps({"V": int(v.shape[0]), "F": int(f.shape[0]), "lattice": list(vol.shape),
-                      **{k: round(x, 3) for k, x in times.items()}}))
+                      **{k: round(x, 3) for k, x in times.items()},
+                      **{k: stats[k] for k in ("components", "V_removed", "F_removed")}}))
 
 
 if __name__ == "__main__":
