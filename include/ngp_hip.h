@@ -310,6 +310,21 @@ int ngp_grid_bwd_param_scaled(const ngp_grid_desc* desc, const float* x, const f
 int ngp_grid_bwd_input(const ngp_grid_desc* desc, const float* table, const float* x,
                        const float* dL_dy, int64_t lddy, int64_t n, float* dL_dx, void* stream);
 
+/* The training forward's density path in one launch, in place of the four launches
+ *   ngp_grid_fwd -> ngp_mlp2_fwd_dact -> ngp_mlp_bwd_input -> ngp_grid_bwd_input
+ * for the density head 128 -> 128 softplus -> 1 softplus:
+ *   feat (n,128) = encode(x), a1 (n,128) = softplus(feat W1^T + b1), sig (n) = softplus(a1 . W2 + b2),
+ *   dfeat (n,128) = d sig / d feat, grads (n,3) = d sig / dx.
+ * feat, a1, sig and dfeat are bitwise what the four launches write; grads agree with theirs within 128 ulps of
+ * the row's largest component (the same expression, contracted into FMAs differently by the compiler).
+ * Takes F = 8 layouts of 16 levels that the tile kernels take (ngp_density_field_layout_ok, host-only: 1 or 0);
+ * W1 (128,128) and W2 (1,128) row-major, b1 (128) / b2 (1) may be NULL; every output is contiguous, and W1, feat,
+ * a1 and dfeat are 16-byte aligned.  Anything else returns NGP_EINVAL without a launch. */
+int ngp_density_field_layout_ok(const ngp_grid_desc* desc);
+int ngp_density_field_fwd(const ngp_grid_desc* desc, const float* table, const float* x, int64_t n,
+                          const float* W1, const float* b1, const float* W2, const float* b2,
+                          float* feat, float* a1, float* sig, float* dfeat, float* grads, void* stream);
+
 /* double backward of ngp_grid_bwd_input: given dL_ddLdx (n,3) (gradient flowing into
  * dL_dx), accumulates dtable (atomic) and writes dL_ddLdy (n, L*F).  Either output
  * may be NULL. */

@@ -14,6 +14,7 @@
 //     Lanes whose upstream gradient is exactly zero (samples behind the early-termination
 //     point, volumerendering.cu:111) issue no atomics.
 #include "common.h"
+#include "mlp_act.h"
 
 namespace {
 
@@ -243,6 +244,8 @@ __device__ __forceinline__ void corners(const LevelInfo& li, const float* __rest
 }
 }  // namespace run
 
+// The fused density kernel below (density_field_fwd_kernel) repeats this kernel's code: keep the two in step
+// (tests/test_density_fused_gpu.py compares them bit for bit).
 __global__ void __launch_bounds__(256) grid_fwd_run_kernel(GridMeta meta, const float* __restrict__ table,
                                                            const float* __restrict__ x, int64_t n,
                                                            float* __restrict__ y, int64_t ldy)
@@ -294,6 +297,8 @@ __global__ void __launch_bounds__(256) grid_fwd_run_kernel(GridMeta meta, const 
     }
 }
 
+// The fused density kernel below (density_field_fwd_kernel) repeats this kernel's code: keep the two in step
+// (tests/test_density_fused_gpu.py compares them within the bound it states).
 __global__ void __launch_bounds__(256) grid_bwd_input_run_kernel(GridMeta meta, const float* __restrict__ table,
                                                                  const float* __restrict__ x,
                                                                  const float* __restrict__ dL_dy, int64_t lddy,
@@ -362,6 +367,248 @@ __global__ void __launch_bounds__(256) grid_bwd_input_run_kernel(GridMeta meta, 
             float sum = 0.0f;
             for (uint32_t w = 0; w < wpc; w++) sum += red[tl * wpc + w][r];
             dL_dx[3 * c0 + r] = sum;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ fused density path (H1 + density head + H3)
+// The training forward's density path, feat = enc(x), a1 = softplus(feat W1^T + b1), sigma = softplus(a1 . W2 + b2),
+// dfeat = d sigma / d feat and d sigma / dx, in one launch instead of grid_fwd_run -> mlp_stream_fwd ->
+// mlp_stream_dgrad -> grid_bwd_input_run: feat, a1 and dz2 are not read back from memory.  The input gradient gathers
+// the tile's corner rows a second time, tens of microseconds after the first gather; whether the caches still hold them
+// is measured, not assumed (profiles/r04_density_fused_profiles.txt: L2 traffic of the density path, parent against
+// this kernel).  Every output keeps its kernel's operation order (the run-leader gather and its blend, the MFMA step order and reduction-index
+// permutation of the two streaming MLP kernels, the input gradient's per-level-group partial sums added in level-group
+// order): feat, a1, sigma and dfeat are bitwise what the four kernels write.  d sigma / dx can differ in the last
+// bits: its per-level expression is the same source, but hipcc contracts and packs it (v_pk_fma_f32) differently in
+// this kernel (tests/test_density_fused_gpu.py bounds the difference: 128 ulps of the row's largest component).
+// The gather / blend, both MFMA step sequences and the input-gradient expression are COPIES of those kernels' code:
+// a change to grid_fwd_run_kernel, grid_bwd_input_run_kernel, mlp_stream_fwd_kernel<1, 16, SOFTPLUS, 4> or
+// mlp_stream_dgrad_kernel<1, SOFTPLUS> has to be made here too (tests/test_density_fused_gpu.py compares the two).
+//   workgroup: 8 waves, one per CU; W1 (the only copy) sits in LDS as [hidden][input + 4], mlp_stream_fwd's layout.
+//   The data gradient's B operand W1[h][c] is read from it with ds_read_b32 (lanes of a half-wave read consecutive
+//   c): the same values, so the same products.
+//   wave: one 32-sample tile at a time, in four level groups of 4 levels (the 32 features a K block of the first
+//   layer consumes).  A per-wave [32][36] LDS tile turns the gather's lane layout (sample, half row) into the MFMA
+//   operand layout (sample, K half), the MFMA accumulator layout into 128-byte row stores, and a1 into the data
+//   gradient's operand layout (kept in 64 registers from the forward epilogue to the data gradient).
+namespace dens {
+constexpr int NW = 8;          // waves per workgroup
+constexpr int LDW = 132;       // W1 row stride in LDS (mlp_stream_fwd_kernel's conflict-free [H][K + 4])
+constexpr int LDT = 36;        // per-wave staging tile row stride
+constexpr int LDS_FLOATS = 128 * LDW + 128 + 128 + 4 + NW * 32 * LDT + NW * 32;
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+}  // namespace dens
+
+__global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, const float* __restrict__ table,
+                                                                const float* __restrict__ x, int64_t n,
+                                                                const float* __restrict__ W1, const float* __restrict__ b1,
+                                                                const float* __restrict__ W2, const float* __restrict__ b2,
+                                                                float* __restrict__ feat, float* __restrict__ a1,
+                                                                float* __restrict__ sig, float* __restrict__ dfeat,
+                                                                float* __restrict__ grads, int n_tiles)
+{
+    using namespace run;
+    using dens::LDW;
+    using dens::LDT;
+    typedef dens::f32x16 f32x16;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Ws = smem;                        // [128 hidden][LDW]: Ws[h * LDW + c] = W1[h][c]
+    float* W2s = Ws + 128 * LDW;             // [128]
+    float* b1s = W2s + 128;                  // [128]
+    float* b2s = b1s + 128;                  // [4]
+    float* stage = b2s + 4;                  // [NW][32][LDT]
+    float* d2s = stage + dens::NW * 32 * LDT;   // [NW][32]: dz2 = softplus'(z2) of the tile's rows
+    for (int idx = threadIdx.x; idx < 128 * 32; idx += blockDim.x) {
+        const int h = idx >> 5, c4 = (idx & 31) * 4;
+        *reinterpret_cast<float4*>(Ws + h * LDW + c4) = *reinterpret_cast<const float4*>(W1 + h * 128 + c4);
+    }
+    if (threadIdx.x < 128) {
+        W2s[threadIdx.x] = W2[threadIdx.x];
+        b1s[threadIdx.x] = b1 ? b1[threadIdx.x] : 0.0f;
+    }
+    if (threadIdx.x < 4) b2s[threadIdx.x] = (b2 && threadIdx.x == 0) ? b2[0] : 0.0f;
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 31, lh = lane >> 5;      // MFMA layout: lane (row, K half)
+    const int j = lane >> 1, half = lane & 1;      // gather layout: lane (sample, half row)
+    const int piece = lane & 7;
+    float* st = stage + wave * 32 * LDT;
+    float* d2w = d2s + wave * 32;
+    for (int tile = blockIdx.x * dens::NW + wave; tile < n_tiles; tile += gridDim.x * dens::NW) {
+        const int64_t s0 = (int64_t)tile * 32;
+        const int64_t sj = s0 + j < n ? s0 + j : n - 1;
+        const float px = x[3 * sj], py = x[3 * sj + 1], pz = x[3 * sj + 2];
+
+        // ---- gather + first layer, one level group (= one 32-wide K block) at a time
+        f32x16 acc[4];
+#pragma unroll
+        for (int tn = 0; tn < 4; tn++) {
+            const float bv = b1s[tn * 32 + li];
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[tn][r] = bv;
+        }
+#pragma unroll 1
+        for (int g = 0; g < 4; g++) {
+#pragma unroll 2
+            for (int i = 0; i < 4; i++) {                // grid_fwd_run_kernel's gather and blend
+                const LevelInfo lv = level_info(meta, g * 4 + i);
+                const Lead c = phase1(lv.scale, px, py, pz, lane);
+                float4 R[8];
+                corners(lv, table, c, half, R);
+                float f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const float wt = ((k & 1) ? c.w0 : 1 - c.w0) * ((k & 2) ? c.w1 : 1 - c.w1) * ((k & 4) ? c.w2 : 1 - c.w2);
+                    vec_fma<4>(f, wt, R[k]);
+                }
+                *reinterpret_cast<float4*>(st + j * LDT + i * 8 + half * 4) = make_float4(f[0], f[1], f[2], f[3]);
+            }
+            tile::wave_sync();
+#pragma unroll
+            for (int it = 0; it < 4; it++) {
+                const int js = it * 8 + (lane >> 3);
+                if (s0 + js < n)
+                    *reinterpret_cast<float4*>(feat + (s0 + js) * 128 + g * 32 + piece * 4) =
+                        *reinterpret_cast<const float4*>(st + js * LDT + piece * 4);
+            }
+            float4 av[4];                                // A operands: feat[li][8q + 4lh .. +3], q = 4g + i
+#pragma unroll
+            for (int i = 0; i < 4; i++) av[i] = *reinterpret_cast<const float4*>(st + li * LDT + i * 8 + lh * 4);
+            tile::wave_sync();
+#pragma unroll
+            for (int i = 0; i < 4; i++) {                // mlp_stream_fwd_kernel's K steps q = 4g + i
+                const int q = g * 4 + i;
+                float4 bq[4];
+#pragma unroll
+                for (int tn = 0; tn < 4; tn++) bq[tn] = *reinterpret_cast<const float4*>(Ws + (tn * 32 + li) * LDW + 8 * q + 4 * lh);
+                const float a4[4] = {av[i].x, av[i].y, av[i].z, av[i].w};
+#pragma unroll
+                for (int jj = 0; jj < 4; jj++) {
+#pragma unroll
+                    for (int tn = 0; tn < 4; tn++) {
+                        const float bf[4] = {bq[tn].x, bq[tn].y, bq[tn].z, bq[tn].w};
+                        acc[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[jj], bf[jj], acc[tn], 0, 0, 0);
+                    }
+                }
+            }
+        }
+
+        // ---- first-layer epilogue: a1 out (and into the data gradient's operand layout), second layer, sigma, dz2
+        float part[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) part[r] = 0.0f;
+        float4 hv[16];                                   // a1[li][8q + 4lh .. +3]
+#pragma unroll
+        for (int tn = 0; tn < 4; tn++) {
+            const float w2 = W2s[tn * 32 + li];
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[tn][r] = softplus_fast(acc[tn][r]);
+#pragma unroll
+            for (int r = 0; r < 16; r++) st[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDT + li] = acc[tn][r];
+            tile::wave_sync();
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int f = lane + 64 * i, row = f >> 3, c4 = (f & 7) * 4;
+                if (s0 + row < n)
+                    *reinterpret_cast<float4*>(a1 + (s0 + row) * 128 + tn * 32 + c4) = *reinterpret_cast<const float4*>(st + row * LDT + c4);
+            }
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++) hv[tn * 4 + qq] = *reinterpret_cast<const float4*>(st + li * LDT + 8 * qq + 4 * lh);
+            tile::wave_sync();
+#pragma unroll
+            for (int r = 0; r < 16; r++) part[r] = fmaf(acc[tn][r], w2, part[r]);
+        }
+#pragma unroll
+        for (int hf = 8; hf >= 1; hf >>= 1) {            // mlp_stream_fwd_kernel's transposing butterfly (one output)
+            const int mask = hf * 2;
+            const bool up = (li & mask) != 0;
+#pragma unroll
+            for (int jx = 0; jx < hf; jx++) {
+                float lo = part[jx], hi = part[jx + hf];
+                asm volatile("" : "+v"(lo), "+v"(hi));
+                const float keep = up ? hi : lo;
+                const float send = up ? lo : hi;
+                part[jx] = keep + __shfl_xor(send, mask, 64);
+            }
+        }
+        {
+            const float tot = part[0] + __shfl_xor(part[0], 1, 64);
+            const int rr = ((li >> 4) & 1) * 8 + ((li >> 3) & 1) * 4 + ((li >> 2) & 1) * 2 + ((li >> 1) & 1);
+            const int row = (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if ((li & 1) == 0) {
+                const float yv = act_fwd(tot + b2s[0], NGP_ACT_SOFTPLUS);
+                if (s0 + row < n) sig[s0 + row] = yv;
+                d2w[row] = act_dout(yv, NGP_ACT_SOFTPLUS);
+            }
+        }
+        tile::wave_sync();
+
+        // ---- data gradient dfeat = dz1 . W1, dz1 = softplus'(a1) * (dz2 W2): mlp_stream_dgrad_kernel's K steps
+        const float dz = d2w[li];
+        f32x16 acc2[4];
+#pragma unroll
+        for (int tn = 0; tn < 4; tn++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc2[tn][r] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 16; q++) {
+            const float4 w = *reinterpret_cast<const float4*>(W2s + 8 * q + 4 * lh);
+            float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            sv[0] = fmaf(dz, w.x, sv[0]); sv[1] = fmaf(dz, w.y, sv[1]);
+            sv[2] = fmaf(dz, w.z, sv[2]); sv[3] = fmaf(dz, w.w, sv[3]);
+            const float h4[4] = {hv[q].x, hv[q].y, hv[q].z, hv[q].w};
+            float av[4];
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) av[jj] = sv[jj] * act_grad_fast(h4[jj], NGP_ACT_SOFTPLUS);
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) {
+                const float* wrow = Ws + (8 * q + 4 * lh + jj) * LDW + li;   // W1[h][c], h = 8q + 4lh + jj, c = 32 tn + li
+#pragma unroll
+                for (int tn = 0; tn < 4; tn++) acc2[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], wrow[tn * 32], acc2[tn], 0, 0, 0);
+            }
+        }
+
+        // ---- dfeat out, then grid_bwd_input_run_kernel's input gradient per level group (= the 32 columns of acc2[g])
+        float tx = 0.0f, ty = 0.0f, tz = 0.0f;
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) st[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDT + li] = acc2[g][r];
+            tile::wave_sync();
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int f = lane + 64 * i, row = f >> 3, c4 = (f & 7) * 4;
+                if (s0 + row < n)
+                    *reinterpret_cast<float4*>(dfeat + (s0 + row) * 128 + g * 32 + c4) = *reinterpret_cast<const float4*>(st + row * LDT + c4);
+            }
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            int l0 = g * 4;
+            asm volatile("" : "+s"(l0));                 // level records are loaded where they are used, not kept in SGPRs
+#pragma unroll 2
+            for (int i = 0; i < 4; i++) {
+                const LevelInfo lv = level_info(meta, l0 + i);
+                const Lead c = phase1(lv.scale, px, py, pz, lane);
+                float4 v[8];
+                corners(lv, table, c, half, v);
+                const float4 go = *reinterpret_cast<const float4*>(st + j * LDT + i * 8 + half * 4);
+                const float g4[4] = {go.x, go.y, go.z, go.w};
+                const float wx0 = 1 - c.w0, wx1 = c.w0, wy0 = 1 - c.w1, wy1 = c.w1, wz0 = 1 - c.w2, wz1 = c.w2;
+                const float dx = wy0 * wz0 * vec_dot<4>(g4, v[1], v[0]) + wy1 * wz0 * vec_dot<4>(g4, v[3], v[2]) +
+                                 wy0 * wz1 * vec_dot<4>(g4, v[5], v[4]) + wy1 * wz1 * vec_dot<4>(g4, v[7], v[6]);
+                const float dy = wx0 * wz0 * vec_dot<4>(g4, v[2], v[0]) + wx1 * wz0 * vec_dot<4>(g4, v[3], v[1]) +
+                                 wx0 * wz1 * vec_dot<4>(g4, v[6], v[4]) + wx1 * wz1 * vec_dot<4>(g4, v[7], v[5]);
+                const float dzz = wx0 * wy0 * vec_dot<4>(g4, v[4], v[0]) + wx1 * wy0 * vec_dot<4>(g4, v[5], v[1]) +
+                                  wx0 * wy1 * vec_dot<4>(g4, v[6], v[2]) + wx1 * wy1 * vec_dot<4>(g4, v[7], v[3]);
+                gx = fmaf(dx, lv.scale, gx); gy = fmaf(dy, lv.scale, gy); gz = fmaf(dzz, lv.scale, gz);
+            }
+            gx += __shfl_xor(gx, 1); gy += __shfl_xor(gy, 1); gz += __shfl_xor(gz, 1);
+            tx += gx; ty += gy; tz += gz;                // (grid_bwd_input_run_kernel: sum = 0, += each level group's wave)
+            tile::wave_sync();
+        }
+        if (!half && s0 + j < n) {
+            grads[3 * (s0 + j)] = tx; grads[3 * (s0 + j) + 1] = ty; grads[3 * (s0 + j) + 2] = tz;
         }
     }
 }
@@ -1026,6 +1273,44 @@ int ngp_grid_bwd_input(const ngp_grid_desc* desc, const float* table, const floa
         return ngp_check_launch();
     }
     GRID_DISPATCH_F(m.n_features, { launch_bwd_input<F>(m, table, x, dL_dy, lddy, n, dL_dx, st); });
+    return ngp_check_launch();
+}
+
+int ngp_density_field_layout_ok(const ngp_grid_desc* desc)
+{
+    GridMeta m;
+    return make_meta(desc, m) && m.n_levels == 16 && tile_layout_ok(m, desc) ? 1 : 0;
+}
+
+int ngp_density_field_fwd(const ngp_grid_desc* desc, const float* table, const float* x, int64_t n, const float* W1,
+                          const float* b1, const float* W2, const float* b2, float* feat, float* a1, float* sig,
+                          float* dfeat, float* grads, void* stream)
+{
+    GridMeta m;
+    if (!make_meta(desc, m) || m.n_levels != 16 || !tile_layout_ok(m, desc) || n < 0 || n > (int64_t)32 * 0x7fffff00)
+        return NGP_EINVAL;
+    if (n == 0) return NGP_OK;
+    if (!table || !x || !W1 || !W2 || !feat || !a1 || !sig || !dfeat || !grads) return NGP_EINVAL;
+    if ((((uintptr_t)W1 | (uintptr_t)feat | (uintptr_t)a1 | (uintptr_t)dfeat) & 15) != 0) return NGP_EINVAL;
+    static int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
+        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    static bool attr_set = false;
+    const size_t lds = (size_t)dens::LDS_FLOATS * sizeof(float);
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&density_field_fwd_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return NGP_ELAUNCH;
+        attr_set = true;
+    }
+    const int n_tiles = (int)((n + 31) / 32);
+    const int blocks = (n_tiles + dens::NW - 1) / dens::NW < n_cu ? (n_tiles + dens::NW - 1) / dens::NW : n_cu;
+    hipLaunchKernelGGL(density_field_fwd_kernel, dim3(blocks), dim3(64 * dens::NW), lds, (hipStream_t)stream, m, table, x,
+                       n, W1, b1, W2, b2, feat, a1, sig, dfeat, grads, n_tiles);
     return ngp_check_launch();
 }
 

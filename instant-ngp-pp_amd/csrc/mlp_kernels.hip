@@ -11,6 +11,7 @@
 // and B[k=l>>5][j=l&31]; C/D is col=l&31, row=(r&3)+8*(r>>2)+4*(l>>5).
 // Layers with n_out <= 4 (the density head, networks.py:57) use VALU kernels instead.
 #include "common.h"
+#include "mlp_act.h"
 
 namespace {
 
@@ -42,67 +43,6 @@ struct GemmArgs {
     int xf_nout, xf_act;
     float* xf_dW2; int64_t xf_lddw2; float* xf_db2;   // XF WGRAD: also dW2 += dz2^T . hidden, db2 += colsum(dz2)
 };
-
-// softplus(v) = log(1+e^v) with the hardware exp/log (v_exp_f32 / v_log_f32, ~1e-6 relative):
-// v > 20 -> v (torch's threshold); v < -15 -> e^v (1+e^v would round to 1); else log(1+e^v).
-__device__ __forceinline__ float softplus_fast(float v)
-{
-    // raw v_exp_f32 / v_log_f32 (base 2): __expf / __logf wrap them in denormal-range scaling (compare, select, ldexp: ~8 more
-    // vector instructions per element) that a softplus never needs — below v = -87 the result is < 1e-38 either way
-    const float e = __builtin_amdgcn_exp2f(v * 1.4426950408889634f);
-    float l = 0.6931471805599453f * __builtin_amdgcn_logf(1.0f + e);
-    // the logarithm is computed unconditionally and SELECTED: left inside the conditional, hipcc wraps every element of an
-    // epilogue tile in its own exec-mask branch (64 s_and_saveexec / s_cbranch / s_or per tile and wave, with their s_nop padding)
-    asm volatile("" : "+v"(l));
-    const float r = v < -15.0f ? e : l;
-    return v > 20.0f ? v : r;
-}
-
-__device__ __forceinline__ float act_fwd(float v, int act)
-{
-    switch (act) {
-        case NGP_ACT_RELU: return v > 0.0f ? v : 0.0f;
-        case NGP_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        case NGP_ACT_SOFTPLUS: return softplus_fast(v);
-        case NGP_ACT_EXP: return __expf(v);
-        default: return v;
-    }
-}
-
-// derivative of an activation expressed through its OUTPUT y, for a unit upstream gradient (bitwise what act_bwd_kernel writes)
-__device__ __forceinline__ float act_dout(float y, int act)
-{
-    switch (act) {
-        case NGP_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
-        case NGP_ACT_SIGMOID: return y * (1.0f - y);
-        case NGP_ACT_SOFTPLUS: return -expm1f(-y);
-        case NGP_ACT_EXP: return y;
-        default: return 1.0f;
-    }
-}
-
-__device__ __forceinline__ float act_grad_from_output(float y, int act)
-{
-    switch (act) {
-        case NGP_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
-        case NGP_ACT_SIGMOID: return y * (1.0f - y);
-        case NGP_ACT_SOFTPLUS: return -expm1f(-y);
-        case NGP_ACT_EXP: return y;
-        default: return 1.0f;
-    }
-}
-
-// derivative through the OUTPUT for the two hidden activations of the model, cheap enough for the
-// staging path of a GEMM (softplus' = 1 - exp(-y), v_exp_f32)
-__device__ __forceinline__ float act_grad_fast(float y, int act)
-{
-    if (act == NGP_ACT_SOFTPLUS) { // 1 - exp(-y) cancels for tiny y: two Taylor terms there (relative error < 2e-7)
-        // raw v_exp_f32 (base 2): y >= 0, so exp(-y) never needs __expf's denormal-range scaling (~5 more instructions)
-        const float e = __builtin_amdgcn_exp2f(y * -1.4426950408889634f), t = y * (1.0f - 0.5f * y);   // both sides evaluated: a select, not a branch
-        return y < 1e-3f ? t : 1.0f - e;
-    }
-    return act == NGP_ACT_RELU ? (y > 0.0f ? 1.0f : 0.0f) : act_grad_from_output(y, act);
-}
 
 constexpr int BK = 32;
 constexpr int XF_OMAX = 4;   // widest second layer the fused operand transform handles
@@ -587,6 +527,8 @@ __device__ __forceinline__ void stream_wait(f32x4& v)
     asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v) : "n"(N));
 }
 
+// density_field_fwd_kernel (grid_kernels.hip) repeats this kernel's K steps and epilogue for the density head
+// (<1, 16, SOFTPLUS, 4> / <1, SOFTPLUS>): keep the two in step (tests/test_density_fused_gpu.py compares them bit for bit).
 template <int F2, int KQ, int ACT1, int TN>   // KQ = K / 8: float4 pieces per lane and tile; TN = H / 32 column blocks
 __global__ void __launch_bounds__(512) mlp_stream_fwd_kernel(GemmArgs p, int n_tiles)
 {
@@ -770,6 +712,8 @@ __device__ __forceinline__ void stream_wait1(float& v)
 }
 
 
+// density_field_fwd_kernel (grid_kernels.hip) repeats this kernel's K steps and epilogue for the density head
+// (<1, 16, SOFTPLUS, 4> / <1, SOFTPLUS>): keep the two in step (tests/test_density_fused_gpu.py compares them bit for bit).
 template <int XF, int ACT1>
 __global__ void __launch_bounds__(512) mlp_stream_dgrad_kernel(GemmArgs p, int n_tiles)
 {

@@ -247,6 +247,18 @@ def _bound_note(model, st, slot, n_out, n):
     model._norm_bound_hits = getattr(model, "_norm_bound_hits", 0) + 1
 
 
+def _density_fused_ok(enc, W1, b1, W2, b2):
+    """whether ngp_density_field_fwd takes the density path: a 16-level F = 8 table the tile kernels take and the
+    128 -> 128 -> 1 head with contiguous (W1 16-byte aligned) parameters; anything else keeps the four launches"""
+    ok = getattr(enc, "_density_fused_layout", None)
+    if ok is None:
+        ok = enc._density_fused_layout = bool(enc.n_levels == 16 and enc.n_features == 8 and
+                                              call_host("density_field_layout_ok", enc.desc) == 1)
+    return (ok and W1.is_cuda and tuple(W1.shape) == (128, 128) and W1.is_contiguous() and W1.data_ptr() % 16 == 0
+            and W2.numel() == 128 and W2.is_contiguous() and (b1 is None or (b1.numel() == 128 and b1.is_contiguous()))
+            and (b2 is None or b2.numel() == 1))
+
+
 class _FieldFn(Function):
     """The whole NGP field (networks.py:198-240) as one autograd node: explicit kernel launches on
     preallocated buffers, no concat (both encoders write straight into rgb_net's input matrix),
@@ -284,7 +296,6 @@ class _FieldFn(Function):
         rgb_o = torch.empty(n, 3, dtype=_f32, device=dev)
         np_o = torch.empty(n, 3, dtype=_f32, device=dev)
         sem_o = torch.empty(n, C, dtype=_f32, device=dev)
-        dz2 = torch.empty(n, 1, dtype=_f32, device=dev)
         rgb_in = torch.empty(n, Kp, dtype=_f32, device=dev)
         a_r = torch.empty(n, 128, dtype=_f32, device=dev)
         a_n = torch.empty(n, 32, dtype=_f32, device=dev)
@@ -345,14 +356,20 @@ class _FieldFn(Function):
         # density head
         if ev_p is not None:
             ev_p.wait()
-        call("grid_fwd", xe.desc, xyz_table, xn, n, feat, 128)
-        # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
-        # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
-        call("mlp2_fwd_dact", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig, 1,
-             dz2)
-        # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
-        call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
-        call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, grads)
+        if _density_fused_ok(xe, W1, b1, W2, b2):
+            # encoder, both layers, d(sigma)/d(features) and d(sigma)/dx in one launch: feat, a1, sig and dfeat bitwise
+            # those of the four launches below, grads within 128 ulps of the row's largest component
+            call("density_field_fwd", xe.desc, xyz_table, xn, n, W1, b1, W2, b2, feat, a1, sig, dfeat, grads)
+        else:
+            dz2 = torch.empty(n, 1, dtype=_f32, device=dev)
+            call("grid_fwd", xe.desc, xyz_table, xn, n, feat, 128)
+            # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
+            # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
+            call("mlp2_fwd_dact", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig,
+                 1, dz2)
+            # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
+            call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
+            call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, grads)
         # dfeat = d(sigma)/d(features) is kept: the density head has ONE output, so the gradient the backward
         # sends into the density encoder is d_sigma[s] * dfeat[s] — no second data-gradient product there
 
