@@ -536,6 +536,45 @@ int ngp_mesh_compact_rows(const void* src, int row_bytes, int n_verts, int n_fac
 int ngp_mesh_compact_faces(const int32_t* faces, int n_faces, int n_verts, const int32_t* workspace,
                            int32_t* faces_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * I1  SSIM of rendered images (replaces torchmetrics' StructuralSimilarityIndexMeasure(data_range=1) of the
+ *     reference's validation step, train.py:93,353-386; no conv2d / MIOpen on the way)
+ * pred, gt: `count` images of H*W rows of 3 floats, row-major, channel-last (what render() returns and the loaders
+ * keep in `rays`).  out (count) f32: the mean SSIM of each image over its (H-10) x (W-10) fully inside window
+ * positions and 3 channels.  Window 11x11 separable Gaussian, sigma 1.5, taps exp(-x^2/(2 sigma^2)), x = -5..5,
+ * normalised to sum 1 (double on the host, rounded once to float); per window mu_x, mu_y, var_x = E[x^2] - mu_x^2,
+ * var_y, cov_xy; C1 = 0.01^2, C2 = 0.03^2; ssim = (2 mu_x mu_y + C1)(2 cov_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x +
+ * var_y + C2)).  Moments are accumulated in float about a per-tile pivot (the tile's centre pixel: no
+ * cancellation in the variances where a 26x26 tile is flat; a window on another flat level of a tile that straddles an
+ * edge is evaluated as well as in plain float32, no better), per-workgroup sums
+ * go to `partial` (ngp_ssim_workspace(count, H, W) doubles, host-only query) and a second launch adds them in a fixed
+ * order in double: no atomics, the same bits from run to run and for an image alone or inside a batch.
+ * count == 0 returns NGP_OK before anything else is looked at; H or W < 11, H*W > INT32_MAX/3, count > 65535 or a
+ * NULL pointer is NGP_EINVAL.
+ * ---------------------------------------------------------------------- */
+int64_t ngp_ssim_workspace(int count, int H, int W);
+int ngp_ssim(const float* pred, const float* gt, int count, int H, int W, double* partial, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * I2  8-bit frames from the per-ray outputs of the test-time renderer, one launch per frame (replaces the numpy /
+ *     cv2 conversions of the reference's render.py:17-31,150-185 and utils.py:84-95 done on the host in float)
+ * With u8(v) = (uint8)(clip(v, 0, 1) * 255) (truncation), all in float32 in the order written, true division:
+ *   rgb_u8 (n,3)        = u8(rgb (n,3))                                            render.py:158-159
+ *   opacity_u8 (n)      = u8(opacity (n))
+ *   depth_u8 (n,3)      = lut[u8(depth (n) / depth_scale)]                         render.py:17-23,168
+ *   normal_u8, normal_raw_u8 (n,3): n' = n + 1e-6, c_j = (n'_0 R_0j + n'_1 R_1j) + n'_2 R_2j, u8((c_j + 1) / 2)
+ *                         with R (3,3) row-major DEVICE floats, the frame's camera-to-world rotation
+ *                         (convert_normal: world -> camera)                        utils.py:92-95, render.py:176-185
+ *   semantic_u8 (n,3)   = lut[u8(level * (float)semantic (n) int64)], level = 1.0f / (classes - 1)   render.py:25-31
+ * lut (256,3) uint8 is the colour table (the package ships Turbo).  Every output pointer is optional (NULL = not
+ * wanted); an output that is asked for needs its inputs (and classes >= 2 for semantic_u8), else NGP_EINVAL.
+ * n == 0 returns NGP_OK before any pointer is looked at.
+ * ---------------------------------------------------------------------- */
+int ngp_frame_pack(int64_t n, const float* rgb, const float* opacity, const float* depth, float depth_scale,
+                   const float* normal_pred, const float* normal_raw, const float* R, const int64_t* semantic,
+                   int classes, const uint8_t* lut, uint8_t* rgb_u8, uint8_t* opacity_u8, uint8_t* depth_u8,
+                   uint8_t* normal_u8, uint8_t* normal_raw_u8, uint8_t* semantic_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,13 +10,16 @@ Sub-modules (same names / call signatures as zhihao-lin/instant-ngp-pp):
   losses            — NeRFLoss, DistortionLoss
   trainer           — the training schedule of train.py (no Lightning)
   mesh              — marching cubes + PLY export (extract_mesh.py)
+  metrics           — psnr, ssim
+  evaluation        — whole frames from a camera, their 8-bit images, PSNR / SSIM of a split (render.py, validation)
 
 Every compute call goes through libngp_hip.so (include/ngp_hip.h); there is no CPU fallback.
 """
 from . import _lib  # noqa: F401  (parses the header; the .so is loaded on first use)
 
 __all__ = ["vren", "tinycudann", "torch_scatter", "custom_functions", "rendering", "networks", "losses",
-           "metrics", "trainer", "synthetic", "ckpt", "mesh", "install_as_reference_modules"]
+           "metrics", "trainer", "synthetic", "ckpt", "mesh", "evaluation", "colormap",
+           "install_as_reference_modules"]
 
 
 def __getattr__(name):

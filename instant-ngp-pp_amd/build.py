@@ -25,6 +25,7 @@ SOURCES = [
     ("mlp_kernels.hip", []),
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),
+    ("image_kernels.hip", ["-ffp-contract=off"]),   # frame packing is bit-identical to its numpy restatement
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

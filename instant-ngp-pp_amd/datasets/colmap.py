@@ -137,3 +137,4 @@ class ColmapDataset(BaseDataset):
                                            .astype(np.int64))
         if split == 'test' and path_poses is not None:
             self.render_traj_rays = self.get_path_rays(path_poses)
+            self.render_c2w = torch.as_tensor(np.asarray(path_poses), dtype=torch.float32)[:, :3]  # render.py:98

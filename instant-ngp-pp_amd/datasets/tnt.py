@@ -117,3 +117,4 @@ class tntDataset(BaseDataset):
             self.depths_2d = torch.from_numpy(np.stack([np.load(p).reshape(-1) for p in depths]).astype(np.float32))
         if not split.startswith('train') and path_c2w is not None:
             self.render_traj_rays = self.get_path_rays(path_c2w)
+            self.render_c2w = torch.as_tensor(path_c2w, dtype=torch.float32)[:, :3]  # render.py:98

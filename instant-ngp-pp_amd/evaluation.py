@@ -1,0 +1,140 @@
+"""Image-shaped outputs of the test-time renderer: whole frames from one camera, their 8-bit images, and the metrics of
+a held-out split (what the reference's render.py:50-218 and validation step train.py:347-392 do).
+
+  render_image(model, directions, pose, chunk, **render_kwargs) -> the per-ray results of render(test_time=True)
+  render_rays(model, rays_o, rays_d, chunk, **render_kwargs)    -> the same for given rays (a camera path's)
+  image_metrics(rgb, gt, img_wh)                                -> (psnr, ssim) of one image on the device
+  frame_images(results, pose, scale, num_classes, want, img_wh) -> {name: uint8 image} through ngp_frame_pack (I2)
+  evaluate_split(model, test_set, ...)                          -> {'psnr': [...], 'ssim': [...]} per held-out image
+"""
+import torch
+
+from ._lib import call, check_input
+from .colormap import turbo_lut
+from .datasets.ray_utils import get_rays
+from .metrics import psnr, ssim
+from .rendering import render_chunks
+
+# image name -> (results key, channels of the packed image)
+FRAME_OUTPUTS = {"rgb": ("rgb", 3), "opacity": ("opacity", 1), "depth": ("depth", 3), "normal": ("normal_pred", 3),
+                 "normal_raw": ("normal_raw", 3), "semantic": ("semantic", 3)}
+_LUTS = {}
+
+
+def colour_table(device):
+    """the shipped Turbo table as a (256, 3) uint8 tensor on `device` (uploaded once per device)"""
+    device = torch.device(device)
+    if device not in _LUTS:
+        _LUTS[device] = torch.from_numpy(turbo_lut()).to(device)
+    return _LUTS[device]
+
+
+@torch.no_grad()
+def render_rays(model, rays_o, rays_d, chunk=131072, **render_kwargs):
+    """render_chunks(test_time=True, T_threshold=1e-2) over the rays of one frame in chunks of `chunk` rays -> the
+    results dictionary (per-ray tensors; `total_samples` a list, one per chunk)"""
+    kwargs = {"test_time": True, "T_threshold": 1e-2}
+    kwargs.update(render_kwargs)
+    return render_chunks(model, rays_o.contiguous(), rays_d.contiguous(), chunk, **kwargs)
+
+
+@torch.no_grad()
+def render_image(model, directions, pose, chunk=131072, **render_kwargs):
+    """One camera: render_rays of get_rays(directions, pose) (h*w rows)"""
+    rays_o, rays_d = get_rays(directions, pose)
+    return render_rays(model, rays_o, rays_d, chunk, **render_kwargs)
+
+
+def pack_frame(n, rgb=None, opacity=None, depth=None, depth_scale=1.0, normal_pred=None, normal_raw=None,
+               rotation=None, semantic=None, classes=0, lut=None):
+    """ngp_frame_pack on per-ray tensors: each input that is given yields its packed uint8 tensor ((n,3), opacity (n))
+    under the names of FRAME_OUTPUTS; one launch."""
+    ins = {"rgb": rgb, "opacity": opacity, "depth": depth, "normal": normal_pred, "normal_raw": normal_raw,
+           "semantic": semantic}
+    if all(t is None for t in ins.values()):
+        raise ValueError("no input to pack")
+    dev = next(t.device for t in ins.values() if t is not None)
+    for name, t in ins.items():
+        if t is None:
+            continue
+        check_input(t, name)
+        want_dtype = torch.int64 if name == "semantic" else torch.float32
+        rows = (n,) if name in ("opacity", "depth", "semantic") else (n, 3)
+        if t.dtype != want_dtype or tuple(t.shape) != rows:
+            raise ValueError(f"{name} must be {rows} {want_dtype}, got {tuple(t.shape)} {t.dtype}")
+    if (normal_pred is not None or normal_raw is not None):
+        if rotation is None:
+            raise ValueError("normals need the camera-to-world rotation")
+        check_input(rotation, "rotation")
+        if rotation.dtype != torch.float32 or tuple(rotation.shape) != (3, 3):
+            raise ValueError(f"rotation must be (3, 3) float32, got {tuple(rotation.shape)} {rotation.dtype}")
+    if depth is not None or semantic is not None:
+        lut = colour_table(dev) if lut is None else lut
+        check_input(lut, "lut")
+        if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+            raise ValueError(f"lut must be (256, 3) uint8, got {tuple(lut.shape)} {lut.dtype}")
+    if semantic is not None and int(classes) < 2:
+        raise ValueError(f"semantic images need classes >= 2, got {classes}")
+    out = {name: torch.empty((n,) if name == "opacity" else (n, 3), dtype=torch.uint8, device=dev)
+           for name, t in ins.items() if t is not None}
+    call("frame_pack", n, rgb, opacity, depth, float(depth_scale), normal_pred, normal_raw, rotation, semantic,
+         int(classes), lut, *[out.get(k) for k in ("rgb", "opacity", "depth", "normal", "normal_raw", "semantic")])
+    return out
+
+
+@torch.no_grad()
+def frame_images(results, pose, scale, num_classes=7, want=("rgb", "depth", "normal", "normal_raw", "semantic"),
+                 img_wh=None):
+    """The 8-bit images of one frame, as the reference's render.py writes them, packed on the device in one launch:
+    rgb, opacity, depth (Turbo of depth / (2 * scale)), normal / normal_raw (world -> camera through `pose`, then
+    (c + 1) / 2), semantic (Turbo of label / (num_classes - 1)) -> {name: uint8 tensor}, (h*w[, 3]) rows, or
+    (H, W[, 3]) with img_wh=(W, H)."""
+    unknown = [w for w in want if w not in FRAME_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown frame outputs {unknown}; known: {sorted(FRAME_OUTPUTS)}")
+    n = results["rgb"].shape[0]
+    ins = {}
+    for name in want:
+        t = results[FRAME_OUTPUTS[name][0]]
+        ins[name] = (t.reshape(n) if name == "semantic" else t).contiguous()
+    rot = None
+    if "normal" in ins or "normal_raw" in ins:
+        rot = torch.as_tensor(pose, dtype=torch.float32, device=results["rgb"].device)[:3, :3].contiguous()
+    out = pack_frame(n, rgb=ins.get("rgb"), opacity=ins.get("opacity"), depth=ins.get("depth"),
+                     depth_scale=2 * float(scale), normal_pred=ins.get("normal"), normal_raw=ins.get("normal_raw"),
+                     rotation=rot, semantic=ins.get("semantic"), classes=num_classes)
+    if img_wh is not None:
+        w, h = img_wh
+        out = {k: v.reshape((h, w) + tuple(v.shape[1:])) for k, v in out.items()}
+    return out
+
+
+@torch.no_grad()
+def image_metrics(rgb, gt, img_wh):
+    """(psnr, ssim) of one rendered image against its ground truth, both (h*w, 3): rgb is clamped to [0, 1] first, as
+    the reference's validation step does -> two 0-dim tensors on the device (no read-back) and the clamped image"""
+    rgb = rgb.clamp(0, 1)
+    gt = gt.to(rgb.device).contiguous()
+    return psnr(rgb, gt), ssim(rgb, gt, img_wh=img_wh), rgb
+
+
+@torch.no_grad()
+def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs):
+    """Per-image PSNR and SSIM of a held-out split through render(test_time=True) (train.py:347-392): rgb is clamped
+    to [0, 1] and compared with the split's ground truth -> {'psnr': [floats], 'ssim': [floats]}.  `on_image(i, rgb,
+    results)` is called with each clamped (h*w, 3) image and its results dictionary (to save frames).  The metrics stay
+    on the device until every image is rendered: one read-back at the end."""
+    psnrs, ssims = [], []
+    for i in range(len(test_set)):
+        s = test_set[i]
+        if "rgb" not in s:
+            raise ValueError("the split has no ground-truth images to evaluate against")
+        results = render_image(model, test_set.directions, s["pose"], chunk, **render_kwargs)
+        p, q, rgb = image_metrics(results["rgb"], s["rgb"], test_set.img_wh)
+        psnrs.append(p)
+        ssims.append(q)
+        if on_image is not None:
+            on_image(i, rgb, results)
+    if not psnrs:
+        return {"psnr": [], "ssim": []}
+    return {"psnr": torch.stack(psnrs).tolist(), "ssim": torch.stack(ssims).tolist()}

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Renders a frame series from a trained checkpoint (the reference's render.py:50-218): rgb / depth / normal /
+semantic frames as PNG files and the depth points as points.npy, along the test split's poses or the dataset's own
+camera path.  GPU only.  The 8-bit frames are packed on the device (ngp_frame_pack), so one byte per channel crosses to
+the host.  Prints one JSON line: frames, the seconds spent rendering, on the metrics, packing, copying device->host
+and encoding PNGs, and, when the split has ground truth, mean and per-image PSNR / SSIM.  No video is written: the frame directory is
+what a video encoder takes.
+
+  python tools/render.py --ckpt ckpts/lego.ckpt --root_dir /data/nerf_synthetic/lego --out_dir frames --render_rgb
+  python tools/render.py --ckpt ckpts/tnt.ckpt --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 \\
+      --exp_step_factor 0.00390625 --render_traj --render_rgb --render_depth --render_normal --out_dir frames
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FILES = {"rgb": "rgb", "depth": "depth", "normal": "normal", "normal_raw": "normal-raw", "semantic": "semantic"}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(
+        description="Frame series of a trained model: NNN-rgb.png, NNN-depth.png, NNN-normal.png, NNN-normal-raw.png, "
+                    "NNN-semantic.png and points.npy (float32 (frames, H, W, 3)) in --out_dir.",
+        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ap.add_argument("--ckpt", required=True, help="checkpoint ({'state_dict': {'model.<key>': ...}})")
+    ap.add_argument("--scale", type=float, default=0.5)
+    ap.add_argument("--root_dir", required=True)
+    ap.add_argument("--dataset_name", default="nerf", help="nerf, nsvf, colmap, tnt or nerfpp")
+    ap.add_argument("--downsample", type=float, default=1.0)
+    ap.add_argument("--exp_step_factor", type=float, default=0.0, help="1/256 for unbounded scenes (opt.py)")
+    ap.add_argument("--num_classes", type=int, default=7)
+    ap.add_argument("--chunk_size", type=int, default=131072, help="rays per render() call")
+    ap.add_argument("--out_dir", required=True)
+    ap.add_argument("--render_rgb", action="store_true", help="render rgb series")
+    ap.add_argument("--render_depth", action="store_true", help="render depth series (Turbo of depth / (2 * scale))")
+    ap.add_argument("--render_normal", action="store_true", help="render normal series (predicted and raw)")
+    ap.add_argument("--render_semantic", action="store_true", help="render semantic segmentation series")
+    ap.add_argument("--render_points", action="store_true", help="render depth points (points.npy)")
+    ap.add_argument("--render_traj", action="store_true",
+                    help="follow the dataset's own camera path (render_traj_rays) instead of the test poses")
+    args = ap.parse_args(argv)
+    if args.chunk_size <= 0:
+        ap.error("--chunk_size must be positive")
+    if not (args.render_rgb or args.render_depth or args.render_normal or args.render_semantic or args.render_points):
+        ap.error("nothing to render: give at least one of --render_rgb --render_depth --render_normal "
+                 "--render_semantic --render_points")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import numpy as np
+    import torch
+    from PIL import Image
+    import ngp_amd  # noqa: F401
+    from ngp_amd import ckpt
+    from ngp_amd.datasets import dataset_dict
+    from ngp_amd.evaluation import frame_images, image_metrics, render_image, render_rays
+    from ngp_amd.networks import NGP
+
+    if args.dataset_name not in dataset_dict:
+        raise SystemExit(f"unknown --dataset_name {args.dataset_name}; known: {sorted(dataset_dict)}")
+    dev = torch.device("cuda", 0)
+    model = NGP(scale=args.scale, classes=args.num_classes).to(dev)
+    ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model', 'density_grid', 'grid_coords'])
+    test_set = dataset_dict[args.dataset_name](args.root_dir, "test", args.downsample, device=dev,
+                                               render_traj=args.render_traj, num_classes=args.num_classes)
+    w, h = test_set.img_wh
+    directions = test_set.directions.to(dev)
+    if args.render_traj:
+        if getattr(test_set, "render_traj_rays", None) is None or getattr(test_set, "render_c2w", None) is None:
+            raise SystemExit(f"--render_traj: the {args.dataset_name} loader found no camera path for {args.root_dir} "
+                             "(no render_traj_rays); render the test poses instead")
+        traj_rays = test_set.render_traj_rays                # the loader's own rays; the poses only rotate the normals
+        poses = test_set.render_c2w.to(dev)
+        have_gt = False
+    else:
+        poses = test_set.poses.to(dev)
+        have_gt = len(test_set.rays) > 0
+
+    want = [k for k, on in (("rgb", args.render_rgb), ("depth", args.render_depth), ("normal", args.render_normal),
+                            ("normal_raw", args.render_normal), ("semantic", args.render_semantic)) if on]
+    os.makedirs(args.out_dir, exist_ok=True)
+    t = {"render_s": 0.0, "metrics_s": 0.0, "pack_s": 0.0, "d2h_s": 0.0, "png_s": 0.0}
+    psnrs, ssims, points = [], [], []
+    render_kwargs = {"exp_step_factor": args.exp_step_factor, "num_classes": args.num_classes}
+
+    def tick():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    for i in range(len(poses)):
+        gt = test_set[i]["rgb"].to(dev) if have_gt else None      # a split kept on the host is copied outside the stages
+        t0 = tick()
+        if args.render_traj:
+            rays = traj_rays[i][:, :6].to(dev)
+            results = render_rays(model, rays[:, :3], rays[:, 3:6], args.chunk_size, **render_kwargs)
+        else:
+            results = render_image(model, directions, poses[i], args.chunk_size, **render_kwargs)
+        t1 = tick()
+        if have_gt:
+            p, q, _ = image_metrics(results["rgb"], gt, (w, h))
+            psnrs.append(p)
+            ssims.append(q)
+        tm = tick()
+        images = frame_images(results, poses[i], args.scale, args.num_classes, want, img_wh=(w, h)) if want else {}
+        t2 = tick()
+        images = {k: v.cpu().numpy() for k, v in images.items()}
+        if args.render_points:
+            points.append(results["points"].reshape(h, w, 3).cpu().numpy())
+        t3 = tick()
+        for k, img in images.items():
+            Image.fromarray(img).save(os.path.join(args.out_dir, f"{i:03d}-{FILES[k]}.png"))
+        t4 = time.perf_counter()
+        for key, dt in zip(t, (t1 - t0, tm - t1, t2 - tm, t3 - t2, t4 - t3)):
+            t[key] += dt
+    if args.render_points:
+        np.save(os.path.join(args.out_dir, "points.npy"), np.stack(points).astype(np.float32))
+    line = {"frames": len(poses), "img_wh": [w, h], "outputs": want + (["points"] if args.render_points else []),
+            **{k: round(v, 4) for k, v in t.items()}}
+    if have_gt and psnrs:
+        p, s = torch.stack(psnrs).tolist(), torch.stack(ssims).tolist()
+        line.update(psnr_mean=sum(p) / len(p), psnr=p, ssim_mean=sum(s) / len(s), ssim=s)
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()

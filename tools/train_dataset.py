@@ -18,10 +18,10 @@ sys.path.insert(0, ROOT)
 import torch
 import ngp_amd  # noqa: F401
 from ngp_amd import ckpt
-from ngp_amd.datasets import dataset_dict, get_rays, write_synthetic_dataset
+from ngp_amd.datasets import dataset_dict, write_synthetic_dataset
+from ngp_amd.evaluation import evaluate_split
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
-from ngp_amd.rendering import render
 from ngp_amd.trainer import NGPTrainer
 
 
@@ -64,25 +64,22 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     return trainer
 
 
-@torch.no_grad()
+def _save_rgb(save_dir, img_wh):
+    """on_image callback of evaluate_split: writes each clamped rgb image as <save_dir>/NNN.png"""
+    w, h = img_wh
+
+    def save(i, rgb, results):
+        from PIL import Image
+        os.makedirs(save_dir, exist_ok=True)
+        Image.fromarray((rgb.reshape(h, w, 3).cpu().numpy() * 255 + 0.5).astype("uint8")).save(
+            os.path.join(save_dir, f"{i:03d}.png"))
+    return save
+
+
 def evaluate(model, test_set, chunk=131072, save_dir=None, exp_step_factor=0.0):
     """per-image PSNR of the test split through render(test_time=True) (train.py:347-392)"""
-    w, h = test_set.img_wh
-    out = []
-    for i in range(len(test_set)):
-        s = test_set[i]
-        o, d = get_rays(test_set.directions, s["pose"])
-        o, d = o.contiguous(), d.contiguous()
-        rgb = torch.cat([render(model, o[j:j + chunk], d[j:j + chunk], test_time=True, T_threshold=1e-2,
-                                exp_step_factor=exp_step_factor)["rgb"]
-                         for j in range(0, o.shape[0], chunk)], 0).clamp(0, 1)
-        out.append(float(psnr(rgb, s["rgb"])))
-        if save_dir:
-            from PIL import Image
-            os.makedirs(save_dir, exist_ok=True)
-            Image.fromarray((rgb.reshape(h, w, 3).cpu().numpy() * 255 + 0.5).astype("uint8")).save(
-                os.path.join(save_dir, f"{i:03d}.png"))
-    return out
+    return evaluate_split(model, test_set, chunk, on_image=_save_rgb(save_dir, test_set.img_wh) if save_dir else None,
+                          exp_step_factor=exp_step_factor)["psnr"]
 
 
 def main():
@@ -118,10 +115,13 @@ def main():
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
-    psnrs = evaluate(model, test_set, save_dir=args.save_dir, exp_step_factor=args.exp_step_factor)
+    res = evaluate_split(model, test_set, on_image=_save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None,
+                         exp_step_factor=args.exp_step_factor)
+    psnrs, ssims = res["psnr"], res["ssim"]
     if args.ckpt_path:
         ckpt.save_ckpt(model, args.ckpt_path)
     print(json.dumps({"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
+                      "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
                       "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}))
 
 
