@@ -575,6 +575,28 @@ int ngp_frame_pack(int64_t n, const float* rgb, const float* opacity, const floa
                    int classes, const uint8_t* lut, uint8_t* rgb_u8, uint8_t* opacity_u8, uint8_t* depth_u8,
                    uint8_t* normal_u8, uint8_t* normal_raw_u8, uint8_t* semantic_u8, void* stream);
 
+/* ------------------------------------------------------------------------
+ * I3  8-bit antialiased bicubic resize, one launch per call: what PIL.Image.resize((out_w, out_h), BICUBIC) returns
+ *     for `L` and `RGB` images, byte for byte (brings the supersampled frames of --anti_aliasing_factor back to the
+ *     image size, render.py:150-156 of the reference, without copying the large frame to the host)
+ * src: `count` images of (in_h, in_w, channels) bytes, row-major, channel-last; dst the same at (out_h, out_w);
+ * channels 1 or 3.  The taps are computed by the caller in float64 per axis (n_in -> n_out samples; an axis with
+ * n_in == n_out has no pass and takes NULL taps): scale = n_in / n_out, fs = max(scale, 1), support = 2 fs,
+ * ksize = ceil(support) * 2 + 1; for output xx: center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5),
+ * 0), xmax = min((int)(center + support + 0.5), n_in) - xmin, k[x] = f((x + xmin - center + 0.5) / fs) for x < xmax
+ * with f the Keys cubic (a = -0.5), normalised by their sum taken in order; kk[x] = (int)(k[x] 2^22 +- 0.5) (toward
+ * zero), unused slots 0.  k* (n_out, ksize) int32 and b* (n_out, 2) int32 = (xmin, xmax) are DEVICE arrays.
+ * Rows first into an 8-bit intermediate (kept in LDS), then columns; each byte is
+ * clip((2^21 + sum_x src[xmin + x] kk[x]) >> 22, 0, 255) in int32.  Integers only and no atomics: the same bits from
+ * run to run and for an image alone or inside a batch.
+ * count == 0 returns NGP_OK before anything else is looked at, count < 0 is NGP_EINVAL; then NGP_EINVAL for channels
+ * other than 1 or 3, a non-positive size, count > 65535, n_in > 8 n_out on an axis, a ksize that is not the one above
+ * on an axis that changes, or a NULL pointer that is needed.  Both axes unchanged is a copy.
+ * ---------------------------------------------------------------------- */
+int ngp_resize_bicubic_u8(const uint8_t* src, int count, int in_h, int in_w, int channels, uint8_t* dst, int out_h,
+                          int out_w, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky,
+                          const int32_t* by, int ksize_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

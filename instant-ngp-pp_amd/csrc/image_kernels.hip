@@ -23,6 +23,12 @@
 //
 // Frame packing.  One thread per ray, one launch per frame, every output optional; float32 in the order written in
 // include/ngp_hip.h, truncating conversion to uint8 as numpy's astype does for values in [0, 255].
+//
+// Resampling.  Pillow's 8-bit antialiased bicubic resize (ImagingResample: precomputed 22-bit fixed-point taps, a
+// horizontal pass into an 8-bit intermediate, then a vertical pass), for the supersampled frames of
+// --anti_aliasing_factor.  Integers only.  One launch: a workgroup owns tile_w x tile_h output pixels, stages the
+// input window those need in LDS, writes the row pass to LDS and runs the column pass from there; the intermediate
+// image never exists in HBM.  The host picks the tile from the ratio so that window + intermediate fit RS_LDS_BYTES.
 #include "common.h"
 #include <math.h>
 
@@ -212,6 +218,117 @@ __global__ void __launch_bounds__(PACK_BLOCK) frame_pack_kernel(PackArgs a, int6
     if (a.semantic_u8) pack_lut(a.lut, a.level * (float)a.semantic[i], i, a.semantic_u8);
 }
 
+// ------------------------------------------------------------------------------------------------------- resampling
+constexpr int RS_THREADS = 256;
+constexpr int RS_BITS = 22;                      // Pillow's PRECISION_BITS for 8-bit images
+constexpr int RS_MAX_RATIO = 8;
+constexpr int RS_LDS_BYTES = 48 * 1024;          // window + intermediate of the chosen tile stay at or under this
+
+struct ResizeArgs {
+    const uint8_t* src;
+    uint8_t* dst;
+    const int32_t* kx;   // (out_w, ksize_x) taps, NULL: the axis is unchanged
+    const int32_t* bx;   // (out_w, 2) first input column and tap count
+    const int32_t* ky;
+    const int32_t* by;
+    int in_h, in_w, out_h, out_w, ch;
+    int ksize_x, ksize_y;
+    int tile_w, tile_h;  // output pixels per workgroup
+    int win_w, win_h;    // staged input pixels per workgroup (an upper bound of what any tile needs)
+};
+
+__device__ __forceinline__ uint8_t rs_clip8(int acc)
+{
+    return (uint8_t)min(max(acc >> RS_BITS, 0), 255);
+}
+
+// sum over n taps of v[i * stride] * k[i], rounded as Pillow rounds
+__device__ __forceinline__ uint8_t rs_filter(const uint8_t* v, int stride, const int32_t* __restrict__ k, int n)
+{
+    int acc = 1 << (RS_BITS - 1);
+    for (int i = 0; i < n; i++) acc += (int)v[i * stride] * k[i];
+    return rs_clip8(acc);
+}
+
+__global__ void __launch_bounds__(RS_THREADS) resize_bicubic_u8_kernel(ResizeArgs a)
+{
+    extern __shared__ uint8_t rs_lds[];
+    const int C = a.ch;
+    const int win_pitch = a.win_w * C, mid_pitch = a.tile_w * C;
+    uint8_t* win = rs_lds;                          // [win_h][win_w * C] input window
+    uint8_t* mid = rs_lds + a.win_h * win_pitch;    // [win_h][tile_w * C] row-filtered window
+
+    const int tid = threadIdx.x;
+    const int ox0 = blockIdx.x * a.tile_w, oy0 = blockIdx.y * a.tile_h;
+    const int tw = min(a.tile_w, a.out_w - ox0), th = min(a.tile_h, a.out_h - oy0);
+    // the first input column / row any output of the tile reads: the bounds do not decrease along an axis.  Every
+    // index taken from the bounds is clamped into what was staged, whatever the arrays hold.
+    const int ix0 = a.kx ? min(max(a.bx[2 * ox0], 0), a.in_w - 1) : ox0;
+    const int iy0 = a.ky ? min(max(a.by[2 * oy0], 0), a.in_h - 1) : oy0;
+    const int ww = min(a.win_w, a.in_w - ix0), wh = min(a.win_h, a.in_h - iy0);
+    const uint8_t* __restrict__ S = a.src + (int64_t)blockIdx.z * a.in_h * a.in_w * C;
+    uint8_t* __restrict__ D = a.dst + (int64_t)blockIdx.z * a.out_h * a.out_w * C;
+
+    // stage: a window row is ww * C contiguous bytes
+    const int row_bytes = ww * C;
+    for (int i = tid; i < wh * row_bytes; i += RS_THREADS) {
+        const int r = i / row_bytes, e = i - r * row_bytes;
+        win[r * win_pitch + e] = S[((int64_t)(iy0 + r) * a.in_w + ix0) * C + e];
+    }
+    __syncthreads();
+
+    // rows: every staged row to the tile's tw output columns
+    const int out_bytes = tw * C;
+    for (int i = tid; i < wh * out_bytes; i += RS_THREADS) {
+        const int r = i / out_bytes, e = i - r * out_bytes;
+        uint8_t v;
+        if (a.kx) {
+            const int c = e / C, ch = e - c * C, xx = ox0 + c;
+            const int off = a.bx[2 * xx] - ix0;
+            int n = min(a.bx[2 * xx + 1], a.ksize_x);
+            n = (off < 0 || off > ww) ? 0 : min(n, ww - off);
+            v = rs_filter(win + r * win_pitch + off * C + ch, C, a.kx + (int64_t)xx * a.ksize_x, n);
+        } else {
+            v = win[r * win_pitch + e];
+        }
+        mid[r * mid_pitch + e] = v;
+    }
+    __syncthreads();
+
+    // columns
+    for (int i = tid; i < th * out_bytes; i += RS_THREADS) {
+        const int r = i / out_bytes, e = i - r * out_bytes;
+        uint8_t v;
+        if (a.ky) {
+            const int yy = oy0 + r;
+            const int off = a.by[2 * yy] - iy0;
+            int n = min(a.by[2 * yy + 1], a.ksize_y);
+            n = (off < 0 || off > wh) ? 0 : min(n, wh - off);
+            v = rs_filter(mid + off * mid_pitch + e, mid_pitch, a.ky + (int64_t)yy * a.ksize_y, n);
+        } else {
+            v = mid[r * mid_pitch + e];
+        }
+        D[((int64_t)(oy0 + r) * a.out_w + ox0) * C + e] = v;
+    }
+}
+
+// Pillow's tap count for n_in -> n_out samples
+int rs_ksize(int n_in, int n_out)
+{
+    const double scale = (double)n_in / (double)n_out;
+    return (int)ceil(2.0 * (scale > 1.0 ? scale : 1.0)) * 2 + 1;
+}
+
+// input samples a tile of `tile` outputs can read: its centres span (tile - 1) * scale, and a row of taps starts no
+// earlier than centre - support - 0.5 and ends no later than centre + support + 0.5
+int rs_window(int n_in, int n_out, int tile)
+{
+    if (n_in == n_out) return tile;
+    const double scale = (double)n_in / (double)n_out, support = 2.0 * (scale > 1.0 ? scale : 1.0);
+    const double span = floor((tile - 1) * scale + 2.0 * support) + 2.0;
+    return span < (double)n_in ? (int)span : n_in;
+}
+
 }  // namespace
 
 extern "C" {
@@ -279,6 +396,54 @@ int ngp_frame_pack(int64_t n, const float* rgb, const float* opacity, const floa
     a.level = classes >= 2 ? 1.0f / (float)(classes - 1) : 0.f;
     hipLaunchKernelGGL(frame_pack_kernel, dim3((unsigned)((n + PACK_BLOCK - 1) / PACK_BLOCK)), dim3(PACK_BLOCK), 0,
                        (hipStream_t)stream, a, n);
+    return ngp_check_launch();
+}
+
+int ngp_resize_bicubic_u8(const uint8_t* src, int count, int in_h, int in_w, int channels, uint8_t* dst, int out_h,
+                          int out_w, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky,
+                          const int32_t* by, int ksize_y, void* stream)
+{
+    if (count < 0) return NGP_EINVAL;
+    if (count == 0) return NGP_OK;
+    if (channels != 1 && channels != 3) return NGP_EINVAL;
+    if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 || count > 65535) return NGP_EINVAL;
+    if ((int64_t)in_h > (int64_t)RS_MAX_RATIO * out_h || (int64_t)in_w > (int64_t)RS_MAX_RATIO * out_w)
+        return NGP_EINVAL;
+    const bool pass_x = in_w != out_w, pass_y = in_h != out_h;
+    if (!src || !dst || (pass_x && (!kx || !bx)) || (pass_y && (!ky || !by))) return NGP_EINVAL;
+    if ((pass_x && ksize_x != rs_ksize(in_w, out_w)) || (pass_y && ksize_y != rs_ksize(in_h, out_h)))
+        return NGP_EINVAL;
+    ResizeArgs a;
+    a.src = src;
+    a.dst = dst;
+    a.kx = pass_x ? kx : nullptr;
+    a.bx = pass_x ? bx : nullptr;
+    a.ky = pass_y ? ky : nullptr;
+    a.by = pass_y ? by : nullptr;
+    a.in_h = in_h;
+    a.in_w = in_w;
+    a.out_h = out_h;
+    a.out_w = out_w;
+    a.ch = channels;
+    a.ksize_x = ksize_x;
+    a.ksize_y = ksize_y;
+    // the largest tile whose window and intermediate fit the budget: 32 x 16 up to ratio 4 on both axes with three
+    // channels, 16 x 8 (45.9 KB) at ratio 8
+    static const int tiles[][2] = {{32, 16}, {32, 8}, {16, 16}, {16, 8}};
+    int lds = 0;
+    for (const auto& t : tiles) {
+        a.tile_w = t[0];
+        a.tile_h = t[1];
+        a.win_w = rs_window(in_w, out_w, a.tile_w);
+        a.win_h = rs_window(in_h, out_h, a.tile_h);
+        lds = a.win_h * (a.win_w + a.tile_w) * channels;
+        if (lds <= RS_LDS_BYTES) break;
+    }
+    if (lds > RS_LDS_BYTES) return NGP_EINVAL;
+    const int64_t gx = (out_w + a.tile_w - 1) / a.tile_w, gy = (out_h + a.tile_h - 1) / a.tile_h;
+    if (gy > 65535) return NGP_EINVAL;
+    hipLaunchKernelGGL(resize_bicubic_u8_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)count), dim3(RS_THREADS),
+                       (size_t)lds, (hipStream_t)stream, a);
     return ngp_check_launch();
 }
 

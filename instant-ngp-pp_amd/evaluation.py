@@ -1,17 +1,22 @@
 """Image-shaped outputs of the test-time renderer: whole frames from one camera, their 8-bit images, and the metrics of
 a held-out split (what the reference's render.py:50-218 and validation step train.py:347-392 do).
 
-  render_image(model, directions, pose, chunk, **render_kwargs) -> the per-ray results of render(test_time=True)
+  render_image(model, directions, pose, chunk, **render_kwargs) -> the per-ray results of render(test_time=True);
+                                                                   anti_aliasing_factor=s, K=, img_wh= renders the
+                                                                   int(h*s) x int(w*s) lattice of the same camera
   render_rays(model, rays_o, rays_d, chunk, **render_kwargs)    -> the same for given rays (a camera path's)
   image_metrics(rgb, gt, img_wh)                                -> (psnr, ssim) of one image on the device
-  frame_images(results, pose, scale, num_classes, want, img_wh) -> {name: uint8 image} through ngp_frame_pack (I2)
+  frame_images(results, pose, scale, num_classes, want, img_wh) -> {name: uint8 image} through ngp_frame_pack (I2);
+                                                                   out_wh= brings a supersampled frame back to the
+                                                                   image size (ngp_resize_bicubic_u8, I3)
   evaluate_split(model, test_set, ...)                          -> {'psnr': [...], 'ssim': [...]} per held-out image
 """
 import torch
 
 from ._lib import call, check_input
 from .colormap import turbo_lut
-from .datasets.ray_utils import get_rays
+from .datasets.ray_utils import get_ray_directions, get_rays
+from .imaging import resize_u8
 from .metrics import psnr, ssim
 from .rendering import render_chunks
 
@@ -19,6 +24,7 @@ from .rendering import render_chunks
 FRAME_OUTPUTS = {"rgb": ("rgb", 3), "opacity": ("opacity", 1), "depth": ("depth", 3), "normal": ("normal_pred", 3),
                  "normal_raw": ("normal_raw", 3), "semantic": ("semantic", 3)}
 _LUTS = {}
+_FINE_DIRECTIONS = {}
 
 
 def colour_table(device):
@@ -38,9 +44,29 @@ def render_rays(model, rays_o, rays_d, chunk=131072, **render_kwargs):
     return render_chunks(model, rays_o.contiguous(), rays_d.contiguous(), chunk, **kwargs)
 
 
+def supersampled_directions(h, w, s, K, device):
+    """get_ray_directions of the int(h*s) x int(w*s) lattice of a camera with intrinsics K at (h, w), as the
+    reference's loaders build them for --anti_aliasing_factor (ray_utils.py:24-27); K itself is left alone.  Cached
+    per (h, w, s, K, device)."""
+    K = torch.as_tensor(K, dtype=torch.float32).cpu()
+    key = (int(h), int(w), float(s), tuple(K.reshape(-1).tolist()), torch.device(device))
+    if key not in _FINE_DIRECTIONS:
+        # a clone: get_ray_directions scales the matrix it is given in place
+        _FINE_DIRECTIONS[key] = get_ray_directions(h, w, K.clone(), device=device, anti_aliasing_factor=float(s))
+    return _FINE_DIRECTIONS[key]
+
+
 @torch.no_grad()
-def render_image(model, directions, pose, chunk=131072, **render_kwargs):
-    """One camera: render_rays of get_rays(directions, pose) (h*w rows)"""
+def render_image(model, directions, pose, chunk=131072, anti_aliasing_factor=1.0, K=None, img_wh=None,
+                 **render_kwargs):
+    """One camera: render_rays of get_rays(directions, pose) (h*w rows).  With anti_aliasing_factor s > 1 the rays
+    are those of the int(h*s) x int(w*s) lattice of the camera K at img_wh=(w, h) (`directions` is not used, so this
+    works for every loader): int(h*s) * int(w*s) rows, to be packed and brought back with frame_images(out_wh=)."""
+    if anti_aliasing_factor > 1.0:
+        if K is None or img_wh is None:
+            raise ValueError("anti_aliasing_factor > 1 needs the camera: K=(3, 3) intrinsics and img_wh=(w, h)")
+        w, h = img_wh
+        directions = supersampled_directions(h, w, anti_aliasing_factor, K, pose.device)
     rays_o, rays_d = get_rays(directions, pose)
     return render_rays(model, rays_o, rays_d, chunk, **render_kwargs)
 
@@ -84,14 +110,21 @@ def pack_frame(n, rgb=None, opacity=None, depth=None, depth_scale=1.0, normal_pr
 
 @torch.no_grad()
 def frame_images(results, pose, scale, num_classes=7, want=("rgb", "depth", "normal", "normal_raw", "semantic"),
-                 img_wh=None):
+                 img_wh=None, out_wh=None):
     """The 8-bit images of one frame, as the reference's render.py writes them, packed on the device in one launch:
     rgb, opacity, depth (Turbo of depth / (2 * scale)), normal / normal_raw (world -> camera through `pose`, then
     (c + 1) / 2), semantic (Turbo of label / (num_classes - 1)) -> {name: uint8 tensor}, (h*w[, 3]) rows, or
-    (H, W[, 3]) with img_wh=(W, H)."""
+    (H, W[, 3]) with img_wh=(W, H).  With out_wh=(w, h) other than img_wh (a supersampled frame) every image is
+    resized to (h, w[, 3]) as PIL's Image.resize(out_wh, BICUBIC) would, on the device (imaging.resize_u8); a label
+    image cannot be averaged, so `semantic` is refused then."""
     unknown = [w for w in want if w not in FRAME_OUTPUTS]
     if unknown:
         raise ValueError(f"unknown frame outputs {unknown}; known: {sorted(FRAME_OUTPUTS)}")
+    resize = out_wh is not None and (img_wh is None or tuple(out_wh) != tuple(img_wh))
+    if resize and img_wh is None:
+        raise ValueError("out_wh needs img_wh, the size the frame was rendered at")
+    if resize and "semantic" in want:
+        raise ValueError("a semantic image cannot be resampled: labels do not average")
     n = results["rgb"].shape[0]
     ins = {}
     for name in want:
@@ -106,6 +139,8 @@ def frame_images(results, pose, scale, num_classes=7, want=("rgb", "depth", "nor
     if img_wh is not None:
         w, h = img_wh
         out = {k: v.reshape((h, w) + tuple(v.shape[1:])) for k, v in out.items()}
+    if resize:
+        out = {k: resize_u8(v, out_wh) for k, v in out.items()}
     return out
 
 

@@ -2,13 +2,17 @@
 """Renders a frame series from a trained checkpoint (the reference's render.py:50-218): rgb / depth / normal /
 semantic frames as PNG files and the depth points as points.npy, along the test split's poses or the dataset's own
 camera path.  GPU only.  The 8-bit frames are packed on the device (ngp_frame_pack), so one byte per channel crosses to
-the host.  Prints one JSON line: frames, the seconds spent rendering, on the metrics, packing, copying device->host
-and encoding PNGs, and, when the split has ground truth, mean and per-image PSNR / SSIM.  No video is written: the frame directory is
-what a video encoder takes.
+the host.  Prints one JSON line: frames, the seconds spent rendering, on the metrics, packing, resizing, copying
+device->host and encoding PNGs, and, when the split has ground truth, mean and per-image PSNR / SSIM.  No video is written: the frame directory is
+what a video encoder takes.  --anti_aliasing_factor S renders int(H*S) x int(W*S) rays per frame, packs them to 8 bits
+and brings them back to W x H with Pillow's bicubic filter on the device (ngp_resize_bicubic_u8), as the reference's
+render.py:150-156 does on the host; PSNR / SSIM are then those of the anti-aliased 8-bit frame.
 
   python tools/render.py --ckpt ckpts/lego.ckpt --root_dir /data/nerf_synthetic/lego --out_dir frames --render_rgb
   python tools/render.py --ckpt ckpts/tnt.ckpt --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 \\
       --exp_step_factor 0.00390625 --render_traj --render_rgb --render_depth --render_normal --out_dir frames
+  python tools/render.py --ckpt ckpts/lego.ckpt --root_dir /data/nerf_synthetic/lego --out_dir frames --render_rgb \\
+      --anti_aliasing_factor 2
 """
 import argparse
 import json
@@ -43,7 +47,20 @@ def parse_args(argv=None):
     ap.add_argument("--render_points", action="store_true", help="render depth points (points.npy)")
     ap.add_argument("--render_traj", action="store_true",
                     help="follow the dataset's own camera path (render_traj_rays) instead of the test poses")
+    ap.add_argument("--anti_aliasing_factor", type=float, default=1.0,
+                    help="render rgb / depth / normal frames on an int(H*S) x int(W*S) lattice and resize the 8-bit "
+                         "frames back with Pillow's bicubic filter, on the device; 1 to 8")
+    ap.add_argument("--aa_host_check", action="store_true",
+                    help="with --anti_aliasing_factor and --render_rgb: also copy the fine 8-bit rgb frame to the host, "
+                         "resize it with Pillow, require equality with the device result and report host_route_s")
     args = ap.parse_args(argv)
+    if not 1.0 <= args.anti_aliasing_factor <= 8.0:
+        ap.error("--anti_aliasing_factor must lie in [1, 8]")
+    if args.anti_aliasing_factor > 1.0 and (args.render_semantic or args.render_points or args.render_traj):
+        ap.error("--anti_aliasing_factor does not go with --render_semantic (labels do not average), --render_points "
+                 "or --render_traj (the camera path's rays come from the loader at one ray per pixel)")
+    if args.aa_host_check and not (args.anti_aliasing_factor > 1.0 and args.render_rgb):
+        ap.error("--aa_host_check needs --anti_aliasing_factor above 1 and --render_rgb")
     if args.chunk_size <= 0:
         ap.error("--chunk_size must be positive")
     if not (args.render_rgb or args.render_depth or args.render_normal or args.render_semantic or args.render_points):
@@ -61,6 +78,7 @@ def main(argv=None):
     from ngp_amd import ckpt
     from ngp_amd.datasets import dataset_dict
     from ngp_amd.evaluation import frame_images, image_metrics, render_image, render_rays
+    from ngp_amd.imaging import resize_u8, supersampled_size
     from ngp_amd.networks import NGP
 
     if args.dataset_name not in dataset_dict:
@@ -85,8 +103,12 @@ def main(argv=None):
 
     want = [k for k, on in (("rgb", args.render_rgb), ("depth", args.render_depth), ("normal", args.render_normal),
                             ("normal_raw", args.render_normal), ("semantic", args.render_semantic)) if on]
+    aa = args.anti_aliasing_factor
+    fine_h, fine_w = supersampled_size(h, w, aa) if aa > 1.0 else (h, w)
+    packed = want if aa == 1.0 or not have_gt or "rgb" in want else want + ["rgb"]   # the metrics need the 8-bit rgb
     os.makedirs(args.out_dir, exist_ok=True)
-    t = {"render_s": 0.0, "metrics_s": 0.0, "pack_s": 0.0, "d2h_s": 0.0, "png_s": 0.0}
+    t = {"render_s": 0.0, "metrics_s": 0.0, "pack_s": 0.0, "resize_s": 0.0, "d2h_s": 0.0, "png_s": 0.0}
+    host_route_s = 0.0
     psnrs, ssims, points = [], [], []
     render_kwargs = {"exp_step_factor": args.exp_step_factor, "num_classes": args.num_classes}
 
@@ -100,16 +122,45 @@ def main(argv=None):
         if args.render_traj:
             rays = traj_rays[i][:, :6].to(dev)
             results = render_rays(model, rays[:, :3], rays[:, 3:6], args.chunk_size, **render_kwargs)
+        elif aa > 1.0:
+            results = render_image(model, None, poses[i], args.chunk_size, anti_aliasing_factor=aa, K=test_set.K,
+                                   img_wh=(w, h), **render_kwargs)
         else:
             results = render_image(model, directions, poses[i], args.chunk_size, **render_kwargs)
         t1 = tick()
+        t["render_s"] += t1 - t0
+        if aa == 1.0:
+            if have_gt:
+                p, q, _ = image_metrics(results["rgb"], gt, (w, h))
+            tm = tick()
+            images = frame_images(results, poses[i], args.scale, args.num_classes, want, img_wh=(w, h)) if want else {}
+            t2 = tick()
+            t["metrics_s"] += tm - t1
+            t["pack_s"] += t2 - tm
+        else:
+            # the fine frame is packed to 8 bits, then resized; the anti-aliased 8-bit frame is what is kept, so it is
+            # what PSNR / SSIM are taken on
+            fine = frame_images(results, poses[i], args.scale, args.num_classes, packed, img_wh=(fine_w, fine_h)) \
+                if packed else {}
+            tp = tick()
+            images = {k: resize_u8(v, (w, h)) for k, v in fine.items()}
+            tr = tick()
+            if have_gt:
+                p, q, _ = image_metrics(images["rgb"].reshape(h * w, 3).float() / 255, gt, (w, h))
+            t2 = tick()
+            t["pack_s"] += tp - t1
+            t["resize_s"] += tr - tp
+            t["metrics_s"] += t2 - tr
+            if args.aa_host_check:           # the route the device resize replaces: the fine frame to the host, Pillow
+                host = np.asarray(Image.fromarray(fine["rgb"].cpu().numpy()).resize((w, h), Image.Resampling.BICUBIC))
+                host_route_s += time.perf_counter() - t2
+                if not np.array_equal(host, images["rgb"].cpu().numpy()):
+                    raise SystemExit(f"--aa_host_check: frame {i}: the device resize differs from Pillow's")
+                t2 = tick()
+            images = {k: v for k, v in images.items() if k in want}
         if have_gt:
-            p, q, _ = image_metrics(results["rgb"], gt, (w, h))
             psnrs.append(p)
             ssims.append(q)
-        tm = tick()
-        images = frame_images(results, poses[i], args.scale, args.num_classes, want, img_wh=(w, h)) if want else {}
-        t2 = tick()
         images = {k: v.cpu().numpy() for k, v in images.items()}
         if args.render_points:
             points.append(results["points"].reshape(h, w, 3).cpu().numpy())
@@ -117,12 +168,18 @@ def main(argv=None):
         for k, img in images.items():
             Image.fromarray(img).save(os.path.join(args.out_dir, f"{i:03d}-{FILES[k]}.png"))
         t4 = time.perf_counter()
-        for key, dt in zip(t, (t1 - t0, tm - t1, t2 - tm, t3 - t2, t4 - t3)):
-            t[key] += dt
+        t["d2h_s"] += t3 - t2
+        t["png_s"] += t4 - t3
     if args.render_points:
         np.save(os.path.join(args.out_dir, "points.npy"), np.stack(points).astype(np.float32))
     line = {"frames": len(poses), "img_wh": [w, h], "outputs": want + (["points"] if args.render_points else []),
             **{k: round(v, 4) for k, v in t.items()}}
+    if aa > 1.0:
+        line.update(anti_aliasing_factor=aa, supersampled_wh=[fine_w, fine_h])
+        if have_gt:
+            line["metrics_on"] = "antialiased_u8"
+        if args.aa_host_check:
+            line["host_route_s"] = round(host_route_s, 4)
     if have_gt and psnrs:
         p, s = torch.stack(psnrs).tolist(), torch.stack(ssims).tolist()
         line.update(psnr_mean=sum(p) / len(p), psnr=p, ssim_mean=sum(s) / len(s), ssim=s)
