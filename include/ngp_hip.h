@@ -258,6 +258,20 @@ int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* d
                           float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
                           float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                           float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, void* stream);
+/* The same launch for NeRFLoss(embed_msk=True) (losses.py:85-93, 142-151): mask (n_rays) is the transient mask m of
+ * every ray.  Colour term mean((1 - m) e^2), its seed 2 (1 - m) e / (3 R) (the background's share of d_opacity uses it),
+ * terms (5) = [loss, rgb, opacity, distortion, r_ms] with r_ms = size_delta mean(m^2) (the digit term has weight 0 in the
+ * reference and is not formed), dL_dmask[r] = 2 size_delta m / R - sum_c e_rc^2 / (3 R).  Every rendered output,
+ * `rgb` included, is that of ngp_render_loss_fused; with m = 0 and size_delta = 0 so is every other output, bit for bit.
+ * vr_samples may sit at terms + 6 floats (one fill). */
+int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                                 const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                                 const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                                 const float* target_rgb, const float* rgb_bg, const float* mask, float size_delta,
+                                 float T_threshold, int classes, int n_rays, float lambda_opacity, float lambda_distortion,
+                                 int64_t* total_samples, int64_t* vr_samples, float* opacity, float* depth, float* rgb,
+                                 float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
+                                 float* dL_dsigmas, float* dL_drgbs, float* dL_dmask, void* stream);
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,
                        float* normals_diff, float* normals_ori, void* stream);
 int ngp_neg_normalize(const float* x, int64_t ldx, const float* scale3 /* device (3) or NULL */, int64_t n,
@@ -331,6 +345,20 @@ int ngp_density_field_fwd(const ngp_grid_desc* desc, const float* table, const f
 int ngp_grid_bwd_bwd_input(const ngp_grid_desc* desc, const float* table, const float* x,
                            const float* dL_dy, int64_t lddy, const float* dL_ddLdx, int64_t n,
                            float* dtable, float* dL_ddLdy, void* stream);
+
+/* ------------------------------------------------------------------------
+ * M1  transient mask field (models/implicit_mask.py): tcnn Grid/Hash encoding L = 8, F = 2 (desc must say so) of
+ * uvi (n,3), then Linear(16,64) + ReLU + Linear(64,1) + Sigmoid with torch's nn.Linear layouts: W1 (64,16), b1 (64),
+ * W2 (1,64), b2 (1).  One launch each way.
+ * fwd: mask (n).  bwd: from dL_dmask (n) and the forward's mask (the table is gathered again, nothing else is saved)
+ * it ACCUMULATES (+=, the caller zeroes) dtable (like ngp_grid_bwd_param: float atomics), dW1, db1, dW2, db2; the
+ * weight sums are reduced inside a workgroup and added once per workgroup per element.
+ * ---------------------------------------------------------------------- */
+int ngp_mask_field_fwd(const ngp_grid_desc* desc, const float* table, const float* W1, const float* b1, const float* W2,
+                       const float* b2, const float* uvi, int64_t n, float* mask, void* stream);
+int ngp_mask_field_bwd(const ngp_grid_desc* desc, const float* table, const float* W1, const float* b1, const float* W2,
+                       const float* uvi, const float* mask, const float* dL_dmask, int64_t n, float* dtable, float* dW1,
+                       float* db1, float* dW2, float* db2, void* stream);
 
 /* ------------------------------------------------------------------------
  * H5  spherical harmonics (tcnn.Encoding otype SphericalHarmonics, degree 1..4,

@@ -8,6 +8,7 @@ Sub-modules (same names / call signatures as zhihao-lin/instant-ngp-pp):
   rendering         — render(model, rays_o, rays_d, **kwargs)
   networks          — NGP
   losses            — NeRFLoss, DistortionLoss
+  implicit_mask     — implicit_mask, the transient mask field of the embed_msk recipe (models/implicit_mask.py)
   trainer           — the training schedule of train.py (no Lightning)
   mesh              — marching cubes + PLY export (extract_mesh.py)
   metrics           — psnr, ssim
@@ -18,7 +19,7 @@ Every compute call goes through libngp_hip.so (include/ngp_hip.h); there is no C
 from . import _lib  # noqa: F401  (parses the header; the .so is loaded on first use)
 
 __all__ = ["vren", "tinycudann", "torch_scatter", "custom_functions", "rendering", "networks", "losses",
-           "metrics", "trainer", "synthetic", "ckpt", "mesh", "evaluation", "colormap",
+           "metrics", "trainer", "synthetic", "ckpt", "mesh", "evaluation", "colormap", "implicit_mask",
            "install_as_reference_modules"]
 
 

@@ -39,9 +39,12 @@ def load_ckpt(model, ckpt_path, model_name='model', prefixes_to_ignore=()):
             own[k].copy_(v.to(own[k].device))
 
 
-def save_ckpt(model, path, extra=None):
-    """writes {'state_dict': {'model.<key>': ...}} like Lightning's ModelCheckpoint(save_weights_only)"""
+def save_ckpt(model, path, extra=None, msk_model=None):
+    """writes {'state_dict': {'model.<key>': ...}} like Lightning's ModelCheckpoint(save_weights_only); the transient
+    mask model of the embed_msk recipe goes beside it under 'msk_model.<key>' (train.py:112-113, 236)"""
     sd = {f"model.{k}": v.detach().cpu() for k, v in model.state_dict().items()}
+    if msk_model is not None:
+        sd.update({f"msk_model.{k}": v.detach().cpu() for k, v in msk_model.state_dict().items()})
     if extra:
         sd.update(extra)
     torch.save({'state_dict': sd}, path)

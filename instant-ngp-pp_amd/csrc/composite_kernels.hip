@@ -575,17 +575,25 @@ struct RenderLossArgs {
     int classes, n_rays;
     int64_t *total_samples, *vr_samples;
     float *opacity, *depth, *rgb, *normal, *sem, *ws, *Ro, *Rp, *terms, *d_sigmas, *d_rgbs;
+    // MASKED only (NeRFLoss(embed_msk=True), losses.py:85-93): the transient mask of every ray, g_ms = size_delta / R,
+    // and the loss's gradient w.r.t. the mask
+    const float* mask;
+    float g_ms;
+    float* d_mask;
 };
 
-template <int CMAX, int W>
+// MASKED: the colour term is mean (1 - m) e^2 (its seed, and through it the background's share of d_opacity, carry the
+// factor 1 - m), terms[4] = size_delta mean m^2, d_mask = 2 size_delta m / R - sum_c e_c^2 / (3 R); the rendered outputs
+// are those of the unmasked kernel.  With m = 0 and size_delta = 0 every product below is by 1.0 and every sum with 0.0.
+template <int CMAX, int W, bool MASKED>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
     constexpr int RPB = 256 / W;          // rays per block
-    __shared__ float part[3][RPB];
+    __shared__ float part[MASKED ? 4 : 3][RPB];
     __shared__ unsigned long long part_n[RPB];
     Seg sg; int lane;
     const bool have = seg_load_w<W>(p.rays_a, p.n_rays, sg, lane);
-    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f;
+    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f;
     unsigned long long n_used = 0;
     if (have) {
         const size_t r = (size_t)sg.ray;
@@ -677,7 +685,12 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             fR = aR + bg0 * rest; fG = aG + bg1 * rest; fB = aB + bg2 * rest;
         }
         const float e0 = fR - p.gt[3 * r], e1 = fG - p.gt[3 * r + 1], e2 = fB - p.gt[3 * r + 2];
-        const float gR = p.g_rgb * 2.0f * e0, gG = p.g_rgb * 2.0f * e1, gB = p.g_rgb * 2.0f * e2;
+        float gR = p.g_rgb * 2.0f * e0, gG = p.g_rgb * 2.0f * e1, gB = p.g_rgb * 2.0f * e2;
+        float mk = 0.0f, keep = 1.0f;
+        if (MASKED) {
+            mk = p.mask[r]; keep = 1.0f - mk;
+            gR *= keep; gG *= keep; gB *= keep;
+        }
         const float oo = aO + 1e-10f;
         const float lgo = logf(oo);
         // d loss / d opacity: the entropy term, and through the background's weight (1 - opacity)
@@ -693,6 +706,11 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             for (int cc = 0; cc < CMAX; cc++)
                 if (cc < p.classes) p.sem[r * p.classes + cc] = aS[cc];
             s_rgb = e0 * e0 + e1 * e1 + e2 * e2; s_op = -oo * lgo; s_dist = dacc;
+            if (MASKED) {
+                p.d_mask[r] = 2.0f * p.g_ms * mk - p.g_rgb * s_rgb;
+                s_rgb *= keep;
+                s_ms = mk * mk;
+            }
             n_used = (unsigned long long)(stop >= 0 ? stop : sg.n);
         }
         const float w_sum = w_run, wt_sum = wt_run;
@@ -755,14 +773,23 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
     }
     // ---------------- loss terms of the block's rays: one set of atomics per block
     const int hw = threadIdx.x / W;
-    if ((threadIdx.x & (W - 1)) == 0) { part[0][hw] = s_rgb; part[1][hw] = s_op; part[2][hw] = s_dist; part_n[hw] = n_used; }
+    if ((threadIdx.x & (W - 1)) == 0) {
+        part[0][hw] = s_rgb; part[1][hw] = s_op; part[2][hw] = s_dist; part_n[hw] = n_used;
+        if (MASKED) part[3][hw] = s_ms;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float t0 = 0, t1 = 0, t2 = 0;
+        float t0 = 0, t1 = 0, t2 = 0, t3 = 0;
         unsigned long long tn = 0;
         for (int q = 0; q < RPB; q++) { t0 += part[0][q]; t1 += part[1][q]; t2 += part[2][q]; tn += part_n[q]; }
         t0 *= p.g_rgb; t1 *= p.g_op; t2 *= p.g_dist;
-        atomicAdd(p.terms, t0 + t1 + t2);
+        if (MASKED) {
+            for (int q = 0; q < RPB; q++) t3 += part[3][q];
+            t3 *= p.g_ms;
+            atomicAdd(p.terms, (t0 + t1 + t2) + t3);
+            atomicAdd(p.terms + 4, t3);
+        } else
+            atomicAdd(p.terms, t0 + t1 + t2);
         atomicAdd(p.terms + 1, t0);
         atomicAdd(p.terms + 2, t1);
         atomicAdd(p.terms + 3, t2);
@@ -974,23 +1001,27 @@ int ngp_nerf_loss(const float* rgb, const float* target_rgb, const float* opacit
     return ngp_check_launch();
 }
 
-int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
-                          const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
-                          const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
-                          const float* target_rgb, const float* rgb_bg, float T_threshold, int classes, int n_rays, float lambda_opacity,
-                          float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
-                          float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
-                          float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, void* stream)
+// shared body of ngp_render_loss_fused / ngp_render_loss_fused_masked (mask == NULL: the unmasked kernel, 4 terms)
+static int render_loss_fused_launch(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                                    const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                                    const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                                    const float* target_rgb, const float* rgb_bg, const float* mask, float size_delta,
+                                    float T_threshold, int classes, int n_rays, float lambda_opacity,
+                                    float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
+                                    float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
+                                    float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, float* dL_dmask,
+                                    void* stream)
 {
     if (n_rays < 0 || classes < 0 || classes > 8 || ld_normal < 3 || ld_sem < classes) return NGP_EINVAL;
     if (n_rays == 0) return NGP_OK;
     if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
         (classes && !sem) || !loss_o || !loss_p || !terms) return NGP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (reinterpret_cast<char*>(vr_samples) == reinterpret_cast<char*>(terms) + 4 * sizeof(float)) {   // adjacent: one fill
-        if (hipMemsetAsync(terms, 0, 4 * sizeof(float) + sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+    const size_t n_terms = mask ? 5 : 4, gap = mask ? 6 : 4;   // (an int64 behind 5 floats sits at float 6)
+    if (reinterpret_cast<char*>(vr_samples) == reinterpret_cast<char*>(terms) + gap * sizeof(float)) {   // adjacent: one fill
+        if (hipMemsetAsync(terms, 0, gap * sizeof(float) + sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
     } else {
-        if (hipMemsetAsync(terms, 0, 4 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(terms, 0, n_terms * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
         if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
     }
     RenderLossArgs a;
@@ -1001,10 +1032,44 @@ int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* d
     a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
     a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
     a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
+    a.mask = mask; a.g_ms = size_delta / n_rays; a.d_mask = dL_dmask;
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
-    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32>), seg_grid(n_rays), dim3(256), 0, st, a);
+    if (mask)
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
+}
+
+int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                          const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                          const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                          const float* target_rgb, const float* rgb_bg, float T_threshold, int classes, int n_rays, float lambda_opacity,
+                          float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
+                          float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
+                          float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, void* stream)
+{
+    return render_loss_fused_launch(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas,
+                                    ts, rays_a, target_rgb, rgb_bg, nullptr, 0.0f, T_threshold, classes, n_rays,
+                                    lambda_opacity, lambda_distortion, total_samples, vr_samples, opacity, depth, rgb,
+                                    normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs, nullptr, stream);
+}
+
+int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                                 const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                                 const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                                 const float* target_rgb, const float* rgb_bg, const float* mask, float size_delta,
+                                 float T_threshold, int classes, int n_rays, float lambda_opacity, float lambda_distortion,
+                                 int64_t* total_samples, int64_t* vr_samples, float* opacity, float* depth, float* rgb,
+                                 float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
+                                 float* dL_dsigmas, float* dL_drgbs, float* dL_dmask, void* stream)
+{
+    if (n_rays > 0 && (!mask || !dL_dmask)) return NGP_EINVAL;
+    return render_loss_fused_launch(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas,
+                                    ts, rays_a, target_rgb, rgb_bg, mask, size_delta, T_threshold, classes, n_rays,
+                                    lambda_opacity, lambda_distortion, total_samples, vr_samples, opacity, depth, rgb,
+                                    normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs, dL_dmask, stream);
 }
 
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,

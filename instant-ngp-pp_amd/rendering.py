@@ -379,15 +379,57 @@ class _RenderLossFn(torch.autograd.Function):
         return (d_sig, d_rgb) + (None,) * 14
 
 
+class _RenderLossMaskedFn(torch.autograd.Function):
+    """_RenderLossFn for NeRFLoss(embed_msk=True) (ngp_render_loss_fused_masked): `mask` (n_rays) or (n_rays, 1) is a
+    further differentiable input — its gradient is computed by the same launch and handed back by backward — and
+    terms (5) = [loss, rgb, opacity, distortion, r_ms]."""
+
+    @staticmethod
+    def forward(ctx, sig, rgb_o, mask, dsig_dx, np_raw, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, scale3, T_thr, classes,
+                lambda_opa, lambda_dist, size_delta, rgb_bg=None):
+        n, nr = sig.shape[0], rays_a.shape[0]
+        dev = sig.device
+        f32 = torch.float32
+        if mask.numel() != nr:
+            raise ValueError(f"mask has {mask.numel()} entries for {nr} rays")
+        total = torch.empty(nr, dtype=torch.int64, device=dev)
+        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
+        ws, d_sig, d_rgb, d_mask = E(n), E(n), E(n, 3), E(nr)
+        acc = E(8)                                   # [terms (5) | - | vr_samples (int64)]: cleared by one memset
+        terms, vr = acc[:5], acc[6:8].view(torch.int64)
+        call("render_loss_fused_masked", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits,
+             sem_logits.stride(0), dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, mask.contiguous(), float(size_delta), float(T_thr),
+             int(classes), nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp,
+             terms, d_sig, d_rgb, d_mask)
+        ctx.save_for_backward(d_sig, d_rgb, d_mask)
+        ctx.mask_shape = mask.shape
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
+        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
+
+    @staticmethod
+    def backward(ctx, g_terms, *_unused):
+        d_sig, d_rgb, d_mask = ctx.saved_tensors
+        return (d_sig, d_rgb, d_mask.view(ctx.mask_shape)) + (None,) * 15
+
+
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
+    """fused = (rgb_gt, lambda_opa, lambda_distortion) or, for the embed_msk recipe, those three followed by
+    (mask (n_rays[, 1]), size_delta)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
-    rgb_gt, lambda_opa, lambda_dist = fused
+    rgb_gt, lambda_opa, lambda_dist = fused[:3]
     rgb_bg = None
     if kwargs.get('exp_step_factor', 0.) != 0 and kwargs.get('random_bg', False):
         rgb_bg = torch.rand(3, device=xyzs.device)      # rendering.py:239 (drawn at the same place in the RNG stream)
-    (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossFn.apply(
-        sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-        rgb_gt.contiguous(), model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, rgb_bg)
+    if len(fused) == 5:
+        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossMaskedFn.apply(
+            sig, rgb_o, fused[3], dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
+            rgb_gt.contiguous(), model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[4], rgb_bg)
+    else:
+        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossFn.apply(
+            sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
+            rgb_gt.contiguous(), model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, rgb_bg)
     results['sigma'] = sig
     results['xyzs'] = xyzs
     results['vr_samples'] = vr[0]

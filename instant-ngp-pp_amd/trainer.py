@@ -155,8 +155,11 @@ def shard_seed(base_seed, rank):
 class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
-                 force_sharded=None, loss_kwargs=None):
-        """loss_kwargs: the flags train.py:289-300 hands to NeRFLoss (normal_ref, normal_mono, semantic,
+                 force_sharded=None, loss_kwargs=None, msk_model=None):
+        """msk_model: an implicit_mask (the reference's embed_msk recipe, train.py:112-113, 280-299).  Its parameters join
+        the flat store behind the model's as 'msk_model.<key>' (one Adam, one schedule, one clip: the reference keeps it in
+        net_opt), step() then needs uvi=, and the step stays on the fused render + loss tail and on the norm-bound clip.
+        loss_kwargs: the flags train.py:289-300 hands to NeRFLoss (normal_ref, normal_mono, semantic,
         depth_mono, embed_msk, scale, ...).  Any optional term switches the fused default-recipe loss off;
         normal_ref also switches the field to differentiable normals (the Ro term must reach the density
         table through normals_raw, reference networks.py:186-196).
@@ -164,6 +167,7 @@ class NGPTrainer:
         even with ONE rank in the process group, so that a single-GPU box can rehearse every RCCL call of
         the N>1 path; None reads the environment variable NGP_FORCE_SHARDED."""
         self.model = model
+        self.msk_model = msk_model
         self.force_sharded = bool(os.environ.get("NGP_FORCE_SHARDED")) if force_sharded is None else bool(force_sharded)
         self.base_lr = lr
         self.num_epochs = num_epochs
@@ -214,6 +218,8 @@ class NGPTrainer:
         named = [(n, p) for n, p in self.model.named_parameters() if p.numel() > 0]
         order = {"rgb_encoder.params": 0, "xyz_encoder.params": 1}
         named.sort(key=lambda np_: order.get(np_[0], 2))
+        if self.msk_model is not None:   # behind the model's: in the tail whose squares are always summed exactly (_mlp_lo)
+            named += [("msk_model." + n, p) for n, p in self.msk_model.named_parameters()]
         self.names = [n for n, _ in named]
         world = dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
         quantum = 4 * world   # every slice 16-byte aligned; every bucket divisible by the world size
@@ -266,6 +272,10 @@ class NGPTrainer:
             m._grad_sinks = {"W1": lin1.weight.grad, "b1": lin1.bias.grad, "W2": lin2.weight.grad, "b2": lin2.bias.grad,
                              "rgb_p": m.rgb_net.params.grad, "nrm_p": m.norm_pred_header.params.grad,
                              "sem_p": m.semantic_header.params.grad}
+        if self.msk_model is not None:   # implicit_mask._MaskFieldFn.backward adds into these
+            k = self.msk_model
+            k._grad_sinks = {"table": k.mask_encoder.params.grad, "W1": k.mask_net[0].weight.grad, "b1": k.mask_net[0].bias.grad,
+                             "W2": k.mask_net[2].weight.grad, "b2": k.mask_net[2].bias.grad}
         # scatter kernels accumulate directly into the flat gradient (see tinycudann._GridFwd)
         for enc_name in ("rgb_encoder", "xyz_encoder"):
             enc = getattr(self.model, enc_name, None)
@@ -292,8 +302,8 @@ class NGPTrainer:
 
     def _unit_seed(self, terms):
         s = getattr(self, '_seed4', None)
-        if s is None or s.device != terms.device:
-            s = self._seed4 = torch.tensor([1.0, 0.0, 0.0, 0.0], device=terms.device)
+        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model)
+            s = self._seed4 = torch.tensor([1.0] + [0.0] * (terms.numel() - 1), device=terms.device)
         return s
 
     def _early_norm_share(self):
@@ -312,8 +322,10 @@ class NGPTrainer:
     def lr(self):
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
-    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, **loss_kwargs):
+    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
+
+        uvi: (n_rays, 3) input of the trainer's msk_model (implicit_mask.uvi), required when there is one.
 
         target: further per-ray supervision for NeRFLoss's optional terms ('normal', 'label', 'depth': the
         batch dictionary of train.py:299); loss_kwargs: per-step additions to the trainer's loss_kwargs
@@ -324,6 +336,9 @@ class NGPTrainer:
         side stream under this step's backward and the next call picks the result up, provided it
         is called with the very same tensors and no density-grid update lies in between."""
         model = self.model
+        masked = self.msk_model is not None
+        if masked and uvi is None:
+            raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
         self._join_grad_zeroing()
         if self.global_step % self.update_interval == 0:
             model.update_density_grid(self.density_threshold * MAX_SAMPLES / 3 ** 0.5,
@@ -346,9 +361,17 @@ class NGPTrainer:
             marched = ahead.take(rays_o, rays_d, self.exp_step_factor)
         default_recipe = bool(self.fused_loss and not loss_kwargs and not target)
         extra = {}
+        mask = None
+        if masked:
+            ev = getattr(model, "_params_ready", None)   # the mask parameters sit in the Adam sweep's first piece
+            if ev is not None:
+                ev.wait()                                # (left in place: the field waits for it as well)
+            mask = self.msk_model(uvi)
         if default_recipe and rays_o.is_cuda:
             # render + loss + the loss's gradients as one launch behind the field (rendering._RenderLossFn)
             extra['_fused_loss'] = (rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion)
+            if masked:   # size_delta of the step being taken (losses.py:60-69, 85)
+                extra['_fused_loss'] += (mask, self.loss_fn.Annealing.getWeight(self.global_step))
         results = render(model, rays_o, rays_d, exp_step_factor=self.exp_step_factor,
                          num_classes=self.num_classes, marched=marched, **self.render_kwargs, **extra)
         if launch_next_late:
@@ -366,7 +389,7 @@ class NGPTrainer:
             terms = results.pop('_loss_terms')
             loss = terms[0]
             torch.autograd.backward([terms], [self._unit_seed(terms)])
-        elif self.fused_loss and not loss_kwargs and not target:
+        elif self.fused_loss and not loss_kwargs and not target and not masked:
             # same value and gradients as sum(term.mean()) over NeRFLoss's default terms; the
             # gradients are seeded directly (no loss node, no multiplications by 1)
             terms, (d_rgb, d_op, d_ws) = nerf_loss_and_grads(
@@ -383,6 +406,8 @@ class NGPTrainer:
             batch.update(target or {})
             kw = dict(self.loss_kwargs)
             kw.update(loss_kwargs)
+            if masked:
+                kw.update(embed_msk=True, mask=mask, step=self.global_step)
             loss_d = self.loss_fn(results, batch, **kw)
             loss = sum(lo.mean() for lo in loss_d.values())
             loss.backward()

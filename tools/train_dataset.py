@@ -6,6 +6,8 @@ reference: train.py:82-392).  GPU only.
   python tools/train_dataset.py --root_dir /data/nerf_synthetic/lego --num_epochs 20
   python tools/train_dataset.py --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 --exp_step_factor 0.00390625
   python tools/train_dataset.py --make_proxy /tmp/proxy --downsample 0.25 --num_epochs 2   # no dataset at hand
+  python tools/train_dataset.py --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 --exp_step_factor 0.00390625 \
+      --random_bg --embed_msk --save_dir out --ckpt_path out/playground.ckpt   # transient mask: out/mask_NNN.png per image
 """
 import argparse
 import json
@@ -20,6 +22,7 @@ import ngp_amd  # noqa: F401
 from ngp_amd import ckpt
 from ngp_amd.datasets import dataset_dict, write_synthetic_dataset
 from ngp_amd.evaluation import evaluate_split
+from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
 from ngp_amd.trainer import NGPTrainer
@@ -35,16 +38,21 @@ def build_model(scale, device):
 
 
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
-          render_kwargs=None):
-    """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead"""
+          render_kwargs=None, msk_model=None):
+    """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
+    mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices"""
     train_set.batch_size = batch_size
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
-                         exp_step_factor=exp_step_factor, render_kwargs=render_kwargs)
+                         exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model)
+    n_imgs = len(train_set.poses)
 
     def next_batch():
         s = train_set[0]
         o, d = train_set.batch_rays(s)
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous()
+        uvi = None
+        if msk_model is not None:
+            uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(o.device)
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi
 
     import gc
     gc.collect()
@@ -54,7 +62,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     t0 = time.perf_counter()
     for i in range(total):
         nxt = next_batch() if i + 1 < total else None
-        loss, res = trainer.step(*cur, next_rays=None if nxt is None else nxt[:2])
+        loss, res = trainer.step(*cur[:3], next_rays=None if nxt is None else nxt[:2], uvi=cur[3])
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
             print(json.dumps({"step": i + 1, "loss": float(loss), "train_psnr": float(psnr(res["rgb"].detach(), cur[2])),
@@ -76,6 +84,29 @@ def _save_rgb(save_dir, img_wh):
     return save
 
 
+@torch.no_grad()
+def mask_images(msk_model, img_wh, n_imgs, device, save_dir=None, chunk=131072):
+    """the mask field over every pixel of every training image, in chunks -> mean mask of each image; with save_dir
+    also <save_dir>/mask_NNN.png = (uint8)(clip(mask, 0, 1) * 255), so that one can see what was masked"""
+    w, h = img_wh
+    pix = torch.arange(w * h, device=device)
+    uv = torch.stack([pix // w, pix % w], -1)
+    means = []
+    for i in range(n_imgs):
+        parts = []
+        for a in range(0, w * h, chunk):
+            idx = torch.full((min(chunk, w * h - a),), i, device=device)
+            parts.append(msk_model(implicit_mask.uvi(uv[a:a + chunk], idx, img_wh, n_imgs))[:, 0])
+        m = torch.cat(parts)
+        means.append(float(m.mean()))
+        if save_dir:
+            from PIL import Image
+            os.makedirs(save_dir, exist_ok=True)
+            Image.fromarray((m.clamp(0, 1) * 255).to(torch.uint8).reshape(h, w).cpu().numpy()).save(
+                os.path.join(save_dir, f"mask_{i:03d}.png"))
+    return means
+
+
 def evaluate(model, test_set, chunk=131072, save_dir=None, exp_step_factor=0.0):
     """per-image PSNR of the test split through render(test_time=True) (train.py:347-392)"""
     return evaluate_split(model, test_set, chunk, on_image=_save_rgb(save_dir, test_set.img_wh) if save_dir else None,
@@ -91,6 +122,8 @@ def main():
     ap.add_argument("--scale", type=float, default=0.5)
     ap.add_argument("--exp_step_factor", type=float, default=0.0, help="1/256 for unbounded scenes (opt.py)")
     ap.add_argument("--random_bg", action="store_true")
+    ap.add_argument("--embed_msk", action="store_true",
+                    help="train the transient mask field beside the scene (the reference's --embed_msk)")
     ap.add_argument("--batch_size", type=int, default=8192)
     ap.add_argument("--num_epochs", type=int, default=20)
     ap.add_argument("--steps_per_epoch", type=int, default=1000)
@@ -110,19 +143,25 @@ def main():
     train_set = loader(root, "train", args.downsample, device=dev)
     test_set = loader(root, "test", args.downsample, device=dev)
     model = build_model(args.scale, dev)
+    msk_model = implicit_mask().to(dev) if args.embed_msk else None
     t0 = time.perf_counter()
     train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
-          exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None)
+          exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
+          msk_model=msk_model)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     res = evaluate_split(model, test_set, on_image=_save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None,
                          exp_step_factor=args.exp_step_factor)
     psnrs, ssims = res["psnr"], res["ssim"]
     if args.ckpt_path:
-        ckpt.save_ckpt(model, args.ckpt_path)
-    print(json.dumps({"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
-                      "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
-                      "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}))
+        ckpt.save_ckpt(model, args.ckpt_path, msk_model=msk_model)
+    out = {"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
+           "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
+           "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}
+    if msk_model is not None:
+        means = mask_images(msk_model, train_set.img_wh, len(train_set.poses), dev, save_dir=args.save_dir)
+        out["mask_mean"] = sum(means) / len(means)
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
