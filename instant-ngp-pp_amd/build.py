@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libngp_hip.so")
 LIB_ID = LIB + ".id"
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mlp_act.h"), os.path.join(HERE, "..", "include", "ngp_hip.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "grid_index.h", "mlp_act.h", "mlp_tile.h")] + \
+          [os.path.join(HERE, "..", "include", "ngp_hip.h")]
 
 # (source, extra flags).  ray_kernels.hip is compiled without FMA contraction so that the
 # marcher / intersector are bit-identical to the CPU oracle (see the file header); mesh_kernels.hip likewise.

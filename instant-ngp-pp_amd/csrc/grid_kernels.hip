@@ -14,61 +14,11 @@
 //     Lanes whose upstream gradient is exactly zero (samples behind the early-termination
 //     point, volumerendering.cu:111) issue no atomics.
 #include "common.h"
+#include "grid_index.h"
 #include "mlp_act.h"
+#include "mlp_tile.h"
 
 namespace {
-
-struct GridMeta {
-    uint32_t n_levels, n_features;
-    uint32_t offset[NGP_MAX_LEVELS];
-    uint32_t size[NGP_MAX_LEVELS];   // rows in the level
-    uint32_t res[NGP_MAX_LEVELS];
-    uint32_t flags[NGP_MAX_LEVELS];  // bit0: hashed, bit1: size is a power of two
-    float scale[NGP_MAX_LEVELS];
-};
-
-struct LevelInfo {
-    uint32_t offset, size, res, flags;
-    float scale;
-};
-
-__device__ __forceinline__ LevelInfo level_info(const GridMeta& m, uint32_t l)
-{
-    LevelInfo li;
-    li.offset = m.offset[l]; li.size = m.size[l]; li.res = m.res[l]; li.flags = m.flags[l]; li.scale = m.scale[l];
-    return li;
-}
-
-__device__ __forceinline__ uint32_t row_index(const LevelInfo& li, uint32_t x, uint32_t y, uint32_t z)
-{
-    uint32_t idx;
-    if (li.flags & 1u) {
-        idx = x ^ (y * 2654435761u) ^ (z * 805459861u);
-        idx = (li.flags & 2u) ? (idx & (li.size - 1u)) : (idx % li.size);
-    } else {
-        idx = x + y * li.res + z * li.res * li.res;
-        if (idx >= li.size) idx %= li.size;
-    }
-    return li.offset + idx;
-}
-
-struct Cell {
-    uint32_t g[3];
-    float w[3];
-};
-
-__device__ __forceinline__ Cell cell_of(const float* __restrict__ x, int64_t sample, float scale)
-{
-    Cell c;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float p = fmaf(scale, x[3 * sample + k], 0.5f);
-        const float fl = floorf(p);
-        c.g[k] = (uint32_t)(int)fl;
-        c.w[k] = p - fl;
-    }
-    return c;
-}
 
 template <int V> struct VecT;
 template <> struct VecT<1> { typedef float T; };
@@ -120,9 +70,8 @@ __global__ void __launch_bounds__(256) grid_fwd_kernel(GridMeta meta, const floa
     float wts[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const uint32_t cx = k & 1, cy = (k >> 1) & 1, cz = (k >> 2) & 1;
-        rows[k] = row_index(li, c.g[0] + cx, c.g[1] + cy, c.g[2] + cz);
-        wts[k] = (cx ? c.w[0] : 1 - c.w[0]) * (cy ? c.w[1] : 1 - c.w[1]) * (cz ? c.w[2] : 1 - c.w[2]);
+        rows[k] = corner_row(li, c, k);
+        wts[k] = corner_weight(c.w[0], c.w[1], c.w[2], k);
     }
     vec_t vals[8];
 #pragma unroll
@@ -242,10 +191,37 @@ __device__ __forceinline__ void corners(const LevelInfo& li, const float* __rest
         }
     }
 }
+
+// trilinear blend of the eight corner pieces
+__device__ __forceinline__ void blend(float (&acc)[4], const Lead& c, const float4 (&R)[8])
+{
+#pragma unroll
+    for (int k = 0; k < 8; k++) vec_fma<4>(acc, corner_weight(c.w0, c.w1, c.w2, k), R[k]);
+}
+
+// one level's share of the input gradient: the lane's half row of the upstream gradient (gp, in the staging tile) against
+// the corner pieces of its cell, added to (gx, gy, gz)
+__device__ __forceinline__ void level_grad(const LevelInfo& li, const float* __restrict__ table, float px, float py, float pz,
+                                           int lane, int half, const float* gp, float& gx, float& gy, float& gz)
+{
+    const Lead c = phase1(li.scale, px, py, pz, lane);
+    float4 v[8];
+    corners(li, table, c, half, v);
+    const float4 go = *reinterpret_cast<const float4*>(gp);
+    const float g4[4] = {go.x, go.y, go.z, go.w};
+    const float wx0 = 1 - c.w0, wx1 = c.w0, wy0 = 1 - c.w1, wy1 = c.w1, wz0 = 1 - c.w2, wz1 = c.w2;
+    const float dx = wy0 * wz0 * vec_dot<4>(g4, v[1], v[0]) + wy1 * wz0 * vec_dot<4>(g4, v[3], v[2]) +
+                     wy0 * wz1 * vec_dot<4>(g4, v[5], v[4]) + wy1 * wz1 * vec_dot<4>(g4, v[7], v[6]);
+    const float dy = wx0 * wz0 * vec_dot<4>(g4, v[2], v[0]) + wx1 * wz0 * vec_dot<4>(g4, v[3], v[1]) +
+                     wx0 * wz1 * vec_dot<4>(g4, v[6], v[4]) + wx1 * wz1 * vec_dot<4>(g4, v[7], v[5]);
+    const float dz = wx0 * wy0 * vec_dot<4>(g4, v[4], v[0]) + wx1 * wy0 * vec_dot<4>(g4, v[5], v[1]) +
+                     wx0 * wy1 * vec_dot<4>(g4, v[6], v[2]) + wx1 * wy1 * vec_dot<4>(g4, v[7], v[3]);
+    gx = fmaf(dx, li.scale, gx); gy = fmaf(dy, li.scale, gy); gz = fmaf(dz, li.scale, gz);
+}
 }  // namespace run
 
-// The fused density kernel below (density_field_fwd_kernel) repeats this kernel's code: keep the two in step
-// (tests/test_density_fused_gpu.py compares them bit for bit).
+// density_field_fwd_kernel below gathers and blends with the same pieces of namespace run (bit for bit:
+// tests/test_density_fused_gpu.py).
 __global__ void __launch_bounds__(256) grid_fwd_run_kernel(GridMeta meta, const float* __restrict__ table,
                                                            const float* __restrict__ x, int64_t n,
                                                            float* __restrict__ y, int64_t ldy)
@@ -276,29 +252,17 @@ __global__ void __launch_bounds__(256) grid_fwd_run_kernel(GridMeta meta, const 
             const Lead c = phase1(li.scale, px, py, pz, lane);
             float4 R[8];
             corners(li, table, c, half, R);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const float wt = ((k & 1) ? c.w0 : 1 - c.w0) * ((k & 2) ? c.w1 : 1 - c.w1) * ((k & 4) ? c.w2 : 1 - c.w2);
-                vec_fma<4>(acc, wt, R[k]);
-            }
+            blend(acc, c, R);
         }
         *reinterpret_cast<float4*>(st + j * 32 + i * 8 + half * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
     tile::wave_sync();
-    const int piece = lane & 7;
-    if ((lg * LV + (piece >> 1)) < L) {
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int js = it * 8 + (lane >> 3);
-            if (s0 + js < n)
-                *reinterpret_cast<float4*>(y + (s0 + js) * ldy + lg * (LV * F) + piece * 4) =
-                    *reinterpret_cast<const float4*>(st + js * 32 + piece * 4);
-        }
-    }
+    if ((lg * LV + ((lane & 7) >> 1)) < L)                    // the lane's 16-byte piece belongs to an existing level
+        tile_rows_out<32>(st, y, ldy, s0, n, lg * (LV * F), lane);
 }
 
-// The fused density kernel below (density_field_fwd_kernel) repeats this kernel's code: keep the two in step
-// (tests/test_density_fused_gpu.py compares them within the bound it states).
+// density_field_fwd_kernel below forms its input gradient with the same pieces of namespace run
+// (tests/test_density_fused_gpu.py compares the two within the bound it states).
 __global__ void __launch_bounds__(256) grid_bwd_input_run_kernel(GridMeta meta, const float* __restrict__ table,
                                                                  const float* __restrict__ x,
                                                                  const float* __restrict__ dL_dy, int64_t lddy,
@@ -339,19 +303,7 @@ __global__ void __launch_bounds__(256) grid_bwd_input_run_kernel(GridMeta meta, 
         for (int i = 0; i < LV; i++) {
             if (lg * LV + i < L) {
                 const LevelInfo li = level_info(meta, lg * LV + i);
-                const Lead c = phase1(li.scale, px, py, pz, lane);
-                float4 v[8];
-                corners(li, table, c, half, v);
-                const float4 go = *reinterpret_cast<const float4*>(st + j * 32 + i * 8 + half * 4);
-                const float g4[4] = {go.x, go.y, go.z, go.w};
-                const float wx0 = 1 - c.w0, wx1 = c.w0, wy0 = 1 - c.w1, wy1 = c.w1, wz0 = 1 - c.w2, wz1 = c.w2;
-                const float dx = wy0 * wz0 * vec_dot<4>(g4, v[1], v[0]) + wy1 * wz0 * vec_dot<4>(g4, v[3], v[2]) +
-                                 wy0 * wz1 * vec_dot<4>(g4, v[5], v[4]) + wy1 * wz1 * vec_dot<4>(g4, v[7], v[6]);
-                const float dy = wx0 * wz0 * vec_dot<4>(g4, v[2], v[0]) + wx1 * wz0 * vec_dot<4>(g4, v[3], v[1]) +
-                                 wx0 * wz1 * vec_dot<4>(g4, v[6], v[4]) + wx1 * wz1 * vec_dot<4>(g4, v[7], v[5]);
-                const float dz = wx0 * wy0 * vec_dot<4>(g4, v[4], v[0]) + wx1 * wy0 * vec_dot<4>(g4, v[5], v[1]) +
-                                 wx0 * wy1 * vec_dot<4>(g4, v[6], v[2]) + wx1 * wy1 * vec_dot<4>(g4, v[7], v[3]);
-                gx = fmaf(dx, li.scale, gx); gy = fmaf(dy, li.scale, gy); gz = fmaf(dz, li.scale, gz);
+                level_grad(li, table, px, py, pz, lane, half, st + j * 32 + i * 8 + half * 4, gx, gy, gz);
             }
         }
         gx += __shfl_xor(gx, 1); gy += __shfl_xor(gy, 1); gz += __shfl_xor(gz, 1);
@@ -380,11 +332,12 @@ __global__ void __launch_bounds__(256) grid_bwd_input_run_kernel(GridMeta meta, 
 // this kernel).  Every output keeps its kernel's operation order (the run-leader gather and its blend, the MFMA step order and reduction-index
 // permutation of the two streaming MLP kernels, the input gradient's per-level-group partial sums added in level-group
 // order): feat, a1, sigma and dfeat are bitwise what the four kernels write.  d sigma / dx can differ in the last
-// bits: its per-level expression is the same source, but hipcc contracts and packs it (v_pk_fma_f32) differently in
+// bits: its per-level expression is the same function, but hipcc contracts and packs it (v_pk_fma_f32) differently in
 // this kernel (tests/test_density_fused_gpu.py bounds the difference: 128 ulps of the row's largest component).
-// The gather / blend, both MFMA step sequences and the input-gradient expression are COPIES of those kernels' code:
-// a change to grid_fwd_run_kernel, grid_bwd_input_run_kernel, mlp_stream_fwd_kernel<1, 16, SOFTPLUS, 4> or
-// mlp_stream_dgrad_kernel<1, SOFTPLUS> has to be made here too (tests/test_density_fused_gpu.py compares the two).
+// The arithmetic is shared, not restated: the gather, the blend and the input-gradient expression are namespace run's
+// (above), the K steps, dz1, the accumulator -> LDS -> row stores and the butterfly are mlp_tile.h's, as in
+// grid_fwd_run_kernel, grid_bwd_input_run_kernel, mlp_stream_fwd_kernel<1, 16, SOFTPLUS, 4> and
+// mlp_stream_dgrad_kernel<1, SOFTPLUS>.  What this kernel owns is the order of the steps and the LDS layouts.
 //   workgroup: 8 waves, one per CU; W1 (the only copy) sits in LDS as [hidden][input + 4], mlp_stream_fwd's layout.
 //   The data gradient's B operand W1[h][c] is read from it with ds_read_b32 (lanes of a half-wave read consecutive
 //   c): the same values, so the same products.
@@ -397,7 +350,6 @@ constexpr int NW = 8;          // waves per workgroup
 constexpr int LDW = 132;       // W1 row stride in LDS (mlp_stream_fwd_kernel's conflict-free [H][K + 4])
 constexpr int LDT = 36;        // per-wave staging tile row stride
 constexpr int LDS_FLOATS = 128 * LDW + 128 + 128 + 4 + NW * 32 * LDT + NW * 32;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 }  // namespace dens
 
 __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, const float* __restrict__ table,
@@ -411,7 +363,6 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
     using namespace run;
     using dens::LDW;
     using dens::LDT;
-    typedef dens::f32x16 f32x16;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ws = smem;                        // [128 hidden][LDW]: Ws[h * LDW + c] = W1[h][c]
     float* W2s = Ws + 128 * LDW;             // [128]
@@ -433,7 +384,6 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 31, lh = lane >> 5;      // MFMA layout: lane (row, K half)
     const int j = lane >> 1, half = lane & 1;      // gather layout: lane (sample, half row)
-    const int piece = lane & 7;
     float* st = stage + wave * 32 * LDT;
     float* d2w = d2s + wave * 32;
     for (int tile = blockIdx.x * dens::NW + wave; tile < n_tiles; tile += gridDim.x * dens::NW) {
@@ -458,21 +408,11 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
                 float4 R[8];
                 corners(lv, table, c, half, R);
                 float f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const float wt = ((k & 1) ? c.w0 : 1 - c.w0) * ((k & 2) ? c.w1 : 1 - c.w1) * ((k & 4) ? c.w2 : 1 - c.w2);
-                    vec_fma<4>(f, wt, R[k]);
-                }
+                blend(f, c, R);
                 *reinterpret_cast<float4*>(st + j * LDT + i * 8 + half * 4) = make_float4(f[0], f[1], f[2], f[3]);
             }
             tile::wave_sync();
-#pragma unroll
-            for (int it = 0; it < 4; it++) {
-                const int js = it * 8 + (lane >> 3);
-                if (s0 + js < n)
-                    *reinterpret_cast<float4*>(feat + (s0 + js) * 128 + g * 32 + piece * 4) =
-                        *reinterpret_cast<const float4*>(st + js * LDT + piece * 4);
-            }
+            tile_rows_out<LDT>(st, feat, 128, s0, n, g * 32, lane);
             float4 av[4];                                // A operands: feat[li][8q + 4lh .. +3], q = 4g + i
 #pragma unroll
             for (int i = 0; i < 4; i++) av[i] = *reinterpret_cast<const float4*>(st + li * LDT + i * 8 + lh * 4);
@@ -484,14 +424,7 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
 #pragma unroll
                 for (int tn = 0; tn < 4; tn++) bq[tn] = *reinterpret_cast<const float4*>(Ws + (tn * 32 + li) * LDW + 8 * q + 4 * lh);
                 const float a4[4] = {av[i].x, av[i].y, av[i].z, av[i].w};
-#pragma unroll
-                for (int jj = 0; jj < 4; jj++) {
-#pragma unroll
-                    for (int tn = 0; tn < 4; tn++) {
-                        const float bf[4] = {bq[tn].x, bq[tn].y, bq[tn].z, bq[tn].w};
-                        acc[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[jj], bf[jj], acc[tn], 0, 0, 0);
-                    }
-                }
+                mfma_k4(acc, a4, bq);
             }
         }
 
@@ -505,38 +438,18 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
             const float w2 = W2s[tn * 32 + li];
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[tn][r] = softplus_fast(acc[tn][r]);
-#pragma unroll
-            for (int r = 0; r < 16; r++) st[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDT + li] = acc[tn][r];
+            acc_to_tile<LDT>(st, acc[tn], li, lh);
             tile::wave_sync();
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int f = lane + 64 * i, row = f >> 3, c4 = (f & 7) * 4;
-                if (s0 + row < n)
-                    *reinterpret_cast<float4*>(a1 + (s0 + row) * 128 + tn * 32 + c4) = *reinterpret_cast<const float4*>(st + row * LDT + c4);
-            }
+            tile_rows_out<LDT>(st, a1, 128, s0, n, tn * 32, lane);
 #pragma unroll
             for (int qq = 0; qq < 4; qq++) hv[tn * 4 + qq] = *reinterpret_cast<const float4*>(st + li * LDT + 8 * qq + 4 * lh);
             tile::wave_sync();
 #pragma unroll
             for (int r = 0; r < 16; r++) part[r] = fmaf(acc[tn][r], w2, part[r]);
         }
-#pragma unroll
-        for (int hf = 8; hf >= 1; hf >>= 1) {            // mlp_stream_fwd_kernel's transposing butterfly (one output)
-            const int mask = hf * 2;
-            const bool up = (li & mask) != 0;
-#pragma unroll
-            for (int jx = 0; jx < hf; jx++) {
-                float lo = part[jx], hi = part[jx + hf];
-                asm volatile("" : "+v"(lo), "+v"(hi));
-                const float keep = up ? hi : lo;
-                const float send = up ? lo : hi;
-                part[jx] = keep + __shfl_xor(send, mask, 64);
-            }
-        }
         {
-            const float tot = part[0] + __shfl_xor(part[0], 1, 64);
-            const int rr = ((li >> 4) & 1) * 8 + ((li >> 3) & 1) * 4 + ((li >> 2) & 1) * 2 + ((li >> 1) & 1);
-            const int row = (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            const float tot = butterfly16<true>(part, li);   // one output: mlp_stream_fwd_kernel<1, ...>'s form
+            const int row = butterfly_row(li, lh);
             if ((li & 1) == 0) {
                 const float yv = act_fwd(tot + b2s[0], NGP_ACT_SOFTPLUS);
                 if (s0 + row < n) sig[s0 + row] = yv;
@@ -555,13 +468,10 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
 #pragma unroll
         for (int q = 0; q < 16; q++) {
             const float4 w = *reinterpret_cast<const float4*>(W2s + 8 * q + 4 * lh);
-            float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            sv[0] = fmaf(dz, w.x, sv[0]); sv[1] = fmaf(dz, w.y, sv[1]);
-            sv[2] = fmaf(dz, w.z, sv[2]); sv[3] = fmaf(dz, w.w, sv[3]);
+            const float w2[1][4] = {{w.x, w.y, w.z, w.w}};
             const float h4[4] = {hv[q].x, hv[q].y, hv[q].z, hv[q].w};
             float av[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) av[jj] = sv[jj] * act_grad_fast(h4[jj], NGP_ACT_SOFTPLUS);
+            dz1_of<1>(av, &dz, w2, h4, NGP_ACT_SOFTPLUS);
 #pragma unroll
             for (int jj = 0; jj < 4; jj++) {
                 const float* wrow = Ws + (8 * q + 4 * lh + jj) * LDW + li;   // W1[h][c], h = 8q + 4lh + jj, c = 32 tn + li
@@ -574,34 +484,16 @@ __global__ void __launch_bounds__(512) density_field_fwd_kernel(GridMeta meta, c
         float tx = 0.0f, ty = 0.0f, tz = 0.0f;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) st[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDT + li] = acc2[g][r];
+            acc_to_tile<LDT>(st, acc2[g], li, lh);
             tile::wave_sync();
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int f = lane + 64 * i, row = f >> 3, c4 = (f & 7) * 4;
-                if (s0 + row < n)
-                    *reinterpret_cast<float4*>(dfeat + (s0 + row) * 128 + g * 32 + c4) = *reinterpret_cast<const float4*>(st + row * LDT + c4);
-            }
+            tile_rows_out<LDT>(st, dfeat, 128, s0, n, g * 32, lane);
             float gx = 0.0f, gy = 0.0f, gz = 0.0f;
             int l0 = g * 4;
             asm volatile("" : "+s"(l0));                 // level records are loaded where they are used, not kept in SGPRs
 #pragma unroll 2
             for (int i = 0; i < 4; i++) {
                 const LevelInfo lv = level_info(meta, l0 + i);
-                const Lead c = phase1(lv.scale, px, py, pz, lane);
-                float4 v[8];
-                corners(lv, table, c, half, v);
-                const float4 go = *reinterpret_cast<const float4*>(st + j * LDT + i * 8 + half * 4);
-                const float g4[4] = {go.x, go.y, go.z, go.w};
-                const float wx0 = 1 - c.w0, wx1 = c.w0, wy0 = 1 - c.w1, wy1 = c.w1, wz0 = 1 - c.w2, wz1 = c.w2;
-                const float dx = wy0 * wz0 * vec_dot<4>(g4, v[1], v[0]) + wy1 * wz0 * vec_dot<4>(g4, v[3], v[2]) +
-                                 wy0 * wz1 * vec_dot<4>(g4, v[5], v[4]) + wy1 * wz1 * vec_dot<4>(g4, v[7], v[6]);
-                const float dy = wx0 * wz0 * vec_dot<4>(g4, v[2], v[0]) + wx1 * wz0 * vec_dot<4>(g4, v[3], v[1]) +
-                                 wx0 * wz1 * vec_dot<4>(g4, v[6], v[4]) + wx1 * wz1 * vec_dot<4>(g4, v[7], v[5]);
-                const float dzz = wx0 * wy0 * vec_dot<4>(g4, v[4], v[0]) + wx1 * wy0 * vec_dot<4>(g4, v[5], v[1]) +
-                                  wx0 * wy1 * vec_dot<4>(g4, v[6], v[2]) + wx1 * wy1 * vec_dot<4>(g4, v[7], v[3]);
-                gx = fmaf(dx, lv.scale, gx); gy = fmaf(dy, lv.scale, gy); gz = fmaf(dzz, lv.scale, gz);
+                level_grad(lv, table, px, py, pz, lane, half, st + j * LDT + i * 8 + half * 4, gx, gy, gz);
             }
             gx += __shfl_xor(gx, 1); gy += __shfl_xor(gy, 1); gz += __shfl_xor(gz, 1);
             tx += gx; ty += gy; tz += gz;                // (grid_bwd_input_run_kernel: sum = 0, += each level group's wave)
@@ -997,7 +889,7 @@ __global__ void __launch_bounds__(256) grid_bwd_bwd_input_kernel(GridMeta meta, 
         // derivative of the trilinear weight of corner k w.r.t. each coordinate
         const float coef = vx * (cx ? 1.0f : -1.0f) * wy * wz + vy * (cy ? 1.0f : -1.0f) * wx * wz +
                            vz * (cz ? 1.0f : -1.0f) * wx * wy;
-        const uint32_t row = row_index(li, c.g[0] + cx, c.g[1] + cy, c.g[2] + cz);
+        const uint32_t row = corner_row(li, c, k);
         if (dL_ddLdy) ddy = fmaf(coef, table[(size_t)row * F + f], ddy);
         if (dtable && g != 0.0f && coef != 0.0f) atomicAdd(dtable + (size_t)row * F + f, coef * g);
     }
@@ -1089,29 +981,6 @@ __global__ void sh_bwd_kernel(const float* __restrict__ xin, const float* __rest
         dx += 0.59004358992664352f * (-3.0f * x2 + 3.0f * y2) * g[15]; dy += 0.59004358992664352f * 6.0f * x * y * g[15];
     }
     dL_dx[3 * i] = 2 * dx; dL_dx[3 * i + 1] = 2 * dy; dL_dx[3 * i + 2] = 2 * dz;
-}
-
-bool make_meta(const ngp_grid_desc* d, GridMeta& m)
-{
-    if (!d || d->n_levels < 1 || d->n_levels > NGP_MAX_LEVELS) return false;
-    const uint32_t F = d->n_features;
-    if (!(F == 1 || F == 2 || F == 4 || F == 8)) return false;
-    m.n_levels = d->n_levels; m.n_features = F;
-    for (uint32_t l = 0; l < NGP_MAX_LEVELS; l++) {
-        m.offset[l] = 0; m.size[l] = 1; m.res[l] = 1; m.flags[l] = 0; m.scale[l] = 0;
-    }
-    for (uint32_t l = 0; l < d->n_levels; l++) {
-        const uint32_t size = d->offsets[l + 1] - d->offsets[l], res = d->resolution[l];
-        if (size == 0) return false;
-        // tcnn's index loop: accumulate dims while stride <= size; hashed iff size < final stride
-        uint64_t stride = 1;
-        for (int k = 0; k < 3 && stride <= size; k++) stride *= res;
-        uint32_t flags = 0;
-        if (size < stride) flags |= 1u;
-        if ((size & (size - 1)) == 0) flags |= 2u;
-        m.offset[l] = d->offsets[l]; m.size[l] = size; m.res[l] = res; m.flags[l] = flags; m.scale[l] = d->scale[l];
-    }
-    return true;
 }
 
 template <int F>

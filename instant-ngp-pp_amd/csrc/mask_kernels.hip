@@ -15,9 +15,10 @@
 //              - lane (k, quarter) adds the tile's 32 rows into its 4 dW1 elements (registers), db1 / dW2 / db2 likewise;
 //            a workgroup walks its tiles with a grid stride and adds its weight sums ONCE at the end: 1 089 atomics per
 //            workgroup, at most 256 workgroups.
-// Negative coordinates (uvi lies in [-0.5, 0.5)) take tiny-cuda-nn's route: (uint32_t)(int)floorf(p) and unsigned
-// wrap in the dense index and in the hash.
+// Negative coordinates (uvi lies in [-0.5, 0.5)) take tiny-cuda-nn's route (grid_index.h): (uint32_t)(int)floorf(p) and
+// unsigned wrap in the dense index and in the hash.
 #include "common.h"
+#include "grid_index.h"
 
 namespace {
 
@@ -29,26 +30,10 @@ constexpr int MK_LDW = MK_IN + 1;
 constexpr int MK_LDZ = MK_H + 1;
 constexpr int MK_MAX_BLOCKS = 256;
 
-struct MaskMeta {
-    uint32_t offset[MK_L], size[MK_L], res[MK_L], flags[MK_L];   // flags bit0: hashed, bit1: size is a power of two
-    float scale[MK_L];
-};
-
-// same rule as the grid kernels' make_meta (tcnn's index loop: hashed iff the level is smaller than its dense cube)
-bool mask_meta(const ngp_grid_desc* d, MaskMeta& m)
+// the layout the kernels are written for (levels and features as compile-time constants)
+bool mask_meta(const ngp_grid_desc* d, GridMeta& m)
 {
-    if (!d || d->n_levels != MK_L || d->n_features != 2) return false;
-    for (int l = 0; l < MK_L; l++) {
-        const uint32_t size = d->offsets[l + 1] - d->offsets[l], res = d->resolution[l];
-        if (size == 0) return false;
-        uint64_t stride = 1;
-        for (int k = 0; k < 3 && stride <= size; k++) stride *= res;
-        uint32_t flags = 0;
-        if (size < stride) flags |= 1u;
-        if ((size & (size - 1)) == 0) flags |= 2u;
-        m.offset[l] = d->offsets[l]; m.size[l] = size; m.res[l] = res; m.flags[l] = flags; m.scale[l] = d->scale[l];
-    }
-    return true;
+    return make_meta(d, m) && m.n_levels == MK_L && m.n_features == 2;
 }
 
 struct Corners {
@@ -56,34 +41,16 @@ struct Corners {
     float w[8];
 };
 
-__device__ __forceinline__ Corners corners_of(const MaskMeta& m, int level, float px, float py, float pz)
+// the level rule is grid_index.h's
+__device__ __forceinline__ Corners corners_of(const GridMeta& m, int level, float px, float py, float pz)
 {
-    const uint32_t off = m.offset[level], size = m.size[level], res = m.res[level], flags = m.flags[level];
-    const float scale = m.scale[level];
-    const float p[3] = {fmaf(scale, px, 0.5f), fmaf(scale, py, 0.5f), fmaf(scale, pz, 0.5f)};
-    uint32_t g[3];
-    float f[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float fl = floorf(p[k]);
-        g[k] = (uint32_t)(int)fl;
-        f[k] = p[k] - fl;
-    }
+    const LevelInfo li = level_info(m, level);
+    const Cell cell = cell_of(li.scale, px, py, pz);
     Corners c;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const uint32_t cx = k & 1, cy = (k >> 1) & 1, cz = (k >> 2) & 1;
-        const uint32_t x = g[0] + cx, y = g[1] + cy, z = g[2] + cz;
-        uint32_t idx;
-        if (flags & 1u) {
-            idx = x ^ (y * 2654435761u) ^ (z * 805459861u);
-            idx = (flags & 2u) ? (idx & (size - 1u)) : (idx % size);
-        } else {
-            idx = x + y * res + z * res * res;
-            if (idx >= size) idx = (flags & 2u) ? (idx & (size - 1u)) : (idx % size);
-        }
-        c.row[k] = off + idx;
-        c.w[k] = (cx ? f[0] : 1 - f[0]) * (cy ? f[1] : 1 - f[1]) * (cz ? f[2] : 1 - f[2]);
+        c.row[k] = corner_row(li, cell, k);
+        c.w[k] = corner_weight(cell.w[0], cell.w[1], cell.w[2], k);
     }
     return c;
 }
@@ -102,7 +69,7 @@ __device__ __forceinline__ void stage_weights(MaskLds& s, const float* __restric
 }
 
 // lane (row, j): level j of the row -> feat[row][2j, 2j+1] in LDS (zeros for rows behind n); keeps the corners
-__device__ __forceinline__ Corners gather_level(const MaskMeta& m, const float* __restrict__ table,
+__device__ __forceinline__ Corners gather_level(const GridMeta& m, const float* __restrict__ table,
                                                 const float* __restrict__ uvi, int64_t row, bool live, int lrow, int j,
                                                 MaskLds& s)
 {
@@ -138,7 +105,7 @@ __device__ __forceinline__ void layer1(const MaskLds& s, int lrow, int j, float 
     }
 }
 
-__global__ void __launch_bounds__(256) mask_field_fwd_kernel(MaskMeta m, const float* __restrict__ table,
+__global__ void __launch_bounds__(256) mask_field_fwd_kernel(GridMeta m, const float* __restrict__ table,
                                                              const float* __restrict__ W1, const float* __restrict__ b1,
                                                              const float* __restrict__ W2, const float* __restrict__ b2,
                                                              const float* __restrict__ uvi, int64_t n,
@@ -161,7 +128,9 @@ __global__ void __launch_bounds__(256) mask_field_fwd_kernel(MaskMeta m, const f
     if (live && j == 0) mask[row] = 1.0f / (1.0f + expf(-(a2 + b2[0])));
 }
 
-__global__ void __launch_bounds__(256) mask_field_bwd_kernel(MaskMeta m, const float* __restrict__ table,
+// (waves_per_eu: with the shared level rule's plain modulo hipcc otherwise settles at 106 registers, 4 waves; held to the
+// 5 waves it had, it allocates 88 without scratch)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) mask_field_bwd_kernel(GridMeta m, const float* __restrict__ table,
                                                              const float* __restrict__ W1, const float* __restrict__ b1,
                                                              const float* __restrict__ W2, const float* __restrict__ uvi,
                                                              const float* __restrict__ mask,
@@ -244,7 +213,7 @@ int ngp_mask_field_fwd(const ngp_grid_desc* desc, const float* table, const floa
 {
     if (n < 0) return NGP_EINVAL;
     if (n == 0) return NGP_OK;
-    MaskMeta m;
+    GridMeta m;
     if (!mask_meta(desc, m) || !table || !W1 || !b1 || !W2 || !b2 || !uvi || !mask) return NGP_EINVAL;
     const int64_t n_tiles = (n + MK_ROWS - 1) / MK_ROWS;
     if (n_tiles > 0x7fffffff) return NGP_EINVAL;
@@ -259,7 +228,7 @@ int ngp_mask_field_bwd(const ngp_grid_desc* desc, const float* table, const floa
 {
     if (n < 0) return NGP_EINVAL;
     if (n == 0) return NGP_OK;
-    MaskMeta m;
+    GridMeta m;
     if (!mask_meta(desc, m) || !table || !W1 || !b1 || !W2 || !uvi || !mask || !dL_dmask || !dtable || !dW1 || !db1 ||
         !dW2 || !db2) return NGP_EINVAL;
     const int64_t n_tiles = (n + MK_ROWS - 1) / MK_ROWS;

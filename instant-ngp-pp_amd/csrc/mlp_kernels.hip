@@ -8,14 +8,13 @@
 //                                                          A = dz [k][m],  B = x [k][n]
 // Both operands are staged k-major in LDS (As[k][m], Bs[k][n]) so that an MFMA fragment read
 // is one conflict-free ds_read_b32 per lane: lane l of the 32x32x2 MFMA holds A[i=l&31][k=l>>5]
-// and B[k=l>>5][j=l&31]; C/D is col=l&31, row=(r&3)+8*(r>>2)+4*(l>>5).
+// and B[k=l>>5][j=l&31]; C/D is col=l&31, row=acc_row(r, l>>5) (mlp_tile.h).
 // Layers with n_out <= 4 (the density head, networks.py:57) use VALU kernels instead.
 #include "common.h"
 #include "mlp_act.h"
+#include "mlp_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
 
@@ -102,13 +101,7 @@ struct TileT {
             if (row < ROWS) {
                 const float4 dq = *reinterpret_cast<const float4*>(D2s + row * 4);
                 const float d[4] = {dq.x, dq.y, dq.z, dq.w};
-                float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int o = 0; o < OM; o++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) sv[j] = fmaf(d[o], w2[o][j], sv[j]);
-#pragma unroll
-                for (int j = 0; j < 4; j++) v[pass][j] = sv[j] * act_grad_fast(v[pass][j], act);
+                dz1_of<OM>(v[pass], d, w2, v[pass], act);
             }
         }
     }
@@ -182,19 +175,15 @@ struct TileD {
             if (kr < BK) {
                 const float4 dq = *reinterpret_cast<const float4*>(D2s + kr * 4);
                 const float d[4] = {dq.x, dq.y, dq.z, dq.w};
-                float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (w2g) {
 #pragma unroll
-                for (int o = 0; o < OM; o++) {
-                    if (w2g) {
+                    for (int o = 0; o < OM; o++) {
                         gb[o] += d[o];
 #pragma unroll
                         for (int j = 0; j < 4; j++) gw[o][j] = fmaf(d[o], v[pass][j], gw[o][j]);
                     }
-#pragma unroll
-                    for (int j = 0; j < 4; j++) sv[j] = fmaf(d[o], w2[o][j], sv[j]);
                 }
-#pragma unroll
-                for (int j = 0; j < 4; j++) v[pass][j] = sv[j] * act_grad_fast(v[pass][j], act);
+                dz1_of<OM>(v[pass], d, w2, v[pass], act);
             }
         }
     }
@@ -377,6 +366,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p)
         // dot products of its TN columns for its 16 rows, a transposing butterfly over the 32 lanes
         // of the half-wave (16 shuffles per output instead of 16 x 5) leaves one row total per
         // lane pair, the WN column halves meet in LDS (the staging tiles are free by now).
+        // (butterfly16 / butterfly_row of mlp_tile.h written out: called from here, the <2, 2, 2, 2, 8> instantiation, which is
+        // at its register limit, spills 6 to 21 registers instead of 4; the same goes for the accumulator rows below)
         float* red = As;   // [WN][BM][F2]
         constexpr int OGW = F2 < 4 ? F2 : 4;            // outputs per pass over the tile
         constexpr int OGN = (F2 + OGW - 1) / OGW;       // passes (8 outputs: two passes of four keep 64 partial sums)
@@ -400,7 +391,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p)
                         w2[o] = (ncol && og * OGW + o < p.f2_nout) ? p.f2_W2[(og * OGW + o) * p.f2_ldw2 + n] : 0.0f;
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
-                        const int64_t m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const int64_t m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;   // acc_row(r, lh), added in 64 bits
                         const float v = act_fwd(acc[tm][tn][r] + bv, p.act);
                         if (og == 0 && ncol && m < p.M) p.C[m * p.ldc + n] = v;
 #pragma unroll
@@ -417,7 +408,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p)
 #pragma unroll
                         for (int j = 0; j < half; j++) {
                             float lo = v[j], hi = v[j + half];
-                            if constexpr (OGW == 1) asm volatile("" : "+v"(lo), "+v"(hi));   // plain selects (see mlp_stream_fwd_kernel's butterfly)
+                            if constexpr (OGW == 1) asm volatile("" : "+v"(lo), "+v"(hi));   // plain selects (see butterfly16)
                             const float keep = up ? hi : lo;
                             const float send = up ? lo : hi;
                             v[j] = keep + __shfl_xor(send, mask, 64);
@@ -455,7 +446,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p)
             const float bv = (MODE == MODE_FWD && p.bias) ? p.bias[n] : 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int64_t m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int64_t m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;   // acc_row(r, lh), added in 64 bits
                 if (m >= p.M) continue;
                 float v = acc[tm][tn][r];
                 if (MODE == MODE_FWD) {
@@ -508,8 +499,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) g
 // activated tile leaves through a per-wave [32][32] LDS transposition as 16-byte stores, the second
 // layer is per-lane partial products and a transposing butterfly over the 32 lanes (as in
 // gemm_fwd2_kernel, without the cross-wave combine: a wave owns all H columns of its rows).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // The row prefetch is written as inline assembly with hand-placed s_waitcnt: vmcnt counts loads AND
 // stores in issue order, and the compiler's own bookkeeping answers a load that is older than the
 // stores of the previous tile's epilogue with a full drain at every tile start.  The piece loaded at
@@ -527,8 +516,8 @@ __device__ __forceinline__ void stream_wait(f32x4& v)
     asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v) : "n"(N));
 }
 
-// density_field_fwd_kernel (grid_kernels.hip) repeats this kernel's K steps and epilogue for the density head
-// (<1, 16, SOFTPLUS, 4> / <1, SOFTPLUS>): keep the two in step (tests/test_density_fused_gpu.py compares them bit for bit).
+// density_field_fwd_kernel (grid_kernels.hip) computes the density head as <1, 16, SOFTPLUS, 4> does, bit for bit
+// (tests/test_density_fused_gpu.py): the K steps, the tile stores and the butterfly are the pieces of mlp_tile.h in both.
 template <int F2, int KQ, int ACT1, int TN>   // KQ = K / 8: float4 pieces per lane and tile; TN = H / 32 column blocks
 __global__ void __launch_bounds__(512) mlp_stream_fwd_kernel(GemmArgs p, int n_tiles)
 {
@@ -598,14 +587,7 @@ __global__ void __launch_bounds__(512) mlp_stream_fwd_kernel(GemmArgs p, int n_t
                 for (int tn = 0; tn < TN; tn++)
                     bnxt[tn] = *reinterpret_cast<const float4*>(Ws + (tn * 32 + li) * LDW + 8 * (q + 1) + 4 * lh);
             }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-#pragma unroll
-                for (int tn = 0; tn < TN; tn++) {
-                    const float bf[4] = {bcur[tn].x, bcur[tn].y, bcur[tn].z, bcur[tn].w};
-                    acc[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bf[j], acc[tn], 0, 0, 0);
-                }
-            }
+            mfma_k4(acc, av, bcur);
             switch (q) {   // the immediate offset must be a literal
 #define STREAM_CASE(Q) case Q: stream_load<32 * Q>(a[Q < KQ ? Q : 0], nsrc); break;
                 STREAM_CASE(0) STREAM_CASE(1) STREAM_CASE(2) STREAM_CASE(3) STREAM_CASE(4) STREAM_CASE(5) STREAM_CASE(6)
@@ -643,18 +625,8 @@ __global__ void __launch_bounds__(512) mlp_stream_fwd_kernel(GemmArgs p, int n_t
                         const float z = acc[tn][r];
                         acc[tn][r] = ACT1 == NGP_ACT_RELU ? fmaxf(z, 0.0f) : (ACT1 == NGP_ACT_SOFTPLUS ? softplus_fast(z) : z);
                     }
-                    // hidden store: 64 dword stores per lane and tile would overrun the 64 vector-memory
-                    // operations a wave may have in flight; through LDS the 32x32 block leaves as 4 x 16 bytes
-                    // per lane (rows of 128 contiguous bytes).  Both access patterns are conflict-free on an
-                    // unpadded [32][32] tile; LDS operations of one wave execute in order, so no barrier.
-#pragma unroll
-                    for (int r = 0; r < 16; r++) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = acc[tn][r];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const int f = lane + 64 * i, row = f >> 3, c4 = (f & 7) * 4;
-                        const float4 v = *reinterpret_cast<const float4*>(stg + row * 32 + c4);
-                        if (m0 + row < p.M) *reinterpret_cast<float4*>(p.C + (m0 + row) * p.ldc + tn * 32 + c4) = v;
-                    }
+                    acc_to_tile<32>(stg, acc[tn], li, lh);   // hidden store: through LDS, as rows of 128 contiguous bytes
+                    tile_rows_out<32>(stg, p.C, p.ldc, m0, p.M, tn * 32, lane);
                 }
 #pragma unroll
                 for (int r = 0; r < 16; r++)
@@ -663,26 +635,8 @@ __global__ void __launch_bounds__(512) mlp_stream_fwd_kernel(GemmArgs p, int n_t
             }
 #pragma unroll
             for (int o = 0; o < OGW; o++) {
-                float* v = part[o];
-#pragma unroll
-                for (int half = 8; half >= 1; half >>= 1) {
-                    const int mask = half * 2;   // 16, 8, 4, 2
-                    const bool up = (li & mask) != 0;
-#pragma unroll
-                    for (int j = 0; j < half; j++) {
-                        float lo = v[j], hi = v[j + half];
-                        // two plain selects: without the barrier hipcc turns `up ? v[j + half] : v[j]` into an extract with a
-                        // lane-dependent index, i.e. a 15-compare select chain per read (930 vector instructions per tile)
-                        // (one output only: with 4 the compiler emits the plain selects by itself and the barrier costs 5 %)
-                        if constexpr (OGW == 1) asm volatile("" : "+v"(lo), "+v"(hi));
-                        const float keep = up ? hi : lo;
-                        const float send = up ? lo : hi;
-                        v[j] = keep + __shfl_xor(send, mask, 64);
-                    }
-                }
-                const float tot = v[0] + __shfl_xor(v[0], 1, 64);
-                const int rr = ((li >> 4) & 1) * 8 + ((li >> 3) & 1) * 4 + ((li >> 2) & 1) * 2 + ((li >> 1) & 1);
-                const int64_t m = m0 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+                const float tot = butterfly16<OGW == 1>(part[o], li);
+                const int64_t m = m0 + butterfly_row(li, lh);
                 const int oo = og * OGW + o;
                 if ((li & 1) == 0 && oo < nout && m < p.M) {
                     const float yv = act_fwd(tot + b2s[oo], f2_act);
@@ -712,8 +666,8 @@ __device__ __forceinline__ void stream_wait1(float& v)
 }
 
 
-// density_field_fwd_kernel (grid_kernels.hip) repeats this kernel's K steps and epilogue for the density head
-// (<1, 16, SOFTPLUS, 4> / <1, SOFTPLUS>): keep the two in step (tests/test_density_fused_gpu.py compares them bit for bit).
+// density_field_fwd_kernel (grid_kernels.hip) computes the density head's data gradient as <1, SOFTPLUS> does, bit for
+// bit (tests/test_density_fused_gpu.py): dz1, the K steps and the tile stores are the pieces of mlp_tile.h in both.
 template <int XF, int ACT1>
 __global__ void __launch_bounds__(512) mlp_stream_dgrad_kernel(GemmArgs p, int n_tiles)
 {
@@ -784,24 +738,15 @@ __global__ void __launch_bounds__(512) mlp_stream_dgrad_kernel(GemmArgs p, int n
                     bnxt[tn] = *reinterpret_cast<const float4*>(Wt + (tn * 32 + li) * LDW + 8 * (q + 1) + 4 * lh);
             }
             // dz1 for this lane's 4 hidden units
-            float sv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            float w2[XF][4];
 #pragma unroll
             for (int o = 0; o < XF; o++) {
                 const float4 w = *reinterpret_cast<const float4*>(W2s + o * 128 + 8 * q + 4 * lh);
-                sv[0] = fmaf(dcur[o], w.x, sv[0]); sv[1] = fmaf(dcur[o], w.y, sv[1]);
-                sv[2] = fmaf(dcur[o], w.z, sv[2]); sv[3] = fmaf(dcur[o], w.w, sv[3]);
+                w2[o][0] = w.x; w2[o][1] = w.y; w2[o][2] = w.z; w2[o][3] = w.w;
             }
             float av[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) av[j] = sv[j] * act_grad_fast(hv[j], ACT1);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-#pragma unroll
-                for (int tn = 0; tn < 4; tn++) {
-                    const float bf[4] = {bcur[tn].x, bcur[tn].y, bcur[tn].z, bcur[tn].w};
-                    acc[tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bf[j], acc[tn], 0, 0, 0);
-                }
-            }
+            dz1_of<XF>(av, dcur, w2, hv, ACT1);
+            mfma_k4(acc, av, bcur);
             switch (q) {   // the immediate offset must be a literal
 #define STREAM_CASE(Q) case Q: stream_load<32 * Q>(a[Q], nsrc); break;
                 STREAM_CASE(0) STREAM_CASE(1) STREAM_CASE(2) STREAM_CASE(3) STREAM_CASE(4) STREAM_CASE(5) STREAM_CASE(6)
@@ -819,18 +764,12 @@ __global__ void __launch_bounds__(512) mlp_stream_dgrad_kernel(GemmArgs p, int n
 #pragma unroll
             for (int tn = 0; tn < 4; tn++) bcur[tn] = bnxt[tn];
         }
-        // ---- store the tile through the LDS transposition (see mlp_stream_fwd_kernel)
+        // ---- store the tile through the LDS transposition (acc_to_tile / tile_rows_out, mlp_tile.h)
         const int64_t m0 = (int64_t)tile * 32;
 #pragma unroll
         for (int tn = 0; tn < 4; tn++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = acc[tn][r];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int f = lane + 64 * i, row = f >> 3, c4 = (f & 7) * 4;
-                const float4 v = *reinterpret_cast<const float4*>(stg + row * 32 + c4);
-                if (m0 + row < p.M) *reinterpret_cast<float4*>(p.C + (m0 + row) * p.ldc + tn * 32 + c4) = v;
-            }
+            acc_to_tile<32>(stg, acc[tn], li, lh);
+            tile_rows_out<32>(stg, p.C, p.ldc, m0, p.M, tn * 32, lane);
         }
     }
     (void)nout;
@@ -1034,7 +973,7 @@ __global__ void __launch_bounds__(512) mlp_stream_wgrad_kernel(GemmArgs p, int64
 #pragma unroll
         for (int rr = 0; rr < 8; rr++) {
             const int r = half2 * 8 + rr;
-            const int row16 = (rr & 3) + 8 * (rr >> 2) + 4 * lh;        // row inside the 16-row half
+            const int row16 = acc_row(rr, lh);                          // row inside the 16-row half
             const float4 v = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
             *reinterpret_cast<float4*>(&wstage[row16][4 * li]) = v;
         }
@@ -1049,7 +988,7 @@ __global__ void __launch_bounds__(512) mlp_stream_wgrad_kernel(GemmArgs p, int64
         if (col < N) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int row = wave * 32 + acc_row(r, lh);
                 atomicAdd(p.C + (int64_t)row * p.ldc + col, acc[TN - 1][r]);
             }
         }

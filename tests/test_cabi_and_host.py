@@ -317,6 +317,22 @@ def test_product_library_reads_no_environment(ngp):
     assert "getenv" not in out
 
 
+def test_every_header_is_part_of_the_build_digest():
+    """A header missing from build.HEADERS leaves a stale library undetected: every csrc/*.h is in the list, and every
+    #include "..." of a csrc/*.hip (and of those headers) names a file of the list."""
+    import re
+    from ngp_amd import build
+    listed = {os.path.realpath(h) for h in build.HEADERS}
+    names = sorted(os.listdir(build.CSRC))
+    for f in names:
+        if f.endswith(".h"):
+            assert os.path.realpath(os.path.join(build.CSRC, f)) in listed, f
+    for f in names:
+        if f.endswith((".hip", ".h")):
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(build.CSRC, f)).read(), re.M):
+                assert os.path.realpath(os.path.join(build.CSRC, inc)) in listed, (f, inc)
+
+
 def test_sources_have_one_code_path_per_job():
     """No compile-time or environment switch selects between kernel variants, and the package's Python reads only the
     environment variables of the distributed launch (torch.distributed's and NGP_DIST_BACKEND / NGP_FORCE_SHARDED, which
