@@ -361,6 +361,29 @@ int ngp_mask_field_bwd(const ngp_grid_desc* desc, const float* table, const floa
                        float* db1, float* dW2, float* db2, void* stream);
 
 /* ------------------------------------------------------------------------
+ * E1  per-image appearance codes (embed_a: train.py:104-108, 238-244, rendering.py:217-219): the broadcast of a ray's
+ * row of the embedding table over the ray's samples, and the segmented sum of the gradient back.  One launch each
+ * way, ray-parallel (one wave per row of rays_a).
+ * weight (n_imgs, E) f32, 1 <= E <= 32; img_idxs (n_rays) i64: image of every ray; rays_a (n_rays, 3) i64: (ray
+ * index, first sample, sample count) as the marcher emits them.
+ * fwd: `out` points at the FIRST code column of a row-major matrix with row stride `ld` floats (column 144 of rgb_net's
+ *   input): for every row r of rays_a and every sample s in [start, start + count)
+ *     out[s][0:E] = weight[img_idxs[rays_a[r][0]]],  out[s][E:n_cols] = 1.0f  (tcnn's ones-padding), E <= n_cols <= 64.
+ *   Sample rows that belong to no segment and the columns outside [0, n_cols) are not touched.
+ * bwd: `dL_dcols` points at the first code column of the gradient matrix (row stride `ld`); d_weight (n_imgs, E) is
+ *   ACCUMULATED into (+=, the caller zeroes): d_weight[i][c] += sum over the rays of image i, over their samples, of
+ *   dL_dcols[s][c].  A ray's sum is formed inside its wave; consecutive rays of one image are merged before they go to
+ *   memory as float atomics (sums depend on arrival order in the last bits).
+ * A ray with count <= 0 contributes nothing.  A ray whose image index lies outside [0, n_imgs) (or whose ray index lies
+ * outside [0, n_rays)) gets zeros in [0, E) forward and contributes nothing backward: such an index is never used as an
+ * address.  n_rays == 0 returns NGP_OK before any pointer is looked at.
+ * ---------------------------------------------------------------------- */
+int ngp_embed_a_fwd(const float* weight, int64_t n_imgs, int E, const int64_t* img_idxs, const int64_t* rays_a,
+                    int64_t n_rays, float* out, int64_t ld, int n_cols, void* stream);
+int ngp_embed_a_bwd(const float* dL_dcols, int64_t ld, int E, const int64_t* img_idxs, const int64_t* rays_a,
+                    int64_t n_rays, int64_t n_imgs, float* d_weight, void* stream);
+
+/* ------------------------------------------------------------------------
  * H5  spherical harmonics (tcnn.Encoding otype SphericalHarmonics, degree 1..4,
  * networks.py:78-85,128-135).  x (n,3) in [0,1] -> y (n, degree^2).
  * ---------------------------------------------------------------------- */

@@ -9,6 +9,7 @@ Sub-modules (same names / call signatures as zhihao-lin/instant-ngp-pp):
   networks          — NGP
   losses            — NeRFLoss, DistortionLoss
   implicit_mask     — implicit_mask, the transient mask field of the embed_msk recipe (models/implicit_mask.py)
+  appearance        — FrameEmbedding (utils.py:97-143) and RayCodes, the per-image appearance codes of the embed_a recipe
   trainer           — the training schedule of train.py (no Lightning)
   mesh              — marching cubes + PLY export (extract_mesh.py)
   metrics           — psnr, ssim
@@ -19,7 +20,7 @@ Every compute call goes through libngp_hip.so (include/ngp_hip.h); there is no C
 from . import _lib  # noqa: F401  (parses the header; the .so is loaded on first use)
 
 __all__ = ["vren", "tinycudann", "torch_scatter", "custom_functions", "rendering", "networks", "losses",
-           "metrics", "trainer", "synthetic", "ckpt", "mesh", "evaluation", "colormap", "implicit_mask",
+           "metrics", "trainer", "synthetic", "ckpt", "mesh", "evaluation", "colormap", "implicit_mask", "appearance",
            "install_as_reference_modules"]
 
 

@@ -25,6 +25,7 @@ SOURCES = [
     ("grid_kernels.hip", []),
     ("mlp_kernels.hip", []),
     ("mask_kernels.hip", []),
+    ("embed_kernels.hip", []),
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),
     ("image_kernels.hip", ["-ffp-contract=off"]),   # frame packing is bit-identical to its numpy restatement

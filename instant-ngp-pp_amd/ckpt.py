@@ -39,12 +39,16 @@ def load_ckpt(model, ckpt_path, model_name='model', prefixes_to_ignore=()):
             own[k].copy_(v.to(own[k].device))
 
 
-def save_ckpt(model, path, extra=None, msk_model=None):
+def save_ckpt(model, path, extra=None, msk_model=None, embedding_a=None):
     """writes {'state_dict': {'model.<key>': ...}} like Lightning's ModelCheckpoint(save_weights_only); the transient
-    mask model of the embed_msk recipe goes beside it under 'msk_model.<key>' (train.py:112-113, 236)"""
+    mask model of the embed_msk recipe goes beside it under 'msk_model.<key>' (train.py:112-113, 236) and the appearance
+    table of the embed_a recipe (an nn.Embedding, or a FrameEmbedding's) as 'embedding_a.weight' (train.py:104-108)"""
     sd = {f"model.{k}": v.detach().cpu() for k, v in model.state_dict().items()}
     if msk_model is not None:
         sd.update({f"msk_model.{k}": v.detach().cpu() for k, v in msk_model.state_dict().items()})
+    if embedding_a is not None:    # (behind the mask model: the order in which train.py registers the three)
+        embedding_a = getattr(embedding_a, "embedding_a", embedding_a)
+        sd.update({f"embedding_a.{k}": v.detach().cpu().clone() for k, v in embedding_a.state_dict().items()})
     if extra:
         sd.update(extra)
     torch.save({'state_dict': sd}, path)

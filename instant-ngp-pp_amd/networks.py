@@ -24,6 +24,7 @@ from torch.autograd import Function
 from . import tinycudann as tcnn
 from . import vren
 from ._lib import call, call_host
+from .appearance import RayCodes
 from .custom_functions import TruncExp
 from .rendering import NEAR_DISTANCE
 
@@ -272,7 +273,9 @@ class _FieldFn(Function):
     """
 
     @staticmethod
-    def forward(ctx, model, x, d, embed_a, xyz_table, W1, b1, W2, b2, rgb_table, rgb_p, nrm_p, sem_p):
+    def forward(ctx, model, x, d, embed_a, xyz_table, W1, b1, W2, b2, rgb_table, rgb_p, nrm_p, sem_p, ray_codes=None):
+        # ray_codes = (img_idxs (n_rays) i64, rays_a (n_rays, 3) i64) of appearance.RayCodes: embed_a is then the
+        # (n_imgs, E) embedding TABLE, broadcast per sample by ngp_embed_a_fwd and summed back by ngp_embed_a_bwd
         n = x.shape[0]
         dev = x.device
         xe, re = model.xyz_encoder, model.rgb_encoder
@@ -311,10 +314,19 @@ class _FieldFn(Function):
             call("grid_fwd", re.desc, rgb_table, xn, n, rgb_in[:, 16:], Kp)
             if ev_p is not None:
                 ev_p.wait()   # the MLPs' piece
-            if E:
-                rgb_in[:, 144:K] = embed_a
-            if Kp > K:
-                rgb_in[:, K:] = 1.0
+            if ray_codes is not None:
+                img_idxs, rays_a = ray_codes
+                if not getattr(rays_a, "_ngp_full_cover", False):   # rows outside every segment: finite inputs
+                    rgb_in[:, 144:K] = 0.0
+                    rgb_in[:, K:] = 1.0
+                # codes and ones-padding of every sample in one launch
+                call("embed_a_fwd", embed_a, embed_a.shape[0], E, img_idxs, rays_a, rays_a.shape[0], rgb_in[:, 144:], Kp,
+                     Kp - 144)
+            else:
+                if E:
+                    rgb_in[:, 144:K] = embed_a
+                if Kp > K:
+                    rgb_in[:, K:] = 1.0
             if C <= 8 and x.is_cuda:
                 # the two 32-wide heads read the same rows as rgb_net: on a stream of their own their 256-thread
                 # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU (-0.03 ms/step)
@@ -380,6 +392,8 @@ class _FieldFn(Function):
 
         ctx.model = model
         ctx.E, ctx.K, ctx.Kp, ctx.C = E, K, Kp, C
+        ctx.ray_codes = ray_codes
+        ctx.codes_shape = None if ray_codes is None else tuple(embed_a.shape)
         ctx.save_for_backward(xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
                               xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dfeat)
         ctx.mark_non_differentiable(grads)
@@ -516,7 +530,15 @@ class _FieldFn(Function):
         if density_scatter is not None:
             on_side(density_scatter)
         if dfeat_rgb is not None:
-            if E and need[3]:
+            if E and need[3] and ctx.ray_codes is not None:
+                # per-image sums of the code columns, one launch: into the trainer's flat gradient when it registered the
+                # table as a sink (autograd then gets None), else into a fresh buffer handed to autograd
+                img_idxs, rays_a = ctx.ray_codes
+                acc_e = None if sinks is None else sinks.get("embedding_a")
+                if acc_e is None or tuple(acc_e.shape) != ctx.codes_shape:
+                    acc_e = g_emb = torch.zeros(ctx.codes_shape, dtype=_f32, device=dev)
+                call("embed_a_bwd", dfeat_rgb[:, 128:], W_cols, E, img_idxs, rays_a, rays_a.shape[0], ctx.codes_shape[0], acc_e)
+            elif E and need[3]:
                 g_emb = dfeat_rgb[:, 128:]
             if need[1]:
                 g_x = torch.empty(n, 3, dtype=_f32, device=dev)
@@ -556,7 +578,7 @@ class _FieldFn(Function):
             g_x = g_x / span
         if forked:
             main.wait_stream(side)
-        return (None, g_x, None, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem)
+        return (None, g_x, None, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None)
 
 
 class NGP(nn.Module):
@@ -661,17 +683,32 @@ class NGP(nn.Module):
 
     def _field(self, x, d, kwargs):
         """-> sigmas, rgbs (after rgb_net's own output activation), dsigma/dx, raw normal head, semantic logits"""
-        embed_a = None
+        embed_a = ray_codes = None
         if self.embed_a:
             embed_a = kwargs['embedding_a']
-            if embed_a.size(0) < x.size(0):
-                embed_a = torch.repeat_interleave(embed_a, int(x.size(0) / embed_a.size(0)), 0)
-            embed_a = embed_a.contiguous()
+            if isinstance(embed_a, RayCodes):
+                # the table itself enters the node (its gradient is the per-image sum); the rays' images and segments
+                # travel beside it
+                if embed_a.rays_a is None:
+                    raise ValueError("RayCodes is not bound to a ray batch: pass it to render(), which binds rays_a")
+                if embed_a.weight.shape[1] != self.rgb_net.n_input_dims - 144:
+                    raise ValueError(f"codes of length {embed_a.weight.shape[1]} for a model built with embed_a_len="
+                                     f"{self.rgb_net.n_input_dims - 144}")
+                if not x.is_cuda:
+                    raise RuntimeError("RayCodes needs CUDA tensors")
+                ray_codes = (embed_a.img_idxs, embed_a.rays_a.contiguous())
+                if getattr(embed_a.rays_a, "_ngp_full_cover", False):
+                    ray_codes[1]._ngp_full_cover = True
+                embed_a = embed_a.weight if embed_a.weight.is_contiguous() else embed_a.weight.contiguous()
+            else:
+                if embed_a.size(0) < x.size(0):
+                    embed_a = torch.repeat_interleave(embed_a, int(x.size(0) / embed_a.size(0)), 0)
+                embed_a = embed_a.contiguous()
         lin1, lin2 = self.xyz_net[0], self.xyz_net[2]
         return _FieldFn.apply(self, x.contiguous(), d.contiguous(), embed_a,
                               self.xyz_encoder.params, lin1.weight, lin1.bias, lin2.weight, lin2.bias,
                               self.rgb_encoder.params, self.rgb_net.params, self.norm_pred_header.params,
-                              self.semantic_header.params)
+                              self.semantic_header.params, ray_codes)
 
     def grad(self, x):
         """-> sigmas (N), feat_rgb (N,128), d(sigma)/dx (N,3) (detached, see module docstring).
@@ -720,6 +757,8 @@ class NGP(nn.Module):
         cols = [self.dir_encoder((dn + 1) / 2), feat_rgb]
         if self.embed_a:
             embed_a = kwargs['embedding_a']
+            if isinstance(embed_a, RayCodes):
+                embed_a = embed_a.expand()
             if embed_a.size(0) < feat_rgb.size(0):
                 embed_a = torch.repeat_interleave(embed_a, int(feat_rgb.size(0) / embed_a.size(0)), 0)
             cols.append(embed_a)

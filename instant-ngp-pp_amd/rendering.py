@@ -7,12 +7,14 @@ Test keys:  opacity, depth, rgb, normal_pred, normal_raw, semantic, total_sample
                                                                    (rendering.py:176-185)
 kwargs read: test_time, to_cpu, to_numpy, exp_step_factor, embedding_a, num_classes, max_samples,
              T_threshold, use_skybox, random_bg (+ passed through to the model).
+embedding_a: a (n_rays, E) tensor (expanded per sample here) or, at training time, appearance.RayCodes(table, img_idxs).
 """
 import torch
 import torch.nn.functional as F
 
 from . import vren
 from ._lib import call
+from .appearance import RayCodes
 from .custom_functions import RayAABBIntersector, RayMarcher, RefLoss, VolumeRenderer, mark_full_cover
 
 MAX_SAMPLES = 1024
@@ -20,6 +22,9 @@ NEAR_DISTANCE = 0.01
 
 
 def render(model, rays_o, rays_d, **kwargs):
+    if kwargs.get('test_time', False) and isinstance(kwargs.get('embedding_a'), RayCodes):
+        raise ValueError("RayCodes is the training route's embedding_a; test-time rendering takes a (1, E) tensor "
+                         "(e.g. embedding.weight[0:1], or FrameEmbedding(pose, mode='mean'))")
     rays_o = rays_o.contiguous()
     rays_d = rays_d.contiguous()
     marched = kwargs.get('marched', None)
@@ -304,10 +309,13 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     results['total_samples'] = total_samples
 
     # per-ray tensor kwargs (embedding_a, exposure, ...) are repeated per sample; like the
-    # reference this rewrites kwargs in place (rendering.py:217-219)
+    # reference this rewrites kwargs in place (rendering.py:217-219).  RayCodes (the embedding table and the rays' image
+    # indices) is not expanded here: it is handed the batch's segments and the field broadcasts it with one launch
     for k, v in kwargs.items():
         if isinstance(v, torch.Tensor):
             kwargs[k] = torch.repeat_interleave(v[rays_a[:, 0]], rays_a[:, 2], 0, output_size=xyzs.shape[0])
+        elif isinstance(v, RayCodes):
+            kwargs[k] = v.for_batch(rays_a)
     fused = kwargs.pop('_fused_loss', None)
     if fused is not None and _fused_tail_ok(model, kwargs, exp_step_factor, classes):
         return _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs)

@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import call
+from .appearance import RayCodes
 from .losses import NeRFLoss, nerf_loss_and_grads
 from .rendering import MAX_SAMPLES, MarchAhead, render
 
@@ -155,8 +156,12 @@ def shard_seed(base_seed, rank):
 class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
-                 force_sharded=None, loss_kwargs=None, msk_model=None):
-        """msk_model: an implicit_mask (the reference's embed_msk recipe, train.py:112-113, 280-299).  Its parameters join
+                 force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None):
+        """embedding_a: the nn.Embedding(n_imgs, embed_a_len) of the embed_a recipe (or a FrameEmbedding, whose table is
+        taken), for a model built with embed_a=True.  Its weight joins the flat store behind the model's parameters as
+        'embedding_a.weight' (the reference keeps it in net_opt, train.py:238-244: one Adam, one schedule, one clip), step()
+        then needs img_idxs=, and the field reads and differentiates the table through ngp_embed_a_fwd / ngp_embed_a_bwd.
+        msk_model: an implicit_mask (the reference's embed_msk recipe, train.py:112-113, 280-299).  Its parameters join
         the flat store behind the model's as 'msk_model.<key>' (one Adam, one schedule, one clip: the reference keeps it in
         net_opt), step() then needs uvi=, and the step stays on the fused render + loss tail and on the norm-bound clip.
         loss_kwargs: the flags train.py:289-300 hands to NeRFLoss (normal_ref, normal_mono, semantic,
@@ -168,6 +173,12 @@ class NGPTrainer:
         the N>1 path; None reads the environment variable NGP_FORCE_SHARDED."""
         self.model = model
         self.msk_model = msk_model
+        self.embedding_a = getattr(embedding_a, "embedding_a", embedding_a)
+        if self.embedding_a is not None:
+            E = model.rgb_net.n_input_dims - 144 if getattr(model, "embed_a", False) else 0
+            if tuple(self.embedding_a.weight.shape[1:]) != (E,):
+                raise ValueError(f"embedding_a has codes of length {tuple(self.embedding_a.weight.shape[1:])}, the model "
+                                 f"was built with embed_a={bool(E)}, embed_a_len={E}")
         self.force_sharded = bool(os.environ.get("NGP_FORCE_SHARDED")) if force_sharded is None else bool(force_sharded)
         self.base_lr = lr
         self.num_epochs = num_epochs
@@ -220,6 +231,8 @@ class NGPTrainer:
         named.sort(key=lambda np_: order.get(np_[0], 2))
         if self.msk_model is not None:   # behind the model's: in the tail whose squares are always summed exactly (_mlp_lo)
             named += [("msk_model." + n, p) for n, p in self.msk_model.named_parameters()]
+        if self.embedding_a is not None:   # likewise in that tail
+            named += [("embedding_a.weight", self.embedding_a.weight)]
         self.names = [n for n, _ in named]
         world = dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
         quantum = 4 * world   # every slice 16-byte aligned; every bucket divisible by the world size
@@ -272,6 +285,10 @@ class NGPTrainer:
             m._grad_sinks = {"W1": lin1.weight.grad, "b1": lin1.bias.grad, "W2": lin2.weight.grad, "b2": lin2.bias.grad,
                              "rgb_p": m.rgb_net.params.grad, "nrm_p": m.norm_pred_header.params.grad,
                              "sem_p": m.semantic_header.params.grad}
+        if self.embedding_a is not None:   # networks._FieldFn.backward: ngp_embed_a_bwd adds into the table's gradient
+            if not hasattr(m, "_grad_sinks"):
+                m._grad_sinks = {}
+            m._grad_sinks["embedding_a"] = self.embedding_a.weight.grad
         if self.msk_model is not None:   # implicit_mask._MaskFieldFn.backward adds into these
             k = self.msk_model
             k._grad_sinks = {"table": k.mask_encoder.params.grad, "W1": k.mask_net[0].weight.grad, "b1": k.mask_net[0].bias.grad,
@@ -322,10 +339,11 @@ class NGPTrainer:
     def lr(self):
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
-    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, **loss_kwargs):
+    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
 
         uvi: (n_rays, 3) input of the trainer's msk_model (implicit_mask.uvi), required when there is one.
+        img_idxs: (n_rays) image index of every ray, required when the trainer has an embedding_a.
 
         target: further per-ray supervision for NeRFLoss's optional terms ('normal', 'label', 'depth': the
         batch dictionary of train.py:299); loss_kwargs: per-step additions to the trainer's loss_kwargs
@@ -339,6 +357,8 @@ class NGPTrainer:
         masked = self.msk_model is not None
         if masked and uvi is None:
             raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
+        if self.embedding_a is not None and img_idxs is None:
+            raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
         self._join_grad_zeroing()
         if self.global_step % self.update_interval == 0:
             model.update_density_grid(self.density_threshold * MAX_SAMPLES / 3 ** 0.5,
@@ -372,6 +392,8 @@ class NGPTrainer:
             extra['_fused_loss'] = (rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion)
             if masked:   # size_delta of the step being taken (losses.py:60-69, 85)
                 extra['_fused_loss'] += (mask, self.loss_fn.Annealing.getWeight(self.global_step))
+        if self.embedding_a is not None:
+            extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         results = render(model, rays_o, rays_d, exp_step_factor=self.exp_step_factor,
                          num_classes=self.num_classes, marched=marched, **self.render_kwargs, **extra)
         if launch_next_late:

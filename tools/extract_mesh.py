@@ -45,6 +45,9 @@ def main(argv=None):
     ap.add_argument("--min_faces", type=int, metavar="M", help="keep only the connected pieces with at least M faces")
     ap.add_argument("--colors", action="store_true",
                     help="per-vertex RGB rendered from the trained appearance field (PLY red green blue)")
+    ap.add_argument("--embed_a", action="store_true",
+                    help="the checkpoint was trained with appearance codes (--embed_a): --colors renders with the code of training image 0")
+    ap.add_argument("--embed_a_len", type=int, default=4, help="length of an appearance code")
     ap.add_argument("--chunk", type=int, default=128 ** 3)
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
@@ -52,8 +55,14 @@ def main(argv=None):
     res = args.resolution[0] if len(args.resolution) == 1 else tuple(args.resolution)
 
     dev = torch.device("cuda", 0)
-    model = build_model(args.scale, dev)
+    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len)
     ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model'])
+    more = {}
+    if args.embed_a:
+        table = ckpt.extract_model_state_dict(args.ckpt, model_name='embedding_a')['weight']
+        if table.dim() != 2 or table.shape[1] != args.embed_a_len:
+            raise SystemExit(f"--embed_a_len {args.embed_a_len}: the checkpoint's table is {tuple(table.shape)}")
+        more["embedding_a"] = table[0:1].to(dev).float().contiguous()
     lo = args.bbox[:3] if args.bbox else model.xyz_min.reshape(3).tolist()
     hi = args.bbox[3:] if args.bbox else model.xyz_max.reshape(3).tolist()
 
@@ -75,7 +84,7 @@ def main(argv=None):
     nrm = mesh.vertex_normals(model, verts, args.chunk) if args.normals or args.colors else None
     torch.cuda.synchronize()
     t_n = time.perf_counter()
-    rgb = mesh.vertex_colors(model, verts, nrm, 2 * max(spacing)) if args.colors else None
+    rgb = mesh.vertex_colors(model, verts, nrm, 2 * max(spacing), **more) if args.colors else None
     torch.cuda.synchronize()
     t_k = time.perf_counter()
     v, f = verts.cpu(), faces.cpu()

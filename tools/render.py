@@ -13,6 +13,8 @@ render.py:150-156 does on the host; PSNR / SSIM are then those of the anti-alias
       --exp_step_factor 0.00390625 --render_traj --render_rgb --render_depth --render_normal --out_dir frames
   python tools/render.py --ckpt ckpts/lego.ckpt --root_dir /data/nerf_synthetic/lego --out_dir frames --render_rgb \\
       --anti_aliasing_factor 2
+  python tools/render.py --ckpt ckpts/tnt.ckpt --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 \\
+      --exp_step_factor 0.00390625 --render_rgb --embed_a --embed_a_len 8 --out_dir frames   # appearance codes
 """
 import argparse
 import json
@@ -50,6 +52,12 @@ def parse_args(argv=None):
     ap.add_argument("--anti_aliasing_factor", type=float, default=1.0,
                     help="render rgb / depth / normal frames on an int(H*S) x int(W*S) lattice and resize the 8-bit "
                          "frames back with Pillow's bicubic filter, on the device; 1 to 8")
+    ap.add_argument("--embed_a", action="store_true",
+                    help="the checkpoint was trained with appearance codes (--embed_a): every frame is rendered with a code picked by --embed_a_mode")
+    ap.add_argument("--embed_a_len", type=int, default=4, help="length of an appearance code")
+    ap.add_argument("--embed_a_mode", choices=("mean", "nearest", "index"), default="mean",
+                    help="code of a frame: mean of the two training cameras nearest to the frame's pose, the nearest "
+                         "one, or training image <frame number>; needs the train split's poses")
     ap.add_argument("--aa_host_check", action="store_true",
                     help="with --anti_aliasing_factor and --render_rgb: also copy the fine 8-bit rgb frame to the host, "
                          "resize it with Pillow, require equality with the device result and report host_route_s")
@@ -84,12 +92,18 @@ def main(argv=None):
     if args.dataset_name not in dataset_dict:
         raise SystemExit(f"unknown --dataset_name {args.dataset_name}; known: {sorted(dataset_dict)}")
     dev = torch.device("cuda", 0)
-    model = NGP(scale=args.scale, classes=args.num_classes).to(dev)
+    model = (NGP(scale=args.scale, classes=args.num_classes, embed_a=True, embed_a_len=args.embed_a_len) if args.embed_a
+             else NGP(scale=args.scale, classes=args.num_classes)).to(dev)
     ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model', 'density_grid', 'grid_coords'])
     test_set = dataset_dict[args.dataset_name](args.root_dir, "test", args.downsample, device=dev,
                                                render_traj=args.render_traj, num_classes=args.num_classes)
     w, h = test_set.img_wh
     directions = test_set.directions.to(dev)
+    frame_embed = None
+    if args.embed_a:   # render.py:91-93 of the reference: the table over the TRAINING poses
+        from ngp_amd.appearance import FrameEmbedding
+        train_set = dataset_dict[args.dataset_name](args.root_dir, "train", args.downsample, device=dev)
+        frame_embed = FrameEmbedding(args.embed_a_len, train_set.poses.to(dev), args.ckpt).to(dev)
     if args.render_traj:
         if getattr(test_set, "render_traj_rays", None) is None or getattr(test_set, "render_c2w", None) is None:
             raise SystemExit(f"--render_traj: the {args.dataset_name} loader found no camera path for {args.root_dir} "
@@ -118,6 +132,10 @@ def main(argv=None):
 
     for i in range(len(poses)):
         gt = test_set[i]["rgb"].to(dev) if have_gt else None      # a split kept on the host is copied outside the stages
+        if frame_embed is not None:
+            with torch.no_grad():
+                key = i % len(frame_embed.poses) if args.embed_a_mode == "index" else poses[i]
+                render_kwargs["embedding_a"] = frame_embed(key, mode=args.embed_a_mode)
         t0 = tick()
         if args.render_traj:
             rays = traj_rays[i][:, :6].to(dev)

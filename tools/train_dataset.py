@@ -8,6 +8,8 @@ reference: train.py:82-392).  GPU only.
   python tools/train_dataset.py --make_proxy /tmp/proxy --downsample 0.25 --num_epochs 2   # no dataset at hand
   python tools/train_dataset.py --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 --exp_step_factor 0.00390625 \
       --random_bg --embed_msk --save_dir out --ckpt_path out/playground.ckpt   # transient mask: out/mask_NNN.png per image
+  python tools/train_dataset.py --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 --exp_step_factor 0.00390625 \
+      --random_bg --embed_a --embed_a_len 8 --embed_msk --ckpt_path out/playground.ckpt   # the reference's Playground recipe
 """
 import argparse
 import json
@@ -20,6 +22,7 @@ sys.path.insert(0, ROOT)
 import torch
 import ngp_amd  # noqa: F401
 from ngp_amd import ckpt
+from ngp_amd.appearance import FrameEmbedding
 from ngp_amd.datasets import dataset_dict, write_synthetic_dataset
 from ngp_amd.evaluation import evaluate_split
 from ngp_amd.implicit_mask import implicit_mask
@@ -28,8 +31,8 @@ from ngp_amd.networks import NGP
 from ngp_amd.trainer import NGPTrainer
 
 
-def build_model(scale, device):
-    model = NGP(scale=scale).to(device)
+def build_model(scale, device, embed_a=False, embed_a_len=4):
+    model = (NGP(scale=scale, embed_a=True, embed_a_len=embed_a_len) if embed_a else NGP(scale=scale)).to(device)
     G = model.grid_size
     model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=device))
     coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=device)] * 3, indexing="ij"), -1)
@@ -38,12 +41,14 @@ def build_model(scale, device):
 
 
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
-          render_kwargs=None, msk_model=None):
+          render_kwargs=None, msk_model=None, embedding_a=None):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
-    mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices"""
+    mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
+    table of --embed_a, fed with the sampler's image indices"""
     train_set.batch_size = batch_size
+    more = {} if embedding_a is None else {"embedding_a": embedding_a}
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
-                         exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model)
+                         exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
     n_imgs = len(train_set.poses)
 
     def next_batch():
@@ -52,7 +57,10 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         uvi = None
         if msk_model is not None:
             uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(o.device)
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi
+        idx = None
+        if embedding_a is not None:   # one index per ray (the same_image strategy draws ONE image per batch)
+            idx = torch.as_tensor(s["img_idxs"], device=o.device).to(torch.int64).reshape(-1).expand(o.shape[0]).contiguous()
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx
 
     import gc
     gc.collect()
@@ -62,7 +70,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     t0 = time.perf_counter()
     for i in range(total):
         nxt = next_batch() if i + 1 < total else None
-        loss, res = trainer.step(*cur[:3], next_rays=None if nxt is None else nxt[:2], uvi=cur[3])
+        more = {} if cur[4] is None else {"img_idxs": cur[4]}
+        loss, res = trainer.step(*cur[:3], next_rays=None if nxt is None else nxt[:2], uvi=cur[3], **more)
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
             print(json.dumps({"step": i + 1, "loss": float(loss), "train_psnr": float(psnr(res["rgb"].detach(), cur[2])),
@@ -124,6 +133,10 @@ def main():
     ap.add_argument("--random_bg", action="store_true")
     ap.add_argument("--embed_msk", action="store_true",
                     help="train the transient mask field beside the scene (the reference's --embed_msk)")
+    ap.add_argument("--embed_a", action="store_true",
+                    help="train one appearance code per training image (the reference's --embed_a); the test split is "
+                         "evaluated with the code of image 0")
+    ap.add_argument("--embed_a_len", type=int, default=4, help="length of an appearance code, 1 to 32")
     ap.add_argument("--batch_size", type=int, default=8192)
     ap.add_argument("--num_epochs", type=int, default=20)
     ap.add_argument("--steps_per_epoch", type=int, default=1000)
@@ -131,6 +144,8 @@ def main():
     ap.add_argument("--save_dir")
     ap.add_argument("--ckpt_path")
     args = ap.parse_args()
+    if not 1 <= args.embed_a_len <= 32:
+        ap.error("--embed_a_len must lie in [1, 32]")
     dev = torch.device("cuda", 0)
     torch.manual_seed(20220806)
     root = args.root_dir
@@ -142,19 +157,24 @@ def main():
     loader = dataset_dict[args.dataset_name]
     train_set = loader(root, "train", args.downsample, device=dev)
     test_set = loader(root, "test", args.downsample, device=dev)
-    model = build_model(args.scale, dev)
+    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len)
     msk_model = implicit_mask().to(dev) if args.embed_msk else None
+    embedding_a = FrameEmbedding(args.embed_a_len, train_set.poses).to(dev) if args.embed_a else None
     t0 = time.perf_counter()
     train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
-          msk_model=msk_model)
+          msk_model=msk_model, embedding_a=embedding_a)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
+    more = {}
+    if embedding_a is not None:   # train.py:153-154: the test split is rendered with the code of training image 0
+        more["embedding_a"] = embedding_a(0).detach()
     res = evaluate_split(model, test_set, on_image=_save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None,
-                         exp_step_factor=args.exp_step_factor)
+                         exp_step_factor=args.exp_step_factor, **more)
     psnrs, ssims = res["psnr"], res["ssim"]
     if args.ckpt_path:
-        ckpt.save_ckpt(model, args.ckpt_path, msk_model=msk_model)
+        ckpt.save_ckpt(model, args.ckpt_path, msk_model=msk_model, **({} if embedding_a is None else
+                                                                      {"embedding_a": embedding_a}))
     out = {"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
            "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
            "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}
