@@ -15,12 +15,13 @@ from torch.autograd import Function
 
 from . import tinycudann as tcnn
 from ._lib import call
+from .link import FieldLink
 
 _f32 = torch.float32
 
 
 class _MaskFieldFn(Function):
-    """mask (n) = field(uvi).  Gradients: into the owner's `_grad_sinks` (a trainer's flat gradient views: the kernel
+    """mask (n) = field(uvi).  Gradients: into the owner's `link.grad_sinks` (a trainer's flat gradient views: the kernel
     accumulates straight into them and autograd gets None, as networks._FieldFn does) or, without sinks, handed to
     autograd."""
 
@@ -39,13 +40,13 @@ class _MaskFieldFn(Function):
         if not any(ctx.needs_input_grad[1:6]):
             return (None,) * 7
         owner = ctx.owner
-        sinks = getattr(owner, "_grad_sinks", None)
-        if sinks is not None:
+        sinks = owner.link.grad_sinks
+        if sinks:
             out = [sinks[k] for k in ("table", "W1", "b1", "W2", "b2")]
         else:
             out = [torch.zeros_like(t) for t in (table, W1, b1, W2)] + [torch.zeros(1, dtype=_f32, device=g.device)]
         call("mask_field_bwd", owner.mask_encoder.desc, table, W1, b1, W2, uvi, mask, g.contiguous(), uvi.shape[0], *out)
-        if sinks is not None:
+        if sinks:
             return (None,) * 7
         return (None,) + tuple(t if need else None for t, need in zip(out, ctx.needs_input_grad[1:6])) + (None,)
 
@@ -54,6 +55,7 @@ class implicit_mask(nn.Module):
     def __init__(self, latent=32, W=128):
         """both arguments are unused, as in the reference (they belong to its retired frequency-encoded variant)"""
         super().__init__()
+        self.link = FieldLink()   # a trainer's gradient sinks (link.py); empty: gradients go through autograd
         L, F, log2_T, N_min = 8, 2, 16, 16
         b = math.exp(math.log(2048 / N_min) / (L - 1))
         self.mask_encoder = tcnn.Encoding(

@@ -26,6 +26,7 @@ from . import vren
 from ._lib import call, call_host
 from .appearance import RayCodes
 from .custom_functions import TruncExp
+from .link import FieldLink
 from .rendering import NEAR_DISTANCE
 
 _f32 = torch.float32
@@ -76,38 +77,17 @@ _RELU, _NONE = 1, 0
 # widest second layer that takes the fused route (tools/mlp_bwd_microbench.py, n = 433 k, MI355X):
 # density head 0.54 -> 0.49 ms, rgb_net 0.60 -> 0.57 ms, 32-wide headers 0.22 -> 0.22 ms
 _FUSED_BWD_MAX_OUT = 3
-# Per-device default streams of the field: the colour branch of the forward (_SIDE_FWD), the backward's table scatters
-# (_SIDE) and the two 32-wide heads of the forward (_HEADS).  A model that carries its own `_side_stream` /
-# `_heads_stream` (NGPTrainer sets them) uses those instead.
-_SIDE = {}
-_SIDE_FWD = {}
+# Per-device default streams of the field, by role: "colour" (the colour branch of the forward), "scatter" (the backward's
+# table scatters) and "heads" (the two 32-wide heads of the forward).
+_STREAMS = {}
 
 
-def _fwd_stream(dev):
-    key = torch.device(dev).index
-    st = _SIDE_FWD.get(key)
-    if st is None:
-        st = _SIDE_FWD[key] = torch.cuda.Stream(device=dev)
-    return st
-
-
-_HEADS = {}
-
-
-def _heads_stream(dev):
-    key = torch.device(dev).index
-    st = _HEADS.get(key)
-    if st is None:
-        st = _HEADS[key] = torch.cuda.Stream(device=dev)
-    return st
-
-
-def _side_stream(dev):
-    key = torch.device(dev).index
-    st = _SIDE.get(key)
-    if st is None:
-        st = _SIDE[key] = torch.cuda.Stream(device=dev)
-    return st
+def _stream(role, dev, own=None):
+    """`own` (the stream a trainer put on the model's link) if there is one, else the device's default for the role"""
+    key = (role, torch.device(dev).index)
+    if own is None and key not in _STREAMS:
+        _STREAMS[key] = torch.cuda.Stream(device=dev)
+    return _STREAMS[key] if own is None else own
 
 
 class _Mlp2Bwd:
@@ -215,39 +195,6 @@ class _NegNormalize(Function):
         return dx, None
 
 
-def _wait_params(model, rgb_table=True):
-    """The trainer runs clip + Adam on a side stream in two pieces — [density table | MLPs], then
-    the colour table (77 % of the bytes) — and anything that reads parameters first waits for the
-    piece it needs: the field starts on the density path while the colour table is still being
-    updated.  rgb_table=False waits for the first piece only."""
-    # either a HIP event (single GPU: Adam on the optimizer stream) or the handle of an async
-    # all-gather of the updated parameter shards (sharded optimizer): both make the current stream
-    # wait through .wait()
-    ev = getattr(model, "_params_ready", None)
-    if ev is not None:
-        ev.wait()
-        model._params_ready = None
-    if rgb_table:
-        ev = getattr(model, "_rgb_params_ready", None)
-        if ev is not None:
-            ev.wait()
-            model._rgb_params_ready = None
-
-
-def _bound_note(model, st, slot, n_out, n):
-    """The trainer's clip decision (ngp_clip_decide) bounds a table gradient's norm by ||W1||_F ||W2||_F sum_s ||dz2[s]||:
-    accumulate the sum for the MLP whose backward `st` is (slot 0: rgb_net, 1: density head)."""
-    acc = getattr(model, "_norm_bound_acc", None)
-    if acc is None:
-        return
-    if not st.fused:
-        model._norm_bound_ok = False
-        return
-    if not st.norm_noted:      # (the elementwise stage adds the sum itself when it is handed the accumulator)
-        call("row_norm_sum", st.dz2, n_out, n, n_out, acc[slot:slot + 1])
-    model._norm_bound_hits = getattr(model, "_norm_bound_hits", 0) + 1
-
-
 def _density_fused_ok(enc, W1, b1, W2, b2):
     """whether ngp_density_field_fwd takes the density path: a 16-level F = 8 table the tile kernels take and the
     128 -> 128 -> 1 head with contiguous (W1 16-byte aligned) parameters; anything else keeps the four launches"""
@@ -287,8 +234,8 @@ class _FieldFn(Function):
         xn = (x - model.xyz_min).div_(span)   # (before the waits below: it reads no parameter and runs under the Adam sweep)
         # the two pieces of the trainer's Adam sweep (or of the sharded optimizer's all-gather): every stream below waits
         # for a piece where it first reads that piece's parameters
-        ev_p, ev_c = getattr(model, "_params_ready", None), getattr(model, "_rgb_params_ready", None)
-        model._params_ready = model._rgb_params_ready = None
+        link = model.link
+        ev_p, ev_c = link.take_param_events()
         # every buffer comes from the caller's stream (the allocator then knows them as that stream's; the colour
         # stream below only launches into them and is joined before anything is returned)
         feat = torch.empty(n, 128, dtype=_f32, device=dev)
@@ -331,9 +278,7 @@ class _FieldFn(Function):
                 # the two 32-wide heads read the same rows as rgb_net: on a stream of their own their 256-thread
                 # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU (-0.03 ms/step)
                 cur = torch.cuda.current_stream()
-                heads = getattr(model, "_heads_stream", None)
-                if heads is None:
-                    heads = _heads_stream(dev)
+                heads = _stream("heads", dev, link.heads_stream)
                 heads.wait_stream(cur)
                 with torch.cuda.stream(heads):
                     call("mlp2_fwd", feat_rgb, Kp, nrm_p, 128, None, _RELU, nrm_p[32 * 128:], 32, None, _NONE,
@@ -359,7 +304,7 @@ class _FieldFn(Function):
         # stream of its own from the moment the colour table's Adam piece is done, beside the rest of the density
         # path and the analytic normals (which are stretched beyond that piece's end on one stream).
         main = torch.cuda.current_stream()
-        side = _fwd_stream(dev) if x.is_cuda else None
+        side = _stream("colour", dev) if x.is_cuda else None
         if side is not None:
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -405,6 +350,7 @@ class _FieldFn(Function):
         (xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
          xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dsig_dfeat) = ctx.saved_tensors
         model = ctx.model
+        link = model.link
         E, K, Kp, C = ctx.E, ctx.K, ctx.Kp, ctx.C
         n = xn.shape[0]
         dev = xn.device
@@ -415,10 +361,10 @@ class _FieldFn(Function):
         # A trainer that owns the gradient storage (NGPTrainer: one flat buffer, zeroed by its Adam
         # launch) registers the MLP gradients as sinks: the weight products accumulate straight into
         # them and autograd gets None — no zeros_like fill, no AccumulateGrad add per parameter.
-        sinks = getattr(model, "_grad_sinks", None)
+        sinks = link.grad_sinks
 
         def grad_buffer(name, like):
-            t = None if sinks is None else sinks.get(name)
+            t = sinks.get(name)
             if t is not None:
                 return t, None          # (accumulate here, return nothing to autograd)
             z = torch.zeros(like, dtype=_f32, device=dev) if isinstance(like, tuple) else torch.zeros_like(like)
@@ -431,31 +377,24 @@ class _FieldFn(Function):
         # The density scatter can start at once: its input is d_sigma[s] * d(sigma)/d(features)[s], and the second
         # factor was computed (and kept) by the forward pass for the analytic normals.
         main = torch.cuda.current_stream()
-        side = getattr(model, "_side_stream", None)
-        if side is None:
-            side = _side_stream(dev)
+        side = _stream("scatter", dev, link.side_stream)
         forked = False
-        ev = getattr(model, "_acc_zeroed", None)   # the trainer clears its norm accumulators behind the Adam launches
+        ev = link.take_acc_zeroed()   # the trainer clears its norm accumulators behind the Adam launches
         if ev is not None:
             ev.wait()
-            model._acc_zeroed = None
 
         def on_side(fn):
             nonlocal forked
-            if side is None:
-                fn()
-                return
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 fn()
             forked = True
 
         def table_buffer(enc, table):
-            buf = getattr(enc, "grad_buffer", None)
-            if buf is None:
-                buf = torch.zeros_like(table)
-                return buf, buf
-            return buf, None
+            if enc.grad_buffer is not None:
+                return enc.grad_buffer, None
+            buf = torch.zeros_like(table)
+            return buf, buf
 
         reuse = d_sig is not None and not need[1]
         if reuse and need[4]:
@@ -464,13 +403,11 @@ class _FieldFn(Function):
 
             def density_scatter():
                 call("grid_bwd_param_scaled", xe.desc, xn, dsig_dfeat, 128, d_sig_c, n, buf)
-                cb = getattr(xe, "on_grad_ready", None)
-                if cb is not None:
-                    cb()
+                xe.grad_ready()
             # Data parallel: the colour table's gradient (77 % of the bytes) goes into its reduce-scatter the moment
             # its scatter is enqueued, so there the colour scatter leads on the side stream and the density scatter
             # follows it — the collective then runs under the density scatter and the weight products.
-            density_later = bool(getattr(re, "grad_ready_is_collective", False)) and d_rgb is not None and need[9]
+            density_later = re.grad_ready_is_collective and d_rgb is not None and need[9]
             # One GPU: the density scatter leads on the side stream and is let loose at once.  It becomes ready together
             # with the colour branch's data gradient, and whichever reaches the CUs first keeps them (the product takes
             # 0.15 ms when its 256 large workgroups are placed first, 0.4-0.6 ms behind the scatter's thousands of
@@ -491,7 +428,7 @@ class _FieldFn(Function):
         if d_rgb is not None:
             acc_rgbp, g_rgbp = grad_buffer("rgb_p", rgb_p)
             dfeat_rgb = torch.empty(n, W_cols, dtype=_f32, device=dev)
-            nb_acc = getattr(model, "_norm_bound_acc", None)
+            nb_acc = link.norm_acc
             st = _Mlp2Bwd(d_rgb.contiguous(), rgb_o, 3, model.rgb_net.output_activation, rgb_p[128 * Kp:], a_r, 128,
                           _RELU, 3, rgb_in, Kp, Kp, rgb_p, Kp, acc_rgbp, acc_rgbp[128 * Kp:], None, None,
                           norm_acc=None if nb_acc is None else nb_acc[0:1])
@@ -501,7 +438,7 @@ class _FieldFn(Function):
         for d_o, p, a_h, out, n_out, slot in ((d_np, nrm_p, a_n, np_o, 3, "nrm"), (d_sem, sem_p, a_s, sem_o, C, "sem")):
             if d_o is None:
                 continue
-            model._norm_bound_ok = False    # a head adds to the colour features' gradient: outside the norm bound
+            link.bound_spoiled()    # a head adds to the colour features' gradient: outside the norm bound
             acc_p, g_p = grad_buffer(slot + "_p", p)
             first = dfeat_rgb is None
             if first:
@@ -520,9 +457,7 @@ class _FieldFn(Function):
 
             def colour_scatter():
                 call("grid_bwd_param", re.desc, xn, dfeat_rgb, W_cols, n, buf_c)
-                cb = getattr(re, "on_grad_ready", None)
-                if cb is not None:
-                    cb()
+                re.grad_ready()
             if d_sig is not None:
                 on_side(colour_scatter)
             else:
@@ -534,7 +469,7 @@ class _FieldFn(Function):
                 # per-image sums of the code columns, one launch: into the trainer's flat gradient when it registered the
                 # table as a sink (autograd then gets None), else into a fresh buffer handed to autograd
                 img_idxs, rays_a = ctx.ray_codes
-                acc_e = None if sinks is None else sinks.get("embedding_a")
+                acc_e = sinks.get("embedding_a")
                 if acc_e is None or tuple(acc_e.shape) != ctx.codes_shape:
                     acc_e = g_emb = torch.zeros(ctx.codes_shape, dtype=_f32, device=dev)
                 call("embed_a_bwd", dfeat_rgb[:, 128:], W_cols, E, img_idxs, rays_a, rays_a.shape[0], ctx.codes_shape[0], acc_e)
@@ -550,7 +485,7 @@ class _FieldFn(Function):
         if d_sig is not None:
             (acc_W1, g_W1), (acc_W2, g_W2) = grad_buffer("W1", W1), grad_buffer("W2", W2)
             (acc_b1, g_b1), (acc_b2, g_b2) = grad_buffer("b1", (128,)), grad_buffer("b2", (1,))
-            nb_acc = getattr(model, "_norm_bound_acc", None)
+            nb_acc = link.norm_acc
             st = _Mlp2Bwd(d_sig.contiguous().view(n, 1), sig, 1, _SOFTPLUS, W2, a1, 128, _SOFTPLUS, 1,
                           feat, 128, 128, W1, 128, acc_W1, acc_W2, acc_b1, acc_b2,
                           norm_acc=None if nb_acc is None else nb_acc[1:2])
@@ -558,14 +493,12 @@ class _FieldFn(Function):
                 dfeat = torch.empty(n, 128, dtype=_f32, device=dev)
                 st.input_product(dfeat, 128, 128, 0, False)
             st.weight_products()
-            _bound_note(model, st, 1, 1, n)
+            link.bound_note(st, 1, 1, n)
             if not reuse:
                 if need[4]:
                     buf, g_xyz = table_buffer(xe, xyz_table)
                     call("grid_bwd_param", xe.desc, xn, dfeat, 128, n, buf)
-                    cb = getattr(xe, "on_grad_ready", None)
-                    if cb is not None:
-                        cb()
+                    xe.grad_ready()
                 if need[1]:
                     gx2 = torch.empty(n, 3, dtype=_f32, device=dev)
                     call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, gx2)
@@ -573,7 +506,7 @@ class _FieldFn(Function):
         # the norm-bound sums feed the optimizer's clip decision only: behind the weight products, where they fill the
         # wait for the scatters instead of sitting between the data gradient and the weight gradient (67 us there)
         if rgb_stage is not None:
-            _bound_note(model, rgb_stage, 0, 3, rgb_stage.n)
+            link.bound_note(rgb_stage, 0, 3, rgb_stage.n)
         if g_x is not None:
             g_x = g_x / span
         if forked:
@@ -588,6 +521,9 @@ class NGP(nn.Module):
         self.scale = scale
         self.use_skybox = use_skybox
         self.embed_a = embed_a
+        self.link = FieldLink()               # what a trainer and the field's autograd node agree on (link.py)
+        self.grid_rng = None                  # set from outside: a shared-seed generator keeps DDP ranks' grids identical
+        self.differentiable_normals = False   # True: forward() takes the reference's own formulation (module docstring)
         self.register_buffer('center', torch.zeros(1, 3))
         self.register_buffer('xyz_min', -torch.ones(1, 3) * scale)
         self.register_buffer('xyz_max', torch.ones(1, 3) * scale)
@@ -660,7 +596,7 @@ class NGP(nn.Module):
     def density(self, x, return_feat=False, grad=True, grad_feat=True):
         """x (N,3) in [-scale, scale] -> sigmas (N) [, feat_rgb (N,128)]"""
         x = ((x - self.xyz_min) / (self.xyz_max - self.xyz_min)).contiguous()
-        _wait_params(self, rgb_table=return_feat)
+        self.link.wait_params(rgb_table=return_feat)
         if not (grad and torch.is_grad_enabled()):
             # inference (update_density_grid runs this on 1-2 M points): three launches, no graph
             with torch.no_grad():
@@ -745,7 +681,7 @@ class NGP(nn.Module):
         torch.autograd.grad(create_graph=True), so that normals_raw carries gradients back into the
         density table and MLP (H4, needed by --normal_ref).  The grid's double backward runs on
         ngp_grid_bwd_bwd_input; the 17 k-parameter density MLP uses torch ops here."""
-        _wait_params(self)
+        self.link.wait_params()
         x = x.detach().clone().requires_grad_(True)
         xn = (x - self.xyz_min) / (self.xyz_max - self.xyz_min)
         with torch.enable_grad():
@@ -767,7 +703,7 @@ class NGP(nn.Module):
 
     def forward(self, x, d, **kwargs):
         """x, d (N,3) -> sigmas (N), rgbs (N,3), normals_raw (N,3), normals_pred (N,3), semantic (N,C)"""
-        if getattr(self, 'differentiable_normals', False) and torch.is_grad_enabled():
+        if self.differentiable_normals and torch.is_grad_enabled():
             sigmas, rgbs, grads, np_raw, sem_logits = self._forward_differentiable_normals(x, d, kwargs)
             normals_raw = -F.normalize(grads, p=2, dim=-1, eps=1e-6)
         else:
@@ -814,7 +750,7 @@ class NGP(nn.Module):
     def sample_uniform_and_occupied_cells(self, M, density_threshold):
         cells = []
         for c in range(self.cascades):
-            gen = getattr(self, 'grid_rng', None)  # shared-seed generator keeps DDP ranks' grids identical
+            gen = self.grid_rng  # shared-seed generator keeps DDP ranks' grids identical
             coords1 = torch.randint(self.grid_size, (M, 3), dtype=torch.int32, device=self.density_grid.device,
                                     generator=gen)
             indices1 = vren.morton3D(coords1).long()
@@ -882,7 +818,7 @@ class NGP(nn.Module):
                                   torch.empty(2 * M, dtype=torch.int32, device=dev),
                                   torch.empty(2 * M, 3, dtype=_f32, device=dev),
                                   torch.empty(1024, dtype=_f32, device=dev), torch.empty(2, dtype=_f32, device=dev))
-            gen = getattr(self, 'grid_rng', None)
+            gen = self.grid_rng
             self._grid_seed = int(gen.initial_seed() if gen is not None else torch.initial_seed()) & 0x7FFFFFFFFFFF
             self._grid_updates = 0
         work, indices, xyzs_w, partials, thr = ws
@@ -912,7 +848,7 @@ class NGP(nn.Module):
             indices, coords = cells[c]
             s = min(2 ** (c - 1), self.scale)
             noise = torch.rand(coords.shape[0], 3, dtype=_f32, device=coords.device,
-                               generator=getattr(self, 'grid_rng', None))
+                               generator=self.grid_rng)
             xyzs_w = torch.empty(coords.shape[0], 3, dtype=_f32, device=coords.device)
             call("grid_cell_points", coords.contiguous(), noise, coords.shape[0], self.grid_size, float(s), xyzs_w)
             density_grid_tmp[c, indices] = self.density(xyzs_w)

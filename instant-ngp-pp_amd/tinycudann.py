@@ -46,7 +46,7 @@ class _GridFwd(Function):
         if ctx.needs_input_grad[0]:
             dx = _GridBwdInput.apply(dy, x, params, enc)
         if ctx.needs_input_grad[1]:
-            buf = getattr(enc, "grad_buffer", None)
+            buf = enc.grad_buffer
             if buf is not None:
                 # trainer-owned flat gradient: scatter-add straight into it (autograd sees None)
                 call("grid_bwd_param", enc.desc, x, dy, enc.n_output_dims, x.shape[0], buf)
@@ -54,9 +54,7 @@ class _GridFwd(Function):
             else:
                 dparams = torch.zeros_like(params)
                 call("grid_bwd_param", enc.desc, x, dy, enc.n_output_dims, x.shape[0], dparams)
-            cb = getattr(enc, "on_grad_ready", None)
-            if cb is not None:
-                cb()
+            enc.grad_ready()
         return dx, dparams, None
 
 
@@ -111,6 +109,12 @@ class Encoding(nn.Module):
         self.encoding_config = dict(encoding_config)
         ot = encoding_config["otype"]
         self.otype = ot
+        # A trainer's side of a hash table (NGPTrainer fills it, _GridFwd and networks._FieldFn read it).  grad_buffer: its
+        # view of the table's gradient (the scatter adds into it, autograd gets None); on_grad_ready(): called behind the
+        # scatter, and whether it issues a collective; _bound_valid: no scatter outside its norm bound added to grad_buffer
+        self.grad_buffer = self.on_grad_ready = None
+        self.grad_ready_is_collective = False
+        self._bound_valid = True
         if ot in ("Grid", "HashGrid", "DenseGrid"):
             if n_input_dims != 3:
                 raise ValueError("grid encoding: only 3-D inputs are supported")
@@ -144,6 +148,10 @@ class Encoding(nn.Module):
             self.params = nn.Parameter(torch.zeros(0, dtype=_f32))
         else:
             raise ValueError(f"unsupported encoding otype {ot}")
+
+    def grad_ready(self):   # the table's scatter has just been enqueued on the current stream
+        if self.on_grad_ready is not None:
+            self.on_grad_ready()
 
     def forward(self, x):
         if not x.is_cuda:

@@ -213,16 +213,7 @@ class NGPTrainer:
         self._flatten()
         self._opt_stream = torch.cuda.Stream(device=self.flat_param.device) if self.flat_param.is_cuda else None
         self._march_ahead = MarchAhead(self.flat_param.device) if self.flat_param.is_cuda else None
-        if self.flat_param.is_cuda and not self.sharded:
-            # Four streams, one per hardware queue of the HIP runtime's default pool: the caller's, the colour forward's, the
-            # optimizer's and the march-ahead's.  The backward's table scatters of THIS trainer's model go on the optimizer
-            # stream (clip + Adam follow them there anyway) and its two heads on the march-ahead stream (idle in the middle of
-            # the forward) instead of streams of their own: with six streams two pairs share a queue, and which pairs depends
-            # on the order the streams were created in — the scatter behind the caller's MLP kernels would cost 0.4 ms per
-            # step.  Same speed as the six-stream layout that happened to come out right (profiles/r03_occupancy_shaping.txt
-            # (12)).
-            model._side_stream = self._opt_stream
-            model._heads_stream = self._march_ahead.stream
+        self._link_field()
 
     # ------------------------------------------------------------------ flat parameter store
     def _flatten(self):
@@ -277,37 +268,6 @@ class NGPTrainer:
         else:
             self.exp_avg = torch.zeros(total, dtype=_f32, device=dev)
             self.exp_avg_sq = torch.zeros(total, dtype=_f32, device=dev)
-        # the field's weight products accumulate straight into these views of the flat gradient
-        # (networks._FieldFn.backward); autograd then has nothing to add for them
-        m = self.model
-        if hasattr(m, "xyz_net") and hasattr(m, "rgb_net"):
-            lin1, lin2 = m.xyz_net[0], m.xyz_net[2]
-            m._grad_sinks = {"W1": lin1.weight.grad, "b1": lin1.bias.grad, "W2": lin2.weight.grad, "b2": lin2.bias.grad,
-                             "rgb_p": m.rgb_net.params.grad, "nrm_p": m.norm_pred_header.params.grad,
-                             "sem_p": m.semantic_header.params.grad}
-        if self.embedding_a is not None:   # networks._FieldFn.backward: ngp_embed_a_bwd adds into the table's gradient
-            if not hasattr(m, "_grad_sinks"):
-                m._grad_sinks = {}
-            m._grad_sinks["embedding_a"] = self.embedding_a.weight.grad
-        if self.msk_model is not None:   # implicit_mask._MaskFieldFn.backward adds into these
-            k = self.msk_model
-            k._grad_sinks = {"table": k.mask_encoder.params.grad, "W1": k.mask_net[0].weight.grad, "b1": k.mask_net[0].bias.grad,
-                             "W2": k.mask_net[2].weight.grad, "b2": k.mask_net[2].bias.grad}
-        # scatter kernels accumulate directly into the flat gradient (see tinycudann._GridFwd)
-        for enc_name in ("rgb_encoder", "xyz_encoder"):
-            enc = getattr(self.model, enc_name, None)
-            if enc is not None:
-                enc.grad_buffer = enc.params.grad
-        # bucket 0's reduce-scatter is fired from the colour encoder's backward (overlaps the rest)
-        self.hooked0 = bool(hasattr(self.model, "rgb_encoder") and self.sharded and b0)
-        if self.hooked0:
-            self.model.rgb_encoder.on_grad_ready = lambda: self.buckets.reduce_scatter_bucket(0, self.grad_shard[0])
-            self.model.rgb_encoder.grad_ready_is_collective = True   # the field's backward then scatters colour first
-        elif hasattr(self.model, "rgb_encoder") and b0 and dev.type == "cuda" and not self.sharded:
-            # one GPU: the colour table's share of the gradient norm (77 % of the entries) is summed
-            # right behind its scatter, beside the density head's backward, instead of on the path
-            # between the last scatter and Adam
-            self.model.rgb_encoder.on_grad_ready = self._early_norm_share
         # first element behind the two tables (the MLP parameters): their share of the norm is always summed exactly
         self._mlp_lo = 0
         if self.names[:2] == ["rgb_encoder.params", "xyz_encoder.params"] and len(self.names) > 2:
@@ -316,6 +276,41 @@ class NGPTrainer:
         self._bound_step = False
         self._norm_share_armed = False   # step() arms it: exactly one backward per optimizer step
         self._norm_share_fired = 0
+
+    def _link_field(self):
+        """everything the field does on this trainer's behalf: the model's and the mask model's FieldLink (link.py) and the
+        two encoders' per-table slots (tinycudann.Encoding)"""
+        m, link = self.model, self.model.link
+        # the backwards of the field, the appearance codes and the mask field add straight into these views of the flat gradient
+        lin1, lin2 = m.xyz_net[0], m.xyz_net[2]
+        sinks = {"W1": lin1.weight, "b1": lin1.bias, "W2": lin2.weight, "b2": lin2.bias, "rgb_p": m.rgb_net.params,
+                 "nrm_p": m.norm_pred_header.params, "sem_p": m.semantic_header.params}
+        if self.embedding_a is not None:
+            sinks["embedding_a"] = self.embedding_a.weight
+        link.grad_sinks = {name: p.grad for name, p in sinks.items()}
+        if self.msk_model is not None:
+            k, (l1, l2) = self.msk_model, (self.msk_model.mask_net[0], self.msk_model.mask_net[2])
+            k.link.grad_sinks = {"table": k.mask_encoder.params.grad, "W1": l1.weight.grad, "b1": l1.bias.grad,
+                                 "W2": l2.weight.grad, "b2": l2.bias.grad}
+        if self.flat_param.is_cuda and not self.sharded:
+            # Four streams, one per hardware queue of the HIP runtime's default pool (DESIGN.md section 5,
+            # profiles/r03_occupancy_shaping.txt (12)): the backward's table scatters of THIS trainer's model go on the optimizer
+            # stream (clip + Adam follow them there anyway) and its two heads on the march-ahead stream (idle in the middle of
+            # the forward) instead of streams of their own, which would share queues by the accident of creation order.
+            link.side_stream, link.heads_stream = self._opt_stream, self._march_ahead.stream
+        # the scatter kernels accumulate directly into the flat gradient (networks._FieldFn, tinycudann._GridFwd)
+        for enc in (m.rgb_encoder, m.xyz_encoder):
+            enc.grad_buffer = enc.params.grad
+        b0 = self.buckets.bounds[1] if len(self.buckets.bounds) > 2 else 0
+        # bucket 0's reduce-scatter is fired from the colour encoder's backward (overlaps the rest)
+        self.hooked0 = bool(self.sharded and b0)
+        if self.hooked0:
+            m.rgb_encoder.on_grad_ready = lambda: self.buckets.reduce_scatter_bucket(0, self.grad_shard[0])
+            m.rgb_encoder.grad_ready_is_collective = True   # the field's backward then scatters colour first
+        elif b0 and self.flat_param.is_cuda:
+            # one GPU: the colour table's share of the gradient norm (77 % of the entries) is summed right behind its
+            # scatter, beside the density head's backward, instead of on the path between the last scatter and Adam
+            m.rgb_encoder.on_grad_ready = self._early_norm_share
 
     def _unit_seed(self, terms):
         s = getattr(self, '_seed4', None)
@@ -383,9 +378,7 @@ class NGPTrainer:
         extra = {}
         mask = None
         if masked:
-            ev = getattr(model, "_params_ready", None)   # the mask parameters sit in the Adam sweep's first piece
-            if ev is not None:
-                ev.wait()                                # (left in place: the field waits for it as well)
+            model.link.join_params(rgb_table=False)   # the mask parameters sit in the Adam sweep's first piece
             mask = self.msk_model(uvi)
         if default_recipe and rays_o.is_cuda:
             # render + loss + the loss's gradients as one launch behind the field (rendering._RenderLossFn)
@@ -401,17 +394,15 @@ class NGPTrainer:
         self._norm_share_armed, self._norm_share_fired = True, 0   # one backward follows, then the optimizer step
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
         # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
-        self._bound_step = bool(self.norm_bound and self.fused_loss and not loss_kwargs and not target
-                                and not getattr(model, "differentiable_normals", False))
-        model._norm_bound_acc = self.norm_acc if self._bound_step else None
-        model._norm_bound_hits, model._norm_bound_ok = 0, True
+        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals)
+        model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]
             torch.autograd.backward([terms], [self._unit_seed(terms)])
-        elif self.fused_loss and not loss_kwargs and not target and not masked:
+        elif default_recipe and not masked:
             # same value and gradients as sum(term.mean()) over NeRFLoss's default terms; the
             # gradients are seeded directly (no loss node, no multiplications by 1)
             terms, (d_rgb, d_op, d_ws) = nerf_loss_and_grads(
@@ -476,7 +467,7 @@ class NGPTrainer:
         lr = self.lr_at(min((self.global_step - 1) // self.steps_per_epoch, self.num_epochs))
         if not self.sharded:
             # clip + Adam stream 6.4 GB and touch no ray data: they run on the optimizer stream, the
-            # field waits on `_params_ready` / `_rgb_params_ready` where it first reads the respective
+            # field waits on its link's `params_ready` / `rgb_params_ready` where it first reads the respective
             # parameters (the ray-only front of the next step is on MarchAhead's stream anyway).
             n = self.flat_grad.numel()
             main = torch.cuda.current_stream()
@@ -485,11 +476,11 @@ class NGPTrainer:
             b0 = self.buckets.bounds[1] if len(self.buckets.bounds) > 2 else 0
             early = self._norm_share_armed and self._norm_share_fired == 1   # scalars[0] holds the colour table's share
             self._norm_share_armed, self._norm_share_fired = False, 0
-            m = self.model
-            bounded = bool(self._bound_step and getattr(m, "_norm_bound_hits", 0) == 2 and getattr(m, "_norm_bound_ok", False)
+            m, link = self.model, self.model.link
+            bounded = bool(self._bound_step and link.hits == 2 and link.ok
                            and m.rgb_encoder._bound_valid and m.xyz_encoder._bound_valid)
             self._bound_step = False
-            m._norm_bound_acc = None
+            link.norm_acc = None
             zero_after = False
             with torch.cuda.stream(side):
                 if bounded:
@@ -531,8 +522,8 @@ class NGPTrainer:
                     # the next backward adds into both: it waits for this event (networks._FieldFn.backward)
                     ev = torch.cuda.Event()
                     ev.record(side)
-                    self.model._acc_zeroed = ev
-            self.model._params_ready, self.model._rgb_params_ready = events[b0], events[0]
+                    link.acc_zeroed = ev
+            link.params_ready, link.rgb_params_ready = events[b0], events[0]
             return
         self.scalars.zero_()
         # sharded: bucket 0's reduce-scatter was issued from the colour encoder's backward
@@ -574,11 +565,7 @@ class NGPTrainer:
             call("adam_step", self.param_shard[i], self.grad_shard[i], self.exp_avg[i], self.exp_avg_sq[i],
                  self.grad_shard[i].numel(), float(lr), 0.9, 0.999, 1e-8, 0.0, self.global_step, self.scalars[1:2], 0)
             works[i] = self.buckets.all_gather_bucket(i, self.flat_param, self.param_shard[i], detach=True)
-        if nb == 2:
-            self.model._params_ready, self.model._rgb_params_ready = works[1], works[0]
-        else:
-            self.model._params_ready = works[0]
-
+        self.model.link.params_ready, self.model.link.rgb_params_ready = works[nb - 1], (works[0] if nb == 2 else None)
 
     def _join_grad_zeroing(self):
         ev, self._grad_zeroed = self._grad_zeroed, None
@@ -589,10 +576,7 @@ class NGPTrainer:
         """make the current stream wait for a pending side-stream optimizer step (call before reading
         parameters / gradients outside the model's own forward)"""
         self._join_grad_zeroing()
-        for name in ("_params_ready", "_rgb_params_ready"):
-            ev = getattr(self.model, name, None)
-            if ev is not None:
-                ev.wait()
+        self.model.link.join_params()
 
     # ------------------------------------------------------------------ parameter store <-> shards
     def sync_shards(self):

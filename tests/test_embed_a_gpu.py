@@ -265,7 +265,7 @@ def test_trainer_owns_the_table(ngp):
     assert numel == 160 and off >= tr._mlp_lo
     assert emb.weight.data_ptr() == tr.flat_param[off:].data_ptr()
     assert emb.weight.grad.data_ptr() == tr.flat_grad[off:].data_ptr()
-    assert tr.model._grad_sinks["embedding_a"].data_ptr() == tr.flat_grad[off:].data_ptr()
+    assert tr.model.link.grad_sinks["embedding_a"].data_ptr() == tr.flat_grad[off:].data_ptr()
     assert tr.fused_loss is True and tr.norm_bound is True
     assert np.isfinite(losses).all()
     assert torch.isfinite(tr.flat_param).all()

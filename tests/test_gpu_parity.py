@@ -1317,6 +1317,99 @@ def test_trainer_streams_belong_to_its_model(ngp, monkeypatch):
     assert not {tr_b._opt_stream.cuda_stream, tr_b._march_ahead.stream.cuda_stream} & {st for _, st in launches}
 
 
+def _lego_batch(n_rays=1024, seed=5):
+    from ngp_amd.synthetic import LegoProxy
+    scene = LegoProxy(n_images=20, img_wh=(200, 200), device=DEV)
+    img, pix = scene.sample_batch(n_rays, generator=torch.Generator(device=DEV).manual_seed(seed))
+    o, d = scene.rays(img, pix)
+    gt, _ = scene.ground_truth(o, d, n_quad=64)
+    return o, d, gt
+
+
+def test_trainer_parameter_events_live_on_the_link(ngp):
+    """The two pieces of the Adam sweep as the field and the trainer share them through model.link: a step leaves both
+    events pending, NGPTrainer.wait() waits without clearing them, density() alone takes the MLP piece and leaves the
+    colour table's, the next step's forward takes both before its optimizer step posts new ones; the norm accumulator is on
+    the link during a bound step's backward only, and the steps do stay on the bound route."""
+    from ngp_amd.trainer import NGPTrainer
+    model = _grid_model(ngp, seed=3)
+    tr = NGPTrainer(model, lr=1e-2)
+    link = model.link
+    assert tr.norm_bound and link.side_stream is tr._opt_stream and link.heads_stream is tr._march_ahead.stream
+    o, d, gt = _lego_batch()
+    tr.step(o, d, gt)
+    p, c = link.params_ready, link.rgb_params_ready
+    assert p is not None and c is not None and p is not c
+    tr.wait()
+    assert link.params_ready is p and link.rgb_params_ready is c
+    x = (torch.rand(64, 3, device=DEV) - 0.5) * 0.9
+    assert torch.isfinite(model.density(x, grad=False)).all()
+    assert link.params_ready is None and link.rgb_params_ready is c
+    seen = {}
+    optimizer_step = tr.optimizer_step
+
+    def spy():
+        seen["events"] = (link.params_ready, link.rgb_params_ready)
+        seen["bound"] = (tr._bound_step, link.norm_acc is tr.norm_acc, link.hits, link.ok)
+        optimizer_step()
+    tr.optimizer_step = spy
+    tr.step(o, d, gt)
+    assert seen["events"] == (None, None)                     # the forward took both ...
+    assert link.params_ready is not None and link.rgb_params_ready is not None      # ... and these are the new ones
+    assert link.params_ready is not p and link.rgb_params_ready is not c
+    assert seen["bound"] == (True, True, 2, True) and link.norm_acc is None
+    tr.wait()
+    torch.cuda.synchronize()
+    assert int(tr.need_exact) == 0 and bool(torch.isfinite(tr.scalars[1])) and torch.isfinite(tr.flat_param).all()
+
+
+def _record_step_launches(networks, monkeypatch, tr, step):
+    """-> [(kernel name, stream role, arguments)] of the launches networks.py makes during step(); the role is one of
+    caller, colour-forward, optimizer, march-ahead (any other stream fails)"""
+    launches = []
+    real_call = networks.call
+
+    def recording_call(name, *args):
+        launches.append((name, torch.cuda.current_stream().cuda_stream, args))
+        return real_call(name, *args)
+    caller = torch.cuda.current_stream().cuda_stream
+    with monkeypatch.context() as mp:
+        mp.setattr(networks, "call", recording_call)
+        step()
+    roles = {caller: "caller", networks._stream("colour", DEV).cuda_stream: "colour-forward",
+             tr._opt_stream.cuda_stream: "optimizer", tr._march_ahead.stream.cuda_stream: "march-ahead"}
+    assert len(roles) == 4 and {st for _, st, _ in launches} <= set(roles)
+    return [(name, roles[st], args) for name, st, args in launches]
+
+
+def test_trainer_step_launch_order_and_streams(ngp, monkeypatch):
+    """One steady-state step of the one-GPU trainer, as the list of (kernel, stream role) networks.py launches: both table
+    scatters on the optimizer stream with the density table's (grid_bwd_param_scaled) leading, the colour table's gather on
+    the colour-forward stream, the two 32-wide heads on the march-ahead stream."""
+    from ngp_amd import networks
+    from ngp_amd.trainer import NGPTrainer
+    model = _grid_model(ngp, seed=3)
+    tr = NGPTrainer(model, lr=1e-2)
+    o, d, gt = _lego_batch()
+    tr.step(o, d, gt)                                          # (the step with the all-cells occupancy update)
+    rec = _record_step_launches(networks, monkeypatch, tr, lambda: tr.step(o, d, gt))
+    tr.wait()
+    torch.cuda.synchronize()
+    assert torch.isfinite(tr.flat_param).all()
+    names = [name for name, _, _ in rec]
+    scatters = [(name, role) for name, role, _ in rec if name.startswith("grid_bwd_param")]
+    assert scatters == [("grid_bwd_param_scaled", "optimizer"), ("grid_bwd_param", "optimizer")]
+    assert names.index("grid_bwd_param_scaled") < names.index("grid_bwd_param")
+    colour_table = model.rgb_encoder.params.data_ptr()
+    gathers = [role for name, role, args in rec if name == "grid_fwd" and args[1].data_ptr() == colour_table]
+    assert gathers == ["colour-forward"]
+    heads = [role for name, role, args in rec if name == "mlp2_fwd" and args[12] == 32]
+    assert heads == ["march-ahead", "march-ahead"]
+    # the rest of the forward: the density path on the caller's stream, rgb_net on the colour-forward stream
+    assert [role for name, role, _ in rec if name == "density_field_fwd"] == ["caller"]
+    assert [role for name, role, args in rec if name == "mlp2_fwd" and args[12] == 128] == ["colour-forward"]
+
+
 def test_trainer_march_ahead_matches_inline(ngp):
     """Marching batch k+1 on the side stream under step k (MarchAhead) gives the same training run
     as marching every batch inside its own step: identical sample counts (the marcher is
