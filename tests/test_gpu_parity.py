@@ -172,6 +172,13 @@ def test_raymarching_test_bit_exact(ngp, case):
 
 # ---------------------------------------------------------------------------- V1 / V2 / V3 / D1
 def _composite_inputs(n_rays, max_len, classes, seed, sigma_scale=30.0):
+    if n_rays == "crafted":
+        # one ray per (length, stop sample) case on both sides of the 32-sample chunk edges, rows and ray indices
+        # permuted, a gap between two segments (tests/fused_tail_reference.py:make_crafted); no ray is borderline
+        import fused_tail_reference
+        x = fused_tail_reference.make_crafted(0)
+        return (x["rays_a"], x["n"], x["sig"], x["deltas"], x["ts"], x["rgbs"], x["nrm"],
+                np.ascontiguousarray(x["sem"][:, :classes]))
     g = rng(seed)
     rays_a, n = make_segments(n_rays, max_len, seed=seed + 1)
     # shuffle rows: the kernels must honour ray_idx, not the row number
@@ -191,9 +198,10 @@ def _composite_inputs(n_rays, max_len, classes, seed, sigma_scale=30.0):
 
 @pytest.mark.parametrize("n_rays,max_len,classes,T_thr", [
     (1, 1, 7, 1e-4), (700, 40, 7, 1e-4), (300, 700, 7, 1e-4), (200, 90, 0, 1e-2), (150, 64, 10, 0.0),
-    (64, 33, 40, 1e-4)])
+    (64, 33, 40, 1e-4), ("crafted", 200, 7, 1e-4), ("crafted", 200, 7, 1e-2)])
 def test_composite_train_fw_bw(ngp, n_rays, max_len, classes, T_thr):
     rays_a, n, sig, deltas, ts, rgbs, nrm, sems = _composite_inputs(n_rays, max_len, classes, seed=50 + max_len)
+    n_rays = len(rays_a)
     ok = ~borderline_rays(sig, deltas, rays_a, T_thr)
     out = ngp.vren.composite_train_fw(T(sig), T(rgbs), T(nrm), T(sems), T(deltas), T(ts), T(rays_a), T_thr, classes)
     ref = oracle.composite_train_fw(sig, rgbs, nrm, sems, deltas, ts, rays_a, T_thr, classes)
@@ -237,7 +245,15 @@ def test_composite_alpha_fw(ngp):
 
 
 def test_refloss_fw_bw(ngp):
-    rays_a, n, sig, deltas, ts, rgbs, nrm, _ = _composite_inputs(500, 60, 0, seed=80)
+    _refloss_fw_bw(ngp, 500)
+
+
+def test_refloss_fw_bw_crafted_edges(ngp):
+    _refloss_fw_bw(ngp, "crafted")
+
+
+def _refloss_fw_bw(ngp, n_rays):
+    rays_a, n, sig, deltas, ts, rgbs, nrm, _ = _composite_inputs(n_rays, 60, 0, seed=80)
     ok = ~borderline_rays(sig, deltas, rays_a, 1e-4)
     ndiff = (rgbs ** 2).astype(np.float32)
     nori = np.abs(nrm[:, 0]).astype(np.float32)
@@ -259,9 +275,10 @@ def test_refloss_fw_bw(ngp):
         close(N(a)[smask], b[smask], 2e-4, 2e-5)
 
 
-@pytest.mark.parametrize("n_rays,max_len", [(600, 40), (100, 900), (5, 1)])
+@pytest.mark.parametrize("n_rays,max_len", [(600, 40), (100, 900), (5, 1), ("crafted", 200)])
 def test_distortion_loss_fw_bw(ngp, n_rays, max_len):
     rays_a, n, sig, deltas, ts, *_ = _composite_inputs(n_rays, max_len, 0, seed=90 + max_len)
+    n_rays = len(rays_a)
     ws = oracle.composite_train_fw(sig, np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32),
                                    np.zeros((n, 0), np.float32), deltas, ts, rays_a, 1e-4, 0)[6]
     loss, wi, wti = ngp.vren.distortion_loss_fw(T(ws), T(deltas), T(ts), T(rays_a))
