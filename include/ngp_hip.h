@@ -384,6 +384,37 @@ int ngp_embed_a_bwd(const float* dL_dcols, int64_t ld, int E, const int64_t* img
                     int64_t n_rays, int64_t n_imgs, float* d_weight, void* stream);
 
 /* ------------------------------------------------------------------------
+ * P1  camera pose refinement (optimize_ext: train.py:143-149, 225-230; datasets/ray_utils.py:50-104): the rays of a
+ * batch from per-image corrections, and the adjoint of that map reduced per image.  One launch each way.
+ * poses (n_imgs, 3, 4) camera-to-world [Rp | t]; dR (n_imgs, 3) axis-angle, dT (n_imgs, 3); directions (n_pix, 3) camera
+ * space; img_idxs, pix_idxs (n_rays) i64.
+ * fwd (a lane per ray): with v = dR[img], theta = |v| + 1e-7, K = skew(v):
+ *     Rd = (I + sin(theta)/theta K) + (1 - cos(theta))/theta^2 K^2,  R' = Rd Rp,
+ *     rays_d[r][i] = (R'_i0 dir_0 + R'_i1 dir_1) + R'_i2 dir_2,  rays_o[r] = t + dT[img]
+ *   in float32 without FMA contraction (1 - cos(theta) formed as 2 sin^2(theta / 2)).  At dR = dT = 0 the rays are bit for
+ *   bit get_rays' fixed-order products.
+ * bwd (a wave per chunk of consecutive rays_a rows): g_x (n, 3) and g_dir (n, 3) or NULL are the gradients of the loss
+ *   w.r.t. the sample positions x_s = o + t_s d and the sample directions dir_s = d; ts (n); rays_a (n_rays, 3) i64 = (ray
+ *   index, first sample, sample count).  Per row, g_o = sum_s g_x[s] and g_d = sum_s (g_x[s] ts[s] + g_dir[s])
+ *   (RayMarcher.backward, custom_functions.py:104-114), then through R' = Rd(v) Rp to v.  g_dR, g_dT (n_imgs, 3) are
+ *   ACCUMULATED into (+=, float atomics, consecutive rows of one image merged first; the caller zeroes); the term that
+ *   goes through |v| is exactly 0 at v = 0, as torch's norm backward is.
+ * An image, pixel, ray or sample index outside its range is never used as an address: forward such a ray is zero, backward
+ * it (or the sample) contributes nothing.  Rows of images that no ray names are not touched.  n_rays == 0 (bwd: or
+ * n == 0) returns NGP_OK before any pointer is looked at.
+ * ---------------------------------------------------------------------- */
+int ngp_pose_rays_fwd(const float* poses, const float* dR, const float* dT, const float* directions,
+                      const int64_t* img_idxs, const int64_t* pix_idxs, int64_t n_imgs, int64_t n_pix, int64_t n_rays,
+                      float* rays_o, float* rays_d, void* stream);
+int ngp_pose_rays_bwd(const float* g_x, const float* g_dir, const float* ts, const int64_t* rays_a, const float* poses,
+                      const float* dR, const float* directions, const int64_t* img_idxs, const int64_t* pix_idxs,
+                      int64_t n_imgs, int64_t n_pix, int64_t n_rays, int64_t n, float* g_dR, float* g_dT, void* stream);
+
+/* adjoint of ngp_sh_fwd_dirs at degree 4: dL_dd (n, 3) from dL_dy (n rows of 16, row stride lddy >= 16 floats) through
+ * the basis, the [0,1] remap and F.normalize(eps = 1e-6) (under the clamp: g / eps) */
+int ngp_sh_bwd_dirs(const float* d, const float* dL_dy, int64_t lddy, int64_t n, float* dL_dd, void* stream);
+
+/* ------------------------------------------------------------------------
  * H5  spherical harmonics (tcnn.Encoding otype SphericalHarmonics, degree 1..4,
  * networks.py:78-85,128-135).  x (n,3) in [0,1] -> y (n, degree^2).
  * ---------------------------------------------------------------------- */

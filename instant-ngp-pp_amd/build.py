@@ -26,6 +26,7 @@ SOURCES = [
     ("mlp_kernels.hip", []),
     ("mask_kernels.hip", []),
     ("embed_kernels.hip", []),
+    ("pose_kernels.hip", ["-ffp-contract=off"]),    # at dR = dT = 0 the rays are bit-identical to get_rays' products
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),
     ("image_kernels.hip", ["-ffp-contract=off"]),   # frame packing is bit-identical to its numpy restatement

@@ -39,19 +39,40 @@ def load_ckpt(model, ckpt_path, model_name='model', prefixes_to_ignore=()):
             own[k].copy_(v.to(own[k].device))
 
 
-def save_ckpt(model, path, extra=None, msk_model=None, embedding_a=None):
+def save_ckpt(model, path, extra=None, msk_model=None, embedding_a=None, pose_refiner=None):
     """writes {'state_dict': {'model.<key>': ...}} like Lightning's ModelCheckpoint(save_weights_only); the transient
     mask model of the embed_msk recipe goes beside it under 'msk_model.<key>' (train.py:112-113, 236) and the appearance
-    table of the embed_a recipe (an nn.Embedding, or a FrameEmbedding's) as 'embedding_a.weight' (train.py:104-108)"""
+    table of the embed_a recipe (an nn.Embedding, or a FrameEmbedding's) as 'embedding_a.weight' (train.py:104-108); the
+    pose corrections of the optimize_ext recipe (a pose.PoseRefiner) as 'dR', 'dT' and 'poses' at the top level, the keys
+    Lightning gives the reference's system (train.py:222-230) and slim_ckpt(save_poses=True) keeps"""
     sd = {f"model.{k}": v.detach().cpu() for k, v in model.state_dict().items()}
     if msk_model is not None:
         sd.update({f"msk_model.{k}": v.detach().cpu() for k, v in msk_model.state_dict().items()})
     if embedding_a is not None:    # (behind the mask model: the order in which train.py registers the three)
         embedding_a = getattr(embedding_a, "embedding_a", embedding_a)
         sd.update({f"embedding_a.{k}": v.detach().cpu().clone() for k, v in embedding_a.state_dict().items()})
+    if pose_refiner is not None:
+        sd.update({k: v.detach().cpu().clone() for k, v in pose_refiner.state_dict().items()})
     if extra:
         sd.update(extra)
     torch.save({'state_dict': sd}, path)
+
+
+def load_poses(pose_refiner, ckpt_path):
+    """in-place update of a pose.PoseRefiner from the top-level 'dR', 'dT' and 'poses' of a checkpoint (values are copied:
+    a trainer's pose buffer stays bound); a checkpoint without them or with other shapes raises"""
+    checkpoint = torch.load(ckpt_path, map_location='cpu', weights_only=True)
+    checkpoint = checkpoint.get('state_dict', checkpoint)
+    own = pose_refiner.state_dict()
+    missing = [k for k in own if k not in checkpoint]
+    if missing:
+        raise KeyError(f"checkpoint has no pose keys {missing}")
+    bad = [(k, tuple(checkpoint[k].shape), tuple(own[k].shape)) for k in own if tuple(checkpoint[k].shape) != tuple(own[k].shape)]
+    if bad:
+        raise RuntimeError("size mismatch for " + ", ".join(f"{k}: checkpoint {a} vs refiner {b}" for k, a, b in bad))
+    with torch.no_grad():
+        for k in own:
+            own[k].copy_(checkpoint[k].to(own[k].device))
 
 
 def slim_ckpt(ckpt_path, save_poses=False):

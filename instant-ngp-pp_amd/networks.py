@@ -339,8 +339,10 @@ class _FieldFn(Function):
         ctx.E, ctx.K, ctx.Kp, ctx.C = E, K, Kp, C
         ctx.ray_codes = ray_codes
         ctx.codes_shape = None if ray_codes is None else tuple(embed_a.shape)
+        # (pose refinement: the view directions need a gradient, and its kernel reads them again)
         ctx.save_for_backward(xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
-                              xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dfeat)
+                              xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dfeat,
+                              *((d,) if ctx.needs_input_grad[2] else ()))
         ctx.mark_non_differentiable(grads)
         ctx.set_materialize_grads(False)
         return sig[:, 0], rgb_o, grads, np_o, sem_o
@@ -348,7 +350,7 @@ class _FieldFn(Function):
     @staticmethod
     def backward(ctx, d_sig, d_rgb, _d_grads, d_np, d_sem):
         (xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
-         xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dsig_dfeat) = ctx.saved_tensors
+         xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dsig_dfeat) = ctx.saved_tensors[:19]
         model = ctx.model
         link = model.link
         E, K, Kp, C = ctx.E, ctx.K, ctx.Kp, ctx.C
@@ -356,7 +358,7 @@ class _FieldFn(Function):
         dev = xn.device
         xe, re = model.xyz_encoder, model.rgb_encoder
         need = ctx.needs_input_grad  # (model, x, d, embed_a, xyz_table, W1, b1, W2, b2, rgb_table, rgb_p, nrm_p, sem_p)
-        g_x = g_emb = g_xyz = g_W1 = g_b1 = g_W2 = g_b2 = g_rgbt = g_rgbp = g_nrm = g_sem = None
+        g_x = g_d = g_emb = g_xyz = g_W1 = g_b1 = g_W2 = g_b2 = g_rgbt = g_rgbp = g_nrm = g_sem = None
         span = model._span()
         # A trainer that owns the gradient storage (NGPTrainer: one flat buffer, zeroed by its Adam
         # launch) registers the MLP gradients as sinks: the weight products accumulate straight into
@@ -435,6 +437,12 @@ class _FieldFn(Function):
             st.input_product(dfeat_rgb, W_cols, W_cols, 16, False)
             stages.append(st)
             rgb_stage = st
+            if need[2]:
+                # dL/dd: rgb_net's data gradient for the 16 SH columns, then the adjoint of the direction encoding
+                d_sh = torch.empty(n, 16, dtype=_f32, device=dev)
+                st.input_product(d_sh, 16, 16, 0, False)
+                g_d = torch.empty(n, 3, dtype=_f32, device=dev)
+                call("sh_bwd_dirs", ctx.saved_tensors[19], d_sh, 16, n, g_d)
         for d_o, p, a_h, out, n_out, slot in ((d_np, nrm_p, a_n, np_o, 3, "nrm"), (d_sem, sem_p, a_s, sem_o, C, "sem")):
             if d_o is None:
                 continue
@@ -511,7 +519,7 @@ class _FieldFn(Function):
             g_x = g_x / span
         if forked:
             main.wait_stream(side)
-        return (None, g_x, None, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None)
+        return (None, g_x, g_d, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None)
 
 
 class NGP(nn.Module):

@@ -307,6 +307,11 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     mark_full_cover(rays_a)   # the marcher's segments tile [0, N): the compositor may skip its zero-fills
     results['rays_a'] = rays_a
     results['total_samples'] = total_samples
+    pose = kwargs.pop('_pose', None)
+    if pose is not None:
+        # pose refinement (pose.PoseRefiner, image and pixel of every ray): the samples were marched from the rays' values;
+        # from here on they carry a gradient that ngp_pose_rays_bwd takes to dR and dT
+        xyzs, dirs = pose[0].attach_samples(xyzs, dirs, results['ts'], rays_a, pose[1], pose[2])
 
     # per-ray tensor kwargs (embedding_a, exposure, ...) are repeated per sample; like the
     # reference this rewrites kwargs in place (rendering.py:217-219).  RayCodes (the embedding table and the rays' image

@@ -156,8 +156,14 @@ def shard_seed(base_seed, rank):
 class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
-                 force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None):
-        """embedding_a: the nn.Embedding(n_imgs, embed_a_len) of the embed_a recipe (or a FrameEmbedding, whose table is
+                 force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6):
+        """pose_refiner: a pose.PoseRefiner (the reference's --optimize_ext, train.py:143-149, 225-230).  step() then takes
+        img_idxs= and pix_idxs= instead of ray tensors and forms the rays itself from the current dR, dT; the samples enter
+        the field requiring a gradient, which ngp_pose_rays_bwd reduces per image.  dR and dT live in a small buffer of their
+        own OUTSIDE the flat store, as the reference keeps them out of net_opt: their own Adam at the constant `pose_lr` (no
+        cosine schedule) and their own clip at clip_norm (Lightning clips per optimizer).  A pose step takes the exact
+        gradient norm for the model (the norm bound is not shown to hold on the field's dL/dx route).  One rank only.
+        embedding_a: the nn.Embedding(n_imgs, embed_a_len) of the embed_a recipe (or a FrameEmbedding, whose table is
         taken), for a model built with embed_a=True.  Its weight joins the flat store behind the model's parameters as
         'embedding_a.weight' (the reference keeps it in net_opt, train.py:238-244: one Adam, one schedule, one clip), step()
         then needs img_idxs=, and the field reads and differentiates the table through ngp_embed_a_fwd / ngp_embed_a_bwd.
@@ -180,6 +186,10 @@ class NGPTrainer:
                 raise ValueError(f"embedding_a has codes of length {tuple(self.embedding_a.weight.shape[1:])}, the model "
                                  f"was built with embed_a={bool(E)}, embed_a_len={E}")
         self.force_sharded = bool(os.environ.get("NGP_FORCE_SHARDED")) if force_sharded is None else bool(force_sharded)
+        self.pose_refiner, self.pose_lr = pose_refiner, float(pose_lr)
+        if pose_refiner is not None and (self.force_sharded or (dist.is_available() and dist.is_initialized()
+                                                                 and dist.get_world_size(group) > 1)):
+            raise ValueError("pose refinement runs on one rank: a sharded trainer takes no pose_refiner")
         self.base_lr = lr
         self.num_epochs = num_epochs
         self.steps_per_epoch = steps_per_epoch
@@ -192,6 +202,12 @@ class NGPTrainer:
         self.loss_kwargs = dict(loss_kwargs or {})
         optional = any(self.loss_kwargs.get(k) for k in ("normal_ref", "normal_mono", "semantic", "depth_mono", "embed_msk"))
         self.fused_loss = not optional   # default recipe (rgb + opacity + distortion); False -> NeRFLoss module
+        if pose_refiner is not None and (optional or self.render_kwargs.get("use_skybox")
+                                         or getattr(model, "differentiable_normals", False)):
+            # only the field's dL/dx and dL/dd feed the pose gradient; the Ro term (rendering._RefLossInputs returns no
+            # gradient for dirs), a skybox (a function of rays_d) and second-order normals would leave it silently incomplete
+            raise ValueError("pose refinement runs on the fused render + loss tail: a trainer with a pose_refiner takes no "
+                             "optional loss term, no skybox and no differentiable normals")
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -214,6 +230,8 @@ class NGPTrainer:
         self._opt_stream = torch.cuda.Stream(device=self.flat_param.device) if self.flat_param.is_cuda else None
         self._march_ahead = MarchAhead(self.flat_param.device) if self.flat_param.is_cuda else None
         self._link_field()
+        if pose_refiner is not None:
+            self._own_poses()
 
     # ------------------------------------------------------------------ flat parameter store
     def _flatten(self):
@@ -312,6 +330,35 @@ class NGPTrainer:
             # scatter, beside the density head's backward, instead of on the path between the last scatter and Adam
             m.rgb_encoder.on_grad_ready = self._early_norm_share
 
+    def _own_poses(self):
+        """dR and dT move into one buffer [parameters | gradients | exp_avg | exp_avg_sq], each part [dR | dT] with both
+        pieces 16-byte aligned; ngp_pose_rays_bwd adds straight into the gradient part"""
+        ref, dev = self.pose_refiner, self.flat_param.device
+        if ref.dR.device != dev:
+            raise ValueError(f"pose_refiner is on {ref.dR.device}, the model on {dev}")
+        n = ref.dR.numel()
+        seg = (n + 3) // 4 * 4
+        buf = torch.zeros(4, 2 * seg, dtype=_f32, device=dev)
+        self.pose_param, self.pose_grad, self.pose_exp_avg, self.pose_exp_avg_sq = buf[0], buf[1], buf[2], buf[3]
+        for k, p in enumerate((ref.dR, ref.dT)):
+            view = self.pose_param[k * seg:k * seg + n].view_as(p)
+            view.copy_(p.data)
+            p.data = view
+            p.grad = self.pose_grad[k * seg:k * seg + n].view_as(p)
+        ref.grad_sink = (ref.dR.grad, ref.dT.grad)
+        self.pose_scalars = torch.zeros(2, dtype=_f32, device=dev)   # [sum of squares, clip coefficient]
+        self.pose_steps = 0
+
+    def _pose_step(self):
+        """clip_grad_norm_(clip_norm) and Adam(pose_lr, eps=1e-8) over [dR | dT]; the gradient is cleared by the Adam launch"""
+        self.pose_steps += 1
+        n = self.pose_grad.numel()
+        self.pose_scalars.zero_()
+        call("sumsq", self.pose_grad, n, self.pose_scalars[0:1])
+        call("clip_coef", self.pose_scalars[0:1], float(self.clip_norm), 1.0, self.pose_scalars[1:2])
+        call("adam_step", self.pose_param, self.pose_grad, self.pose_exp_avg, self.pose_exp_avg_sq, n, self.pose_lr, 0.9,
+             0.999, 1e-8, 0.0, self.pose_steps, self.pose_scalars[1:2], 1)
+
     def _unit_seed(self, terms):
         s = getattr(self, '_seed4', None)
         if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model)
@@ -334,11 +381,15 @@ class NGPTrainer:
     def lr(self):
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
-    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, **loss_kwargs):
+    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None,
+             **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
 
         uvi: (n_rays, 3) input of the trainer's msk_model (implicit_mask.uvi), required when there is one.
-        img_idxs: (n_rays) image index of every ray, required when the trainer has an embedding_a.
+        img_idxs: (n_rays) image index of every ray, required when the trainer has an embedding_a or a pose_refiner.
+        pix_idxs: (n_rays) pixel index of every ray (into the refiner's `directions`), required with a pose_refiner; rays_o
+        and rays_d are then None (the rays come from the refiner's current dR, dT) and there is no next_rays: a march-ahead
+        would use poses that are one update old.
 
         target: further per-ray supervision for NeRFLoss's optional terms ('normal', 'label', 'depth': the
         batch dictionary of train.py:299); loss_kwargs: per-step additions to the trainer's loss_kwargs
@@ -354,6 +405,20 @@ class NGPTrainer:
             raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
         if self.embedding_a is not None and img_idxs is None:
             raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
+        ref = self.pose_refiner
+        if ref is not None:
+            if rays_o is not None or rays_d is not None or next_rays is not None:
+                raise ValueError("this trainer has a pose_refiner: step() forms the rays itself from img_idxs= and pix_idxs= "
+                                 "(pass rays_o = rays_d = None and no next_rays: a march-ahead would use poses one update old)")
+            if img_idxs is None or pix_idxs is None:
+                raise ValueError("this trainer has a pose_refiner: step() needs img_idxs= and pix_idxs=")
+            if target or loss_kwargs:
+                raise ValueError("this trainer has a pose_refiner: the step stays on the fused render + loss tail and takes "
+                                 "no target= and no per-step loss term")
+            with torch.no_grad():   # the values only: the graph starts at the samples (rendering._render_rays_train)
+                rays_o, rays_d = ref.rays(img_idxs, pix_idxs)
+        elif pix_idxs is not None:
+            raise ValueError("pix_idxs= is for a trainer with a pose_refiner")
         self._join_grad_zeroing()
         if self.global_step % self.update_interval == 0:
             model.update_density_grid(self.density_threshold * MAX_SAMPLES / 3 ** 0.5,
@@ -387,6 +452,8 @@ class NGPTrainer:
                 extra['_fused_loss'] += (mask, self.loss_fn.Annealing.getWeight(self.global_step))
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
+        if ref is not None:
+            extra['_pose'] = (ref, img_idxs, pix_idxs)
         results = render(model, rays_o, rays_d, exp_step_factor=self.exp_step_factor,
                          num_classes=self.num_classes, marched=marched, **self.render_kwargs, **extra)
         if launch_next_late:
@@ -394,7 +461,7 @@ class NGPTrainer:
         self._norm_share_armed, self._norm_share_fired = True, 0   # one backward follows, then the optimizer step
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
         # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
-        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals)
+        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None)
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
@@ -465,6 +532,8 @@ class NGPTrainer:
         self.global_step += 1
         # lr of the epoch this step belongs to (the scheduler ticks at epoch boundaries)
         lr = self.lr_at(min((self.global_step - 1) // self.steps_per_epoch, self.num_epochs))
+        if self.pose_refiner is not None:
+            self._pose_step()   # three small launches on the main stream, where the next step's rays read dR and dT
         if not self.sharded:
             # clip + Adam stream 6.4 GB and touch no ray data: they run on the optimizer stream, the
             # field waits on its link's `params_ready` / `rgb_params_ready` where it first reads the respective

@@ -10,6 +10,8 @@ reference: train.py:82-392).  GPU only.
       --random_bg --embed_msk --save_dir out --ckpt_path out/playground.ckpt   # transient mask: out/mask_NNN.png per image
   python tools/train_dataset.py --root_dir /data/tnt/Playground --dataset_name tnt --scale 8 --exp_step_factor 0.00390625 \
       --random_bg --embed_a --embed_a_len 8 --embed_msk --ckpt_path out/playground.ckpt   # the reference's Playground recipe
+  python tools/train_dataset.py --make_proxy /tmp/proxy --downsample 0.125 --num_epochs 2 --optimize_ext --pose_lr 1e-4 \
+      --perturb_poses 0.02 0.5 --ckpt_path out/poses.ckpt   # pose refinement from perturbed poses: errors before / after
 """
 import argparse
 import json
@@ -28,6 +30,7 @@ from ngp_amd.evaluation import evaluate_split
 from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
+from ngp_amd.pose import PoseRefiner, perturb_poses, pose_errors
 from ngp_amd.trainer import NGPTrainer
 
 
@@ -41,18 +44,28 @@ def build_model(scale, device, embed_a=False, embed_a_len=4):
 
 
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
-          render_kwargs=None, msk_model=None, embedding_a=None):
+          render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
-    table of --embed_a, fed with the sampler's image indices"""
+    table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
+    with the sampler's image and pixel indices (the trainer then forms the rays itself, and nothing is marched ahead)"""
     train_set.batch_size = batch_size
     more = {} if embedding_a is None else {"embedding_a": embedding_a}
+    if pose_refiner is not None:
+        more.update(pose_refiner=pose_refiner, pose_lr=pose_lr)
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
                          exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
     n_imgs = len(train_set.poses)
 
     def next_batch():
         s = train_set[0]
+        if pose_refiner is not None:
+            idx = torch.as_tensor(s["img_idxs"], device=s["rgb"].device).to(torch.int64).reshape(-1)
+            idx = idx.expand(s["rgb"].shape[0]).contiguous()
+            uvi = None
+            if msk_model is not None:
+                uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(idx.device)
+            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous()
         o, d = train_set.batch_rays(s)
         uvi = None
         if msk_model is not None:
@@ -60,7 +73,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         idx = None
         if embedding_a is not None:   # one index per ray (the same_image strategy draws ONE image per batch)
             idx = torch.as_tensor(s["img_idxs"], device=o.device).to(torch.int64).reshape(-1).expand(o.shape[0]).contiguous()
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None
 
     import gc
     gc.collect()
@@ -71,7 +84,10 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     for i in range(total):
         nxt = next_batch() if i + 1 < total else None
         more = {} if cur[4] is None else {"img_idxs": cur[4]}
-        loss, res = trainer.step(*cur[:3], next_rays=None if nxt is None else nxt[:2], uvi=cur[3], **more)
+        if cur[5] is not None:
+            more["pix_idxs"] = cur[5]
+        ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
+        loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
             print(json.dumps({"step": i + 1, "loss": float(loss), "train_psnr": float(psnr(res["rgb"].detach(), cur[2])),
@@ -137,6 +153,13 @@ def main():
                     help="train one appearance code per training image (the reference's --embed_a); the test split is "
                          "evaluated with the code of image 0")
     ap.add_argument("--embed_a_len", type=int, default=4, help="length of an appearance code, 1 to 32")
+    ap.add_argument("--optimize_ext", action="store_true",
+                    help="train a per-image rotation dR and translation dT beside the scene (the reference's --optimize_ext); "
+                         "the test split is rendered with the dataset's test poses")
+    ap.add_argument("--pose_lr", type=float, default=1e-6, help="constant learning rate of dR, dT (the reference's 1e-6)")
+    ap.add_argument("--perturb_poses", type=float, nargs=2, metavar=("SIGMA_T", "DEG"),
+                    help="with --optimize_ext: start from training poses translated by N(0, SIGMA_T^2) per axis and rotated by "
+                         "DEG degrees about random axes (seeded); the JSON line reports the pose errors before and after")
     ap.add_argument("--batch_size", type=int, default=8192)
     ap.add_argument("--num_epochs", type=int, default=20)
     ap.add_argument("--steps_per_epoch", type=int, default=1000)
@@ -146,6 +169,8 @@ def main():
     args = ap.parse_args()
     if not 1 <= args.embed_a_len <= 32:
         ap.error("--embed_a_len must lie in [1, 32]")
+    if args.perturb_poses and not args.optimize_ext:
+        ap.error("--perturb_poses needs --optimize_ext")
     dev = torch.device("cuda", 0)
     torch.manual_seed(20220806)
     root = args.root_dir
@@ -160,10 +185,15 @@ def main():
     model = build_model(args.scale, dev, args.embed_a, args.embed_a_len)
     msk_model = implicit_mask().to(dev) if args.embed_msk else None
     embedding_a = FrameEmbedding(args.embed_a_len, train_set.poses).to(dev) if args.embed_a else None
+    pose_refiner = true_poses = None
+    if args.optimize_ext:
+        true_poses = torch.as_tensor(train_set.poses, dtype=torch.float32)
+        start = perturb_poses(true_poses, *args.perturb_poses, seed=20220806) if args.perturb_poses else true_poses
+        pose_refiner = PoseRefiner(start, train_set.directions).to(dev)
     t0 = time.perf_counter()
     train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
-          msk_model=msk_model, embedding_a=embedding_a)
+          msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
@@ -173,11 +203,16 @@ def main():
                          exp_step_factor=args.exp_step_factor, **more)
     psnrs, ssims = res["psnr"], res["ssim"]
     if args.ckpt_path:
-        ckpt.save_ckpt(model, args.ckpt_path, msk_model=msk_model, **({} if embedding_a is None else
-                                                                      {"embedding_a": embedding_a}))
+        ckpt.save_ckpt(model, args.ckpt_path, msk_model=msk_model, pose_refiner=pose_refiner,
+                       **({} if embedding_a is None else {"embedding_a": embedding_a}))
     out = {"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
            "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
            "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}
+    if pose_refiner is not None:   # mean translation (scene units) and rotation (degrees) error against the dataset's poses
+        before = pose_errors(pose_refiner.poses.cpu(), true_poses.cpu())
+        after = pose_errors(pose_refiner.refined_poses().detach().cpu(), true_poses.cpu())
+        out.update(pose_t_err_before=before[0], pose_rot_err_deg_before=before[1], pose_t_err_after=after[0],
+                   pose_rot_err_deg_after=after[1], pose_lr=args.pose_lr)
     if msk_model is not None:
         means = mask_images(msk_model, train_set.img_wh, len(train_set.poses), dev, save_dir=args.save_dir)
         out["mask_mean"] = sum(means) / len(means)
