@@ -99,7 +99,12 @@ int ngp_grid_cell_points(const int32_t* coords, const float* noise, int n, int g
  * occupied: the m uniform ones only), in Morton bucket order, with their jittered world points
  * x_w = (coord/(G-1)*2-1)*(s-s/G) + U(-1,1)*s/G.  Randomness is a counter-based hash of (seed, sample, draw): the
  * same on every rank, independent of launch order.  workspace: ngp_grid_sample_workspace(G, m) int32 elements
- * (host-only query).  outputs: indices (2m) i32 Morton cell indices, xyzs_w (2m,3) f32. */
+ * (host-only query).  outputs: indices (2m) i32 Morton cell indices, xyzs_w (2m,3) f32.
+ * grid_size must be a power of two in 2..1024 (Morton keys of a G^3 grid span 3*ceil(log2 G) bits; only then is
+ * every key a cell index < G^3): anything else is NGP_EINVAL from both entries, before any launch.
+ * Order of the rows: by the top min(bits, 21) bits of the bits = 3*log2(G)-bit key, i.e. indices[i] >>
+ * max(0, bits - 21) is non-decreasing (G <= 128: fully sorted); rows with equal sort keys come in any order.
+ * The workspace is scratch: its contents need not be cleared or kept between calls, whatever they are. */
 int64_t ngp_grid_sample_workspace(int grid_size, int m);
 int ngp_grid_sample_cells(const float* density_grid_c, int grid_size, float density_threshold, int m,
                           int64_t seed, float s, int32_t* workspace, int32_t* indices, float* xyzs_w,
@@ -130,6 +135,8 @@ int ngp_density_grid_ema(float* density_grid, const float* density_grid_tmp, int
  * n_rays*max_samples); rows >= counter[0] are left untouched unless zero_tail!=0,
  * in which case they are zero-filled like the reference's torch::zeros.
  * counter: (2) i32 -> {total samples, n_rays}.
+ * grid_size must be a power of two in 1..1024 (the bitfield is indexed by the Morton code of the cell), else
+ * NGP_EINVAL; the same holds for ngp_raymarching_test.
  * ---------------------------------------------------------------------- */
 int ngp_raymarching_train(const float* rays_o, const float* rays_d, const float* hits_t /* (n_rays,2) */,
                           const uint8_t* density_bitfield, int cascades, float scale,

@@ -786,6 +786,10 @@ int ngp_grid_cell_points(const int32_t* coords, const float* noise, int n, int g
     return ngp_check_launch();
 }
 
+// Morton keys of a G^3 grid span 3*ceil(log2 G) bits: only for a power of two is every key < G^3, which the bucket
+// shift, the occupied-cell list and the bitfield index of the marcher all rely on
+static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
 static int key_bits(int g3)
 {
     int bits = 0;
@@ -795,7 +799,7 @@ static int key_bits(int g3)
 
 int64_t ngp_grid_sample_workspace(int grid_size, int m)
 {
-    if (grid_size < 1 || grid_size > 1024 || m < 1) return NGP_EINVAL;
+    if (grid_size < 2 || grid_size > 1024 || !is_pow2(grid_size) || m < 1) return NGP_EINVAL;
     const int64_t g3 = (int64_t)grid_size * grid_size * grid_size;
     const int64_t nb = (g3 + OCC_BLOCK - 1) / OCC_BLOCK;
     return 2 * nb + 4 + g3 + 8 * (int64_t)m + 3 * SAMPLE_TOP;
@@ -804,7 +808,7 @@ int64_t ngp_grid_sample_workspace(int grid_size, int m)
 int ngp_grid_sample_cells(const float* density_grid_c, int grid_size, float density_threshold, int m, int64_t seed,
                           float s, int32_t* workspace, int32_t* indices, float* xyzs_w, void* stream)
 {
-    if (grid_size < 2 || grid_size > 1024 || m < 1) return NGP_EINVAL;
+    if (grid_size < 2 || grid_size > 1024 || !is_pow2(grid_size) || m < 1) return NGP_EINVAL;
     if (!density_grid_c || !workspace || !indices || !xyzs_w) return NGP_EINVAL;
     const int64_t g3l = (int64_t)grid_size * grid_size * grid_size;
     if (g3l > (1ll << 30) || 2 * (int64_t)m > (1ll << 30)) return NGP_EINVAL;
@@ -886,7 +890,7 @@ int ngp_raymarching_train(const float* rays_o, const float* rays_d, const float*
                           int64_t* rays_a, float* xyzs, float* dirs, float* deltas, float* ts,
                           int32_t* counter, int64_t sample_capacity, int zero_tail, void* stream)
 {
-    if (n_rays < 0 || cascades < 1 || grid_size < 1 || grid_size > 1024 || max_samples < 1) return NGP_EINVAL;
+    if (n_rays < 0 || cascades < 1 || grid_size > 1024 || !is_pow2(grid_size) || max_samples < 1) return NGP_EINVAL;
     if (!counter) return NGP_EINVAL;
     if (n_rays > 0 && (!rays_o || !rays_d || !hits_t || !density_bitfield || !noise || !t_scratch || !ray_counts ||
                        !rays_a || !xyzs || !dirs || !deltas || !ts)) return NGP_EINVAL;
@@ -914,7 +918,7 @@ int ngp_raymarching_test(const float* rays_o, const float* rays_d, float* hits_t
                          float* xyzs, float* dirs, float* deltas, float* ts,
                          int32_t* n_eff_samples, void* stream)
 {
-    if (n_alive < 0 || cascades < 1 || grid_size < 1 || grid_size > 1024 || n_samples < 1) return NGP_EINVAL;
+    if (n_alive < 0 || cascades < 1 || grid_size > 1024 || !is_pow2(grid_size) || n_samples < 1) return NGP_EINVAL;
     if (n_alive == 0) return NGP_OK;
     if (!rays_o || !rays_d || !hits_t || !alive_indices || !density_bitfield || !xyzs || !dirs || !deltas || !ts ||
         !n_eff_samples) return NGP_EINVAL;
