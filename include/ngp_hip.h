@@ -279,6 +279,30 @@ int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const f
                                  int64_t* total_samples, int64_t* vr_samples, float* opacity, float* depth, float* rgb,
                                  float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
                                  float* dL_dsigmas, float* dL_drgbs, float* dL_dmask, void* stream);
+/* The same launch for NeRFLoss(semantic=True) (losses.py:120-123): labels (n_rays) int64, indexed by ray like target_rgb.
+ * A label y is valid iff 0 <= y < classes; every other value (the reference's ignore_index 256, an 8-bit 255, negative
+ * values, y >= classes) is ignored and never used as an index.  n_valid = number of valid labels among the n_rays rows.
+ * terms (6) = [loss, rgb, opacity, distortion, CELoss, sky_depth]:
+ *   CELoss    = lambda_sem sum_valid (logsumexp_c(S) - S_y) / n_valid, S = sem, the composited class probabilities
+ *               (nn.CrossEntropyLoss(ignore_index=256) on them); 0, with zero gradients, when n_valid == 0 (torch: NaN);
+ *   sky_depth = lambda_sky / n_rays sum_r [y_r == 4] exp(-depth_r), the literal 4 whatever `classes` is.
+ * dL_dsem_logits (N, classes), dense: the CE term through S and the per-sample softmax with the weights held constant
+ * (composite_train_bw drops dL_dsem from dL_dsigmas, volumerendering.cu:234-241, so the CE term does not enter
+ * dL_dsigmas); zero behind a ray's stop.  The sky term enters dL_dsigmas through the depth.  sem_ws: device int32
+ * (NGP_SEM_WS_INTS = 8, 8-byte aligned) workspace, filled by a count kernel launched here ahead of the tail on the same
+ * stream (two launches, no host read, no allocation: capturable): [0] is n_valid afterwards, the rest holds the two
+ * terms' sums in double (one rounding each instead of a float atomic per workgroup).  1 <= classes <= 16.  vr_samples may sit at terms + 6 floats (one fill).  With
+ * lambda_sem = lambda_sky = 0 every output shared with ngp_render_loss_fused is that entry's. */
+#define NGP_SEM_WS_INTS 8
+int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, const int64_t* labels, float lambda_sem,
+                              float lambda_sky, float T_threshold, int classes, int n_rays, float lambda_opacity,
+                              float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
+                              float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
+                              float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* sem_ws,
+                              float* dL_dsem_logits, void* stream);
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,
                        float* normals_diff, float* normals_ori, void* stream);
 int ngp_neg_normalize(const float* x, int64_t ldx, const float* scale3 /* device (3) or NULL */, int64_t n,

@@ -580,21 +580,70 @@ struct RenderLossArgs {
     const float* mask;
     float g_ms;
     float* d_mask;
+    // SEM only (NeRFLoss(semantic=True), losses.py:120-123): the label of every ray, the workspace (SemWs below, filled by
+    // count_valid_labels_kernel ahead of this launch), lambda_sem, g_sky = lambda_sky / R, and the loss's gradient w.r.t.
+    // the class logits, dense (n, classes)
+    const int64_t* labels;
+    int* sem_ws;
+    float lam_sem, g_sky;
+    float* d_sem;
 };
+
+// The semantic tail's workspace, NGP_SEM_WS_INTS = 8 int32, 8-byte aligned: [0] n_valid, [2:4] and [4:6] two doubles, the
+// batch's sums of CE_r and of [y == 4] exp(-D_r), [6] the number of workgroups that have added theirs.  The two new terms
+// are means of O(1) values scaled by weights of 1e-1: summed with one float atomic per workgroup (as terms[0:4] are) they
+// would carry a few ulps of the result in arrival order, more than a faithful float32 evaluation of the loss has.  The
+// workgroups add doubles instead, and the last one to finish rounds the two sums once into terms[4], terms[5] and terms[0].
+constexpr int SEM_WS_NVALID = 0, SEM_WS_SUMS = 2, SEM_WS_DONE = 6;
+
+// number of rows whose ray carries a valid label (0 <= y < classes), and the rest of the workspace cleared: one workgroup,
+// no atomics, so the workspace needs no fill of its own
+__global__ void __launch_bounds__(1024) count_valid_labels_kernel(const int64_t* __restrict__ labels,
+                                                                  const int64_t* __restrict__ rays_a, int n_rays, int classes,
+                                                                  int* __restrict__ ws)
+{
+    __shared__ int part[16];
+    int c = 0;
+    for (int row = threadIdx.x; row < n_rays; row += 1024) {
+        const int64_t y = labels[rays_a[3 * (size_t)row]];
+        c += (y >= 0 && y < classes) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int q = 0; q < 16; q++) t += part[q];
+#pragma unroll
+        for (int q = 0; q < 8; q++) ws[q] = q == SEM_WS_NVALID ? t : 0;   // the sums and the workgroup count start at 0
+    }
+}
 
 // MASKED: the colour term is mean (1 - m) e^2 (its seed, and through it the background's share of d_opacity, carry the
 // factor 1 - m), terms[4] = size_delta mean m^2, d_mask = 2 size_delta m / R - sum_c e_c^2 / (3 R); the rendered outputs
 // are those of the unmasked kernel.  With m = 0 and size_delta = 0 every product below is by 1.0 and every sum with 0.0.
-template <int CMAX, int W, bool MASKED>
+// SEM: with y the ray's label (valid iff 0 <= y < classes; 256, 255, negative, ... are ignored and never index anything),
+// S = sem (the composited probabilities) and n_valid the batch's count of valid labels,
+//   terms[4] = lambda_sem sum_valid (logsumexp(S) - S_y) / n_valid   (nn.CrossEntropyLoss(ignore_index=256) on S; 0 when
+//              n_valid == 0, where torch gives NaN), seed g_c = lambda_sem / n_valid (softmax(S)_c - [c == y]),
+//   d_sem[s, j] = w_s p_sj (g_j - sum_c g_c p_sc) with p the per-sample softmax, recomputed in pass C; the weights are
+//              constants of this term (composite_train_bw drops dL_dsem from dL_dsigma, volumerendering.cu:234-241),
+//   terms[5] = lambda_sky / R sum [y == 4] exp(-depth) (the literal 4, losses.py:122), seed g_D = -g_sky [y == 4] exp(-D),
+//              which enters d_sigmas as delta_s g_D (t_s T_s - (D - d_s)), d_s the inclusive prefix of w t: the scan pass C
+//              forms for the distortion term anyway.
+template <int CMAX, int W, bool MASKED, bool SEM>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
+    static_assert(!(MASKED && SEM), "SEM x MASKED is not built");
     constexpr int RPB = 256 / W;          // rays per block
-    __shared__ float part[MASKED ? 4 : 3][RPB];
+    __shared__ float part[MASKED ? 4 : SEM ? 5 : 3][RPB];
     __shared__ unsigned long long part_n[RPB];
     Seg sg; int lane;
     const bool have = seg_load_w<W>(p.rays_a, p.n_rays, sg, lane);
-    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f;
+    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f, s_ce = 0.0f, s_sky = 0.0f;
     unsigned long long n_used = 0;
+    const int n_valid = SEM ? p.sem_ws[SEM_WS_NVALID] : 0;
     if (have) {
         const size_t r = (size_t)sg.ray;
         const float sc0 = p.scale3 ? p.scale3[0] : 1.0f, sc1 = p.scale3 ? p.scale3[1] : 1.0f, sc2 = p.scale3 ? p.scale3[2] : 1.0f;
@@ -667,6 +716,11 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 const int64_t s = sg.start + k;
                 p.ws[s] = 0.0f; p.d_sigmas[s] = 0.0f;
                 p.d_rgbs[3 * s] = 0.0f; p.d_rgbs[3 * s + 1] = 0.0f; p.d_rgbs[3 * s + 2] = 0.0f;
+                if (SEM) {
+#pragma unroll
+                    for (int cc = 0; cc < CMAX; cc++)
+                        if (cc < p.classes) p.d_sem[s * p.classes + cc] = 0.0f;
+                }
             }
         }
         const int n_live = stop >= 0 ? (stop / W + 1) * W : sg.n;   // passes B and C stop behind the stop sample's chunk
@@ -696,6 +750,29 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
         // d loss / d opacity: the entropy term, and through the background's weight (1 - opacity)
         const float gO = p.g_op * (-lgo - 1.0f) - (gR * bg0 + gG * bg1 + gB * bg2);
         const float gd = p.g_dist;
+        // SEM: the seeds of the class probabilities and of the depth (every lane holds the ray's sums)
+        float gS[CMAX], gD = 0.0f, ce = 0.0f, sky = 0.0f;
+        if (SEM) {
+            const int64_t y = p.labels[r];
+            const bool y_ok = y >= 0 && y < p.classes;
+            const float gs = (y_ok && n_valid > 0) ? p.lam_sem / (float)n_valid : 0.0f;
+            float mx = -INFINITY, den = 0.0f, Sy = 0.0f;
+#pragma unroll
+            for (int cc = 0; cc < CMAX; cc++)
+                if (cc < p.classes) mx = fmaxf(mx, aS[cc]);
+#pragma unroll
+            for (int cc = 0; cc < CMAX; cc++) {
+                gS[cc] = cc < p.classes ? expf(aS[cc] - mx) : 0.0f;
+                den += gS[cc];
+                if ((int64_t)cc == y) Sy = aS[cc];      // (a select per class: the label never indexes)
+            }
+            if (y_ok) ce = mx + logf(den) - Sy;
+            const float ginv = gs / den;
+#pragma unroll
+            for (int cc = 0; cc < CMAX; cc++) gS[cc] = gS[cc] * ginv - ((int64_t)cc == y && y_ok ? gs : 0.0f);
+            if (y == 4) sky = expf(-aD);
+            gD = -p.g_sky * sky;
+        }
         if (lane == 0) {
             p.total_samples[r] = stop >= 0 ? stop : sg.n;
             p.opacity[r] = aO; p.depth[r] = aD;
@@ -711,6 +788,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 s_rgb *= keep;
                 s_ms = mk * mk;
             }
+            if (SEM) { s_ce = ce; s_sky = sky; }
             n_used = (unsigned long long)(stop >= 0 ? stop : sg.n);
         }
         const float w_sum = w_run, wt_sum = wt_run;
@@ -760,9 +838,31 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                     const float wa = c.active ? w : 0.0f;
                     p.d_rgbs[3 * s] = gR * wa; p.d_rgbs[3 * s + 1] = gG * wa; p.d_rgbs[3 * s + 2] = gB * wa;
                     const float T = c.T_after;
-                    const float v = dl * (gR * (cr * T - (aR - ri)) + gG * (cg * T - (aG - gi)) + gB * (cb * T - (aB - bi)) +
-                                          gO * (1 - aO) + T * dws - (tot - pi));
+                    float v = dl * (gR * (cr * T - (aR - ri)) + gG * (cg * T - (aG - gi)) + gB * (cb * T - (aB - bi)) +
+                                    gO * (1 - aO) + T * dws - (tot - pi));
+                    if (SEM) v += dl * gD * (tt * T - (wt_sum - wti));
                     p.d_sigmas[s] = c.active ? v : 0.0f;
+                    if (SEM) {
+                        // the sample's softmax again (pass A kept none), then the softmax backward of the seeds
+                        float pr[CMAX], mx = -INFINITY;
+#pragma unroll
+                        for (int cc = 0; cc < CMAX; cc++) {
+                            pr[cc] = (c.active && cc < p.classes) ? p.sem_logits[s * p.ld_sem + cc] : -INFINITY;
+                            mx = fmaxf(mx, pr[cc]);
+                        }
+                        float den = 0.0f, dot = 0.0f;
+#pragma unroll
+                        for (int cc = 0; cc < CMAX; cc++) {
+                            pr[cc] = (c.active && cc < p.classes) ? __expf(pr[cc] - mx) : 0.0f;
+                            den += pr[cc];
+                            dot += gS[cc] * pr[cc];
+                        }
+                        const float winv = c.active ? wa / den : 0.0f;
+                        dot = c.active ? dot / den : 0.0f;
+#pragma unroll
+                        for (int cc = 0; cc < CMAX; cc++)
+                            if (cc < p.classes) p.d_sem[s * p.classes + cc] = winv * pr[cc] * (gS[cc] - dot);
+                    }
                 }
                 if (c.first >= 0) break;
                 T2 = __shfl(c.T_after, W - 1, W);
@@ -776,6 +876,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
     if ((threadIdx.x & (W - 1)) == 0) {
         part[0][hw] = s_rgb; part[1][hw] = s_op; part[2][hw] = s_dist; part_n[hw] = n_used;
         if (MASKED) part[3][hw] = s_ms;
+        if (SEM) { part[3][hw] = s_ce; part[4][hw] = s_sky; }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -788,6 +889,24 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             t3 *= p.g_ms;
             atomicAdd(p.terms, (t0 + t1 + t2) + t3);
             atomicAdd(p.terms + 4, t3);
+        } else if (SEM) {
+            atomicAdd(p.terms, t0 + t1 + t2);
+            double c_sum = 0.0, s_sum = 0.0;
+            for (int q = 0; q < RPB; q++) { c_sum += (double)part[3][q]; s_sum += (double)part[4][q]; }
+            double* sums = reinterpret_cast<double*>(p.sem_ws + SEM_WS_SUMS);
+            atomicAdd(sums, c_sum);
+            atomicAdd(sums + 1, s_sum);
+            __threadfence();
+            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(p.sem_ws + SEM_WS_DONE), 1u);
+            if (done == gridDim.x - 1) {   // every workgroup's sums are in: round them once
+                __threadfence();
+                const double ce_all = atomicAdd(sums, 0.0), sky_all = atomicAdd(sums + 1, 0.0);
+                const float t_ce = n_valid > 0 ? (float)(ce_all * ((double)p.lam_sem / (double)n_valid)) : 0.0f;
+                const float t_sky = (float)(sky_all * (double)p.g_sky);
+                p.terms[4] = t_ce;
+                p.terms[5] = t_sky;
+                atomicAdd(p.terms, t_ce + t_sky);
+            }
         } else
             atomicAdd(p.terms, t0 + t1 + t2);
         atomicAdd(p.terms + 1, t0);
@@ -1033,12 +1152,13 @@ static int render_loss_fused_launch(const float* sigmas, const float* rgbs, cons
     a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
     a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
     a.mask = mask; a.g_ms = size_delta / n_rays; a.d_mask = dL_dmask;
+    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
     if (mask)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
 
@@ -1070,6 +1190,49 @@ int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const f
                                     ts, rays_a, target_rgb, rgb_bg, mask, size_delta, T_threshold, classes, n_rays,
                                     lambda_opacity, lambda_distortion, total_samples, vr_samples, opacity, depth, rgb,
                                     normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs, dL_dmask, stream);
+}
+
+int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, const int64_t* labels, float lambda_sem,
+                              float lambda_sky, float T_threshold, int classes, int n_rays, float lambda_opacity,
+                              float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
+                              float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
+                              float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* sem_ws,
+                              float* dL_dsem_logits, void* stream)
+{
+    if (n_rays < 0 || classes < 1 || classes > 16 || ld_normal < 3 || ld_sem < classes) return NGP_EINVAL;
+    if (n_rays == 0) return NGP_OK;
+    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred || !sem ||
+        !loss_o || !loss_p || !terms || !labels || !sem_ws || !sem_logits || !dL_dsem_logits || !dL_dsigmas || !dL_drgbs ||
+        !ws || (reinterpret_cast<uintptr_t>(sem_ws) & 7)) return NGP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    // terms (6) with vr_samples right behind them (float 6): one fill
+    if (reinterpret_cast<char*>(vr_samples) == reinterpret_cast<char*>(terms) + 6 * sizeof(float)) {
+        if (hipMemsetAsync(terms, 0, 6 * sizeof(float) + sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+    } else {
+        if (hipMemsetAsync(terms, 0, 6 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+    }
+    // n_valid depends on the labels alone and every seed needs it: counted (and the workspace cleared) on the same stream
+    // ahead of the tail
+    hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, rays_a, n_rays, classes, sem_ws);
+    RenderLossArgs a;
+    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
+    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
+    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
+    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
+    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
+    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
+    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
+    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
+    a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits;
+    if (classes <= 8)
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((render_loss_fused_kernel<16, 32, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+    return ngp_check_launch();
 }
 
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,

@@ -19,6 +19,17 @@ def _save_png(arr, path):
     Image.fromarray(arr, {2: "L", 3: "RGB", 4: "RGBA"}[arr.shape[2] if arr.ndim == 3 else 2]).save(path)
 
 
+def _label_u8(label):
+    """one label image for the 8-bit PGM writer: 256, the reference's ignore_index, does not fit and is stored as 255
+    (ignored as well by the fused semantic tail for every class count it takes, and mapped back by nothing)"""
+    label = np.asarray(label)
+    if label.dtype == np.uint8:
+        return label
+    if (label < 0).any():
+        raise ValueError("negative labels cannot be written to a .pgm")
+    return np.minimum(label, 255).astype(np.uint8)
+
+
 def _homog(c2w):
     m = np.eye(4)
     m[:3, :4] = c2w
@@ -42,7 +53,7 @@ def export_blender(root, images, c2w, camera_angle_x, splits):
 def export_tnt(root, images, c2w, K, split_of, img_dir="images", labels=None, depths=None, camera_path=None,
                flat_intrinsics=False):
     """T&T / NSVF layout: split_of[i] in {0,1,2} is the file-name prefix of frame i.
-    labels (n,h,w) uint8 -> semantic/*.pgm, depths (n,h,w) float -> depth/*.npy,
+    labels (n,h,w) uint8 or wider integers (256 and above are stored as 255) -> semantic/*.pgm, depths (n,h,w) float -> depth/*.npy,
     camera_path (m,3,4) -> camera_path/pose/<5 digits>.txt"""
     os.makedirs(os.path.join(root, "pose"), exist_ok=True)
     K4 = np.eye(4)
@@ -53,7 +64,7 @@ def export_tnt(root, images, c2w, K, split_of, img_dir="images", labels=None, de
         _save_png(images[i], os.path.join(root, img_dir, stem + ".png"))
         np.savetxt(os.path.join(root, "pose", stem + ".txt"), _homog(c2w[i]))
         if labels is not None:
-            _save_png(labels[i], os.path.join(root, "semantic", stem + ".pgm"))
+            _save_png(_label_u8(labels[i]), os.path.join(root, "semantic", stem + ".pgm"))
         if depths is not None:
             os.makedirs(os.path.join(root, "depth"), exist_ok=True)
             np.save(os.path.join(root, "depth", stem + ".npy"), depths[i])
@@ -112,7 +123,7 @@ def export_colmap(root, images, c2w, K, names=None, points=None, model="PINHOLE"
                                   np.zeros((0, 2)), np.zeros(0, dtype=np.int64))
         _save_png(images[i], os.path.join(root, "images", names[i]))
         if labels is not None:
-            _save_png(labels[i], os.path.join(root, "semantic", os.path.splitext(names[i])[0] + ".pgm"))
+            _save_png(_label_u8(labels[i]), os.path.join(root, "semantic", os.path.splitext(names[i])[0] + ".pgm"))
     cu.write_images_binary(records, os.path.join(root, "sparse/0/images.bin"))
     points = np.zeros((1, 3)) if points is None else np.asarray(points, dtype=np.float64)
     cloud = {j + 1: cu.Point3D(j + 1, p, np.array([128, 128, 128], dtype=np.uint8), 0.5,
@@ -140,6 +151,19 @@ def render_scene_views(scene, idxs, rgba=True, n_quad=256):
         else:
             img = rgb.clamp(0, 1).reshape(h, w, 3)
         out.append((img.cpu().numpy() * 255.0 + 0.5).astype(np.uint8))
+    return np.stack(out)
+
+
+@torch.no_grad()
+def render_scene_labels(scene, idxs, n_quad=256):
+    """per-pixel classes of an analytic scene's views (synthetic.LegoProxy.ground_truth_labels: parts 0-3, 4 = sky,
+    256 = ignore) -> (n, h, w) int64; export_tnt / export_colmap take them as `labels`"""
+    w, h = scene.img_wh
+    pix = torch.arange(w * h, device=scene.device)
+    out = []
+    for i in idxs:
+        o, d = scene.rays(torch.full((w * h,), int(i), dtype=torch.long, device=scene.device), pix)
+        out.append(scene.ground_truth_labels(o, d, n_quad=n_quad).reshape(h, w).cpu().numpy())
     return np.stack(out)
 
 

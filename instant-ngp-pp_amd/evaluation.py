@@ -9,7 +9,10 @@ a held-out split (what the reference's render.py:50-218 and validation step trai
   frame_images(results, pose, scale, num_classes, want, img_wh) -> {name: uint8 image} through ngp_frame_pack (I2);
                                                                    out_wh= brings a supersampled frame back to the
                                                                    image size (ngp_resize_bicubic_u8, I3)
-  evaluate_split(model, test_set, ...)                          -> {'psnr': [...], 'ssim': [...]} per held-out image
+  evaluate_split(model, test_set, ...)                          -> {'psnr': [...], 'ssim': [...]} per held-out image,
+                                                                   with labels also 'sem_acc', 'sem_miou', 'sem_valid'
+  semantic_summary(res)                                         -> (pixel-weighted accuracy, mean IoU) of the split
+  semantic_metrics(pred, label, classes)                        -> (accuracy, mean IoU) of one label image on the device
 """
 import torch
 
@@ -154,12 +157,46 @@ def image_metrics(rgb, gt, img_wh):
 
 
 @torch.no_grad()
+def semantic_metrics(pred, label, classes):
+    """(accuracy, mean IoU) of predicted classes against a label image, both (h*w) integers, as two 0-dim tensors on the
+    device.  A pixel is valid iff 0 <= label < classes (256, 255, ... are ignored, as in the loss).  accuracy: share of the
+    valid pixels whose prediction equals the label; mean IoU: over the classes that occur in the label or the prediction
+    among the valid pixels.  Both from ONE bincount of label * classes + pred; NaN when no pixel is valid."""
+    C = int(classes)
+    pred = pred.reshape(-1).to(torch.int64)
+    label = label.reshape(-1).to(pred.device, torch.int64)
+    valid = (label >= 0) & (label < C)
+    # invalid pixels land in one extra bin behind the C * C cells
+    cell = torch.where(valid, label.clamp(0, C - 1) * C + pred.clamp(0, C - 1), C * C)
+    conf = torch.bincount(cell, minlength=C * C + 1)[:C * C].reshape(C, C).to(torch.float64)   # [label, prediction]
+    hit = conf.diagonal()
+    union = conf.sum(0) + conf.sum(1) - hit
+    seen = union > 0
+    iou = torch.where(seen, hit / union.clamp(min=1), torch.zeros_like(hit))
+    return hit.sum() / conf.sum(), iou.sum() / seen.sum()
+
+
+def semantic_summary(res):
+    """(accuracy over all valid pixels of the split, mean IoU over the images that have valid pixels) from evaluate_split's
+    dictionary; images without a valid label (sem_acc NaN) take no part; (None, None) when no image has one"""
+    rows = [(a, m, n) for a, m, n in zip(res["sem_acc"], res["sem_miou"], res["sem_valid"]) if n > 0]
+    if not rows:
+        return None, None
+    total = sum(n for _, _, n in rows)
+    return sum(a * n for a, _, n in rows) / total, sum(m for _, m, _ in rows) / len(rows)
+
+
+@torch.no_grad()
 def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs):
     """Per-image PSNR and SSIM of a held-out split through render(test_time=True) (train.py:347-392): rgb is clamped
     to [0, 1] and compared with the split's ground truth -> {'psnr': [floats], 'ssim': [floats]}.  `on_image(i, rgb,
     results)` is called with each clamped (h*w, 3) image and its results dictionary (to save frames).  The metrics stay
-    on the device until every image is rendered: one read-back at the end."""
-    psnrs, ssims = [], []
+    on the device until every image is rendered: one read-back at the end.  When a test item carries 'label' the
+    dictionary also holds 'sem_acc' and 'sem_miou' (semantic_metrics of results['semantic'] with render_kwargs'
+    num_classes, default 7), one per image, NaN for an image without a valid label, and 'sem_valid', the number of valid
+    pixels of each image (the weights of an accuracy over the split; semantic_summary forms it)."""
+    psnrs, ssims, accs, mious, valids = [], [], [], [], []
+    classes = render_kwargs.get("num_classes", 7)
     for i in range(len(test_set)):
         s = test_set[i]
         if "rgb" not in s:
@@ -168,8 +205,18 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
         p, q, rgb = image_metrics(results["rgb"], s["rgb"], test_set.img_wh)
         psnrs.append(p)
         ssims.append(q)
+        if "label" in s:
+            a, m = semantic_metrics(results["semantic"], s["label"], classes)
+            accs.append(a)
+            mious.append(m)
+            lab = s["label"].reshape(-1)
+            valids.append(((lab >= 0) & (lab < classes)).sum().to(a.device))
         if on_image is not None:
             on_image(i, rgb, results)
     if not psnrs:
         return {"psnr": [], "ssim": []}
-    return {"psnr": torch.stack(psnrs).tolist(), "ssim": torch.stack(ssims).tolist()}
+    out = {"psnr": torch.stack(psnrs).tolist(), "ssim": torch.stack(ssims).tolist()}
+    if accs:
+        out.update(sem_acc=torch.stack(accs).tolist(), sem_miou=torch.stack(mious).tolist(),
+                   sem_valid=torch.stack(valids).tolist())
+    return out

@@ -322,7 +322,7 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
         elif isinstance(v, RayCodes):
             kwargs[k] = v.for_batch(rays_a)
     fused = kwargs.pop('_fused_loss', None)
-    if fused is not None and _fused_tail_ok(model, kwargs, exp_step_factor, classes):
+    if fused is not None and _fused_tail_ok(model, kwargs, exp_step_factor, classes, fused):
         return _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs)
     sigmas, rgbs, normals_raw, normals_pred, sems = model(xyzs, dirs, **kwargs)
     results['sigma'] = sigmas
@@ -352,11 +352,14 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     return results
 
 
-def _fused_tail_ok(model, kwargs, exp_step_factor, classes):
+def _fused_tail_ok(model, kwargs, exp_step_factor, classes, fused=None):
     """the one-launch render + loss tail covers the default recipe: sigmoid colours (no tone mapper), black or random
-    constant background (no skybox network), detached analytic normals, at most 8 classes"""
+    constant background (no skybox network), detached analytic normals, at most 8 classes (the semantic form of the
+    tail, fused[3] == 'sem': 1 to 16)"""
+    sem = fused is not None and len(fused) > 3 and isinstance(fused[3], str) and fused[3] == 'sem'
     return (getattr(model, 'rgb_act', 'Sigmoid') == 'Sigmoid' and not kwargs.get('use_skybox', False)
-            and not getattr(model, 'differentiable_normals', False) and classes <= 8 and hasattr(model, '_field'))
+            and not getattr(model, 'differentiable_normals', False) and (1 <= classes <= 16 if sem else classes <= 8)
+            and hasattr(model, '_field'))
 
 
 class _RenderLossFn(torch.autograd.Function):
@@ -427,15 +430,63 @@ class _RenderLossMaskedFn(torch.autograd.Function):
         return (d_sig, d_rgb, d_mask.view(ctx.mask_shape)) + (None,) * 15
 
 
+class _RenderLossSemFn(torch.autograd.Function):
+    """_RenderLossFn for NeRFLoss(semantic=True) (ngp_render_loss_fused_sem): `labels` (n_rays) int64, one per ray; a label
+    outside [0, classes) is ignored (256, the reference's ignore_index, and an 8-bit 255 among them).  The class logits
+    are a further differentiable input whose gradient the same launch computes, and terms (6) = [loss, rgb, opacity,
+    distortion, CELoss, sky_depth].  A batch without a valid label has CELoss = 0 and a zero logit gradient, where torch's
+    cross-entropy gives NaN.  Differentiable through terms[0] only."""
+
+    @staticmethod
+    def forward(ctx, sig, rgb_o, sem_logits, dsig_dx, np_raw, dirs, deltas, ts, rays_a, rgb_gt, labels, scale3, T_thr,
+                classes, lambda_opa, lambda_dist, lambda_sem, lambda_sky, rgb_bg=None):
+        n, nr = sig.shape[0], rays_a.shape[0]
+        dev = sig.device
+        f32 = torch.float32
+        if labels.numel() != nr or labels.dtype != torch.int64:
+            raise ValueError(f"labels must be {nr} int64 entries, one per ray: got {tuple(labels.shape)} {labels.dtype}")
+        if not 1 <= classes <= 16 or sem_logits.shape[1] < classes:
+            raise ValueError(f"the semantic tail takes 1 to 16 classes: got {classes} for logits {tuple(sem_logits.shape)}")
+        total = torch.empty(nr, dtype=torch.int64, device=dev)
+        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
+        ws, d_sig, d_rgb, d_sem = E(n), E(n), E(n, 3), E(n, classes)
+        acc = E(8)                                   # [terms (6) | vr_samples (int64)]: adjacent, cleared by one memset
+        terms, vr = acc[:6], acc[6:8].view(torch.int64)
+        n_valid = torch.empty(8, dtype=torch.int32, device=dev)    # NGP_SEM_WS_INTS: [n_valid | - | two double sums | count | -]
+        call("render_loss_fused_sem", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
+             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, labels.contiguous().view(-1), float(lambda_sem), float(lambda_sky),
+             float(T_thr), int(classes), nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal,
+             sem, ws, Ro, Rp, terms, d_sig, d_rgb, n_valid, d_sem)
+        ctx.save_for_backward(d_sig, d_rgb, d_sem)
+        ctx.pad = sem_logits.shape[1] - classes
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
+        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
+
+    @staticmethod
+    def backward(ctx, g_terms, *_unused):
+        d_sig, d_rgb, d_sem = ctx.saved_tensors
+        if ctx.pad:
+            d_sem = F.pad(d_sem, (0, ctx.pad))
+        return (d_sig, d_rgb, d_sem) + (None,) * 16
+
+
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
     """fused = (rgb_gt, lambda_opa, lambda_distortion) or, for the embed_msk recipe, those three followed by
-    (mask (n_rays[, 1]), size_delta)"""
+    (mask (n_rays[, 1]), size_delta), or, for the semantic recipe, by ('sem', labels (n_rays) int64, lambda_sem,
+    lambda_sky)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
     rgb_gt, lambda_opa, lambda_dist = fused[:3]
     rgb_bg = None
     if kwargs.get('exp_step_factor', 0.) != 0 and kwargs.get('random_bg', False):
         rgb_bg = torch.rand(3, device=xyzs.device)      # rendering.py:239 (drawn at the same place in the RNG stream)
-    if len(fused) == 5:
+    if len(fused) == 7 and fused[3] == 'sem':
+        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossSemFn.apply(
+            sig, rgb_o, sem_logits, dsig_dx, np_raw, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
+            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5],
+            fused[6], rgb_bg)
+    elif len(fused) == 5:
         (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossMaskedFn.apply(
             sig, rgb_o, fused[3], dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
             rgb_gt.contiguous(), model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[4], rgb_bg)

@@ -15,15 +15,32 @@ import torch
 SIGMA_IN = 60.0
 
 
-def analytic_sigma(x):
-    """x (...,3) world coordinates -> sigma (...)"""
+SKY_LABEL, IGNORE_LABEL = 4, 256   # the class losses.py:122 compares with, nn.CrossEntropyLoss's ignore_index there
+
+
+def _solids(x):
     ax = x.abs()
     box1 = (ax[..., 0] < 0.35) & (ax[..., 1] < 0.10) & (ax[..., 2] < 0.10)
     box2 = (ax[..., 0] < 0.10) & (ax[..., 1] < 0.30) & ((x[..., 2] + 0.15).abs() < 0.08)
     box3 = ((x[..., 0] - 0.15).abs() < 0.08) & ((x[..., 1] + 0.1).abs() < 0.08) & (ax[..., 2] < 0.33)
     r = torch.linalg.norm(x - torch.tensor([-0.15, 0.12, 0.12], device=x.device), dim=-1)
     shell = (r < 0.2) & (r > 0.15)
+    return box1, box2, box3, shell
+
+
+def analytic_sigma(x):
+    """x (...,3) world coordinates -> sigma (...)"""
+    box1, box2, box3, shell = _solids(x)
     return torch.where(box1 | box2 | box3 | shell, SIGMA_IN, 0.0)
+
+
+def analytic_part(x):
+    """x (...,3) -> int64 (...): the solid a point belongs to, 0-3 for box1, box2, box3, shell (the first that contains
+    it), -1 in empty space"""
+    part = torch.full(x.shape[:-1], -1, dtype=torch.int64, device=x.device)
+    for k, inside in reversed(list(enumerate(_solids(x)))):
+        part = torch.where(inside, k, part)
+    return part
 
 
 def analytic_rgb(x):
@@ -98,6 +115,36 @@ class LegoProxy:
         if white_bg:
             out_rgb = out_rgb + (1 - out_op)[:, None]
         return out_rgb, out_op
+
+    @torch.no_grad()
+    def ground_truth_labels(self, rays_o, rays_d, n_quad=1024):
+        """per-ray class of the analytic scene by the quadrature of ground_truth -> int64 (N): the part (analytic_part,
+        0-3) with the largest composited weight; SKY_LABEL (4) where the opacity is below 0.1; IGNORE_LABEL (256) where
+        the ray grazes (0.1 <= opacity < 0.9) or where the best part holds less than 0.6 of the opacity"""
+        inv = 1.0 / rays_d
+        a, b = (-0.5 - rays_o) * inv, (0.5 - rays_o) * inv
+        t1 = torch.minimum(a, b).amax(-1).clamp(min=0)
+        t2 = torch.maximum(a, b).amin(-1)
+        t2 = torch.where(t2 > t1, t2, t1)
+        out = torch.empty(len(rays_o), dtype=torch.int64, device=rays_o.device)
+        step = (t2 - t1) / n_quad
+        chunk = 16384
+        for s in range(0, len(rays_o), chunk):
+            sl = slice(s, s + chunk)
+            k = torch.arange(n_quad, device=rays_o.device, dtype=torch.float32) + 0.5
+            t = t1[sl, None] + step[sl, None] * k[None, :]
+            x = rays_o[sl, None, :] + rays_d[sl, None, :] * t[..., None]
+            part = analytic_part(x)
+            dl = step[sl, None] * rays_d[sl].norm(dim=-1, keepdim=True)
+            alpha = torch.where(part >= 0, 1 - torch.exp(-SIGMA_IN * dl), torch.zeros_like(dl))
+            T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1 - alpha], 1), 1)[:, :-1]
+            w = alpha * T
+            share = torch.stack([(w * (part == c)).sum(1) for c in range(4)], -1)
+            op = share.sum(-1)
+            best, lab = share.max(-1)
+            lab = torch.where((op < 0.9) | (best < 0.6 * op), IGNORE_LABEL, lab)
+            out[sl] = torch.where(op < 0.1, SKY_LABEL, lab)
+        return out
 
     @torch.no_grad()
     def occupancy_from_analytic(self, model, supersample=2):

@@ -27,7 +27,7 @@ import torch.distributed as dist
 from ._lib import call
 from .appearance import RayCodes
 from .losses import NeRFLoss, nerf_loss_and_grads
-from .rendering import MAX_SAMPLES, MarchAhead, render
+from .rendering import MAX_SAMPLES, MarchAhead, _fused_tail_ok, render
 
 _f32 = torch.float32
 
@@ -156,8 +156,17 @@ def shard_seed(base_seed, rank):
 class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
-                 force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6):
-        """pose_refiner: a pose.PoseRefiner (the reference's --optimize_ext, train.py:143-149, 225-230).  step() then takes
+                 force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
+                 semantic=False):
+        """semantic: the reference's render_semantic recipe (train.py:197, 293; NeRFLoss(semantic=True), losses.py:120-123)
+        on the fused render + loss tail (ngp_render_loss_fused_sem).  step() then needs labels= (n_rays) int64; a label
+        outside [0, num_classes) is ignored (256, the reference's ignore_index, and the 255 an 8-bit label image holds in
+        its place), and a batch without a valid label has a zero CE term where torch's cross-entropy gives NaN.  The
+        semantic head's backward adds to the colour table's gradient, outside the norm bound: the step takes the exact
+        gradient norm.  Combines with embedding_a and random_bg; not with msk_model, pose_refiner, a skybox, a tone-mapped
+        model or an optional term in loss_kwargs.  loss_kwargs={'semantic': True} with step(target={'label': ...}) remains
+        the launch-per-operation route through the NeRFLoss module.
+        pose_refiner: a pose.PoseRefiner (the reference's --optimize_ext, train.py:143-149, 225-230).  step() then takes
         img_idxs= and pix_idxs= instead of ray tensors and forms the rays itself from the current dR, dT; the samples enter
         the field requiring a gradient, which ngp_pose_rays_bwd reduces per image.  dR and dT live in a small buffer of their
         own OUTSIDE the flat store, as the reference keeps them out of net_opt: their own Adam at the constant `pose_lr` (no
@@ -208,6 +217,18 @@ class NGPTrainer:
             # gradient for dirs), a skybox (a function of rays_d) and second-order normals would leave it silently incomplete
             raise ValueError("pose refinement runs on the fused render + loss tail: a trainer with a pose_refiner takes no "
                              "optional loss term, no skybox and no differentiable normals")
+        self.semantic = bool(semantic)
+        if self.semantic:
+            why = [w for w, bad in (("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
+                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                                    ("an optional term in loss_kwargs", optional),
+                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
+                                    (f"num_classes = {num_classes} outside 1..16", not 1 <= int(num_classes) <= 16),
+                                    (f"a model with {model.semantic_header.n_output_dims} classes for num_classes = "
+                                     f"{num_classes}", model.semantic_header.n_output_dims != int(num_classes))) if bad]
+            if why:
+                raise ValueError("semantic=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -361,7 +382,7 @@ class NGPTrainer:
 
     def _unit_seed(self, terms):
         s = getattr(self, '_seed4', None)
-        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model)
+        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model, 6 semantic)
             s = self._seed4 = torch.tensor([1.0] + [0.0] * (terms.numel() - 1), device=terms.device)
         return s
 
@@ -381,9 +402,12 @@ class NGPTrainer:
     def lr(self):
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
-    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None,
+    def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None, labels=None,
              **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
+
+        labels: (n_rays) int64 class of every ray, required by a trainer built with semantic=True (which then takes no
+        target= and no per-step loss term).
 
         uvi: (n_rays, 3) input of the trainer's msk_model (implicit_mask.uvi), required when there is one.
         img_idxs: (n_rays) image index of every ray, required when the trainer has an embedding_a or a pose_refiner.
@@ -405,6 +429,16 @@ class NGPTrainer:
             raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
         if self.embedding_a is not None and img_idxs is None:
             raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
+        if self.semantic:
+            if labels is None:
+                raise ValueError("this trainer was built with semantic=True: step() needs labels= (the class of every ray)")
+            if target or loss_kwargs:
+                raise ValueError("this trainer was built with semantic=True: the step stays on the fused render + loss tail "
+                                 "and takes no target= and no per-step loss term")
+            if not rays_o.is_cuda:
+                raise RuntimeError("semantic=True needs CUDA tensors: the fused tail has no other route")
+        elif labels is not None:
+            raise ValueError("labels= is for a trainer built with semantic=True")
         ref = self.pose_refiner
         if ref is not None:
             if rays_o is not None or rays_d is not None or next_rays is not None:
@@ -450,6 +484,13 @@ class NGPTrainer:
             extra['_fused_loss'] = (rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion)
             if masked:   # size_delta of the step being taken (losses.py:60-69, 85)
                 extra['_fused_loss'] += (mask, self.loss_fn.Annealing.getWeight(self.global_step))
+            if self.semantic:
+                extra['_fused_loss'] += ('sem', labels.view(-1).to(torch.int64), self.loss_fn.lambda_semantic,
+                                         self.loss_fn.lambda_sky)
+                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
+                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the labels
+                    raise RuntimeError("semantic=True: the model no longer fits the fused semantic tail "
+                                       "(rendering._fused_tail_ok); the labels would be left out of the loss")
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
@@ -461,10 +502,16 @@ class NGPTrainer:
         self._norm_share_armed, self._norm_share_fired = True, 0   # one backward follows, then the optimizer step
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
         # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
-        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None)
+        # (the semantic head adds to the colour table's gradient: outside the bound, the exact norm from the start)
+        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
+                                and not self.semantic)
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
+        if self.semantic and '_loss_terms' not in results:
+            # (rgb_act / differentiable_normals changed after construction, a model without _field, ...)
+            raise RuntimeError("semantic=True: render() did not take the fused semantic tail (rendering._fused_tail_ok); the "
+                               "labels would be left out of the loss")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]

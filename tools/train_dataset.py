@@ -12,6 +12,9 @@ reference: train.py:82-392).  GPU only.
       --random_bg --embed_a --embed_a_len 8 --embed_msk --ckpt_path out/playground.ckpt   # the reference's Playground recipe
   python tools/train_dataset.py --make_proxy /tmp/proxy --downsample 0.125 --num_epochs 2 --optimize_ext --pose_lr 1e-4 \
       --perturb_poses 0.02 0.5 --ckpt_path out/poses.ckpt   # pose refinement from perturbed poses: errors before / after
+  python tools/train_dataset.py --make_proxy /tmp/proxy_sem --dataset_name tnt --downsample 0.125 --num_epochs 2 \
+      --render_semantic --num_classes 5 --ckpt_path out/sem.ckpt   # semantic head on the labelled proxy: accuracy, mIoU
+      # (--scale must enclose the cameras, here it defaults to 2: the sky term puts density at the far end of the volume on rays labelled 4)
 """
 import argparse
 import json
@@ -26,7 +29,7 @@ import ngp_amd  # noqa: F401
 from ngp_amd import ckpt
 from ngp_amd.appearance import FrameEmbedding
 from ngp_amd.datasets import dataset_dict, write_synthetic_dataset
-from ngp_amd.evaluation import evaluate_split
+from ngp_amd.evaluation import evaluate_split, semantic_summary
 from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
@@ -34,8 +37,9 @@ from ngp_amd.pose import PoseRefiner, perturb_poses, pose_errors
 from ngp_amd.trainer import NGPTrainer
 
 
-def build_model(scale, device, embed_a=False, embed_a_len=4):
-    model = (NGP(scale=scale, embed_a=True, embed_a_len=embed_a_len) if embed_a else NGP(scale=scale)).to(device)
+def build_model(scale, device, embed_a=False, embed_a_len=4, num_classes=7):
+    more = dict(embed_a=True, embed_a_len=embed_a_len) if embed_a else {}
+    model = NGP(scale=scale, classes=num_classes, **more).to(device)
     G = model.grid_size
     model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=device))
     coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=device)] * 3, indexing="ij"), -1)
@@ -43,16 +47,52 @@ def build_model(scale, device, embed_a=False, embed_a_len=4):
     return model
 
 
+def labels_of_split(ds):
+    """makes ds.labels[k] the label image of ds's k-th image.  The tnt loader reads the labels of its split; the colmap
+    loader, as upstream, reads those of ALL registered frames while rays and poses are cut to the split (train: frame
+    i with i % 8 != 0, test: i % 8 == 0), so BaseDataset would pair image k of the split with the labels of frame k.  Here
+    the rows of the split's frames are kept; any other mismatch is an error.  Idempotent."""
+    n_img, n_lab = len(ds.poses), ds.labels.shape[0]
+    if n_lab == n_img:
+        return ds
+    keep = None
+    if type(ds).__name__ == "ColmapDataset" and ds.split in ("train", "test") and "HDR-NeRF" not in ds.root_dir:
+        keep = [i for i in range(n_lab) if (i % 8 != 0) == (ds.split == "train")]
+    if keep is None or len(keep) != n_img:
+        raise ValueError(f"{n_lab} label images for the {n_img} images of the {ds.split} split: cannot tell which belongs to which")
+    ds.labels = ds.labels[torch.as_tensor(keep, device=ds.labels.device)].contiguous()
+    return ds
+
+
+def cameras_outside(train_set, scale):
+    """largest |coordinate| of a training camera if it lies outside the model's volume [-scale, scale]^3, else None"""
+    far = float(torch.as_tensor(train_set.poses)[:, :, 3].abs().max())
+    return far if far > scale else None
+
+
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
-          render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6):
+          render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
+          num_classes=7):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
-    with the sampler's image and pixel indices (the trainer then forms the rays itself, and nothing is marched ahead)"""
+    with the sampler's image and pixel indices (the trainer then forms the rays itself, and nothing is marched ahead);
+    semantic: the semantic head of --render_semantic, fed with the sampler's labels (num_classes of them)"""
     train_set.batch_size = batch_size
+    if semantic:
+        if not hasattr(train_set, "labels"):
+            raise ValueError("--render_semantic needs per-pixel labels: the dataset has none (tnt / colmap layouts read "
+                             "semantic/*.pgm when loaded with use_sem=True)")
+        labels_of_split(train_set)
+        dev = next(model.parameters()).device
+        train_set.labels = train_set.labels.to(dev)   # the sampler indexes them where the pixel indices are drawn
     more = {} if embedding_a is None else {"embedding_a": embedding_a}
     if pose_refiner is not None:
         more.update(pose_refiner=pose_refiner, pose_lr=pose_lr)
+    if semantic:
+        more.update(semantic=True)
+    if semantic or num_classes != 7:
+        more.update(num_classes=num_classes)
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
                          exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
     n_imgs = len(train_set.poses)
@@ -65,7 +105,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             uvi = None
             if msk_model is not None:
                 uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(idx.device)
-            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous()
+            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None
         o, d = train_set.batch_rays(s)
         uvi = None
         if msk_model is not None:
@@ -73,7 +113,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         idx = None
         if embedding_a is not None:   # one index per ray (the same_image strategy draws ONE image per batch)
             idx = torch.as_tensor(s["img_idxs"], device=o.device).to(torch.int64).reshape(-1).expand(o.shape[0]).contiguous()
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None
+        lab = s["label"].to(o.device, torch.int64).contiguous() if semantic else None
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab
 
     import gc
     gc.collect()
@@ -86,6 +127,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         more = {} if cur[4] is None else {"img_idxs": cur[4]}
         if cur[5] is not None:
             more["pix_idxs"] = cur[5]
+        if cur[6] is not None:
+            more["labels"] = cur[6]
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
         if log_every and (i + 1) % log_every == 0:
@@ -138,13 +181,15 @@ def evaluate(model, test_set, chunk=131072, save_dir=None, exp_step_factor=0.0):
                           exp_step_factor=exp_step_factor)["psnr"]
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--root_dir")
     ap.add_argument("--dataset_name", default="nerf", choices=sorted(dataset_dict))
     ap.add_argument("--make_proxy", help="write the analytic lego-proxy scene to this directory first and train on it")
     ap.add_argument("--downsample", type=float, default=1.0)
-    ap.add_argument("--scale", type=float, default=0.5)
+    ap.add_argument("--scale", type=float, default=None,
+                    help="half-width of the model's volume; default 0.5, and 2 with --make_proxy --render_semantic (the "
+                         "exported cameras sit at radius 0.83 and the sky term needs them inside the volume)")
     ap.add_argument("--exp_step_factor", type=float, default=0.0, help="1/256 for unbounded scenes (opt.py)")
     ap.add_argument("--random_bg", action="store_true")
     ap.add_argument("--embed_msk", action="store_true",
@@ -166,11 +211,43 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-2)
     ap.add_argument("--save_dir")
     ap.add_argument("--ckpt_path")
-    args = ap.parse_args()
+    ap.add_argument("--render_semantic", action="store_true",
+                    help="load per-pixel labels (semantic/*.pgm, use_sem=True) and train the semantic head on them (the "
+                         "reference's --render_semantic); the JSON line gains test_sem_acc_mean and test_sem_miou_mean.  "
+                         "Choose --scale so that the volume encloses the cameras: the sky term rewards depth on rays labelled 4")
+    ap.add_argument("--num_classes", type=int, default=7, help="classes of the semantic head, 1 to 16")
+    args = ap.parse_args(argv)
+    if not 1 <= args.num_classes <= 16:
+        ap.error("--num_classes must lie in [1, 16]")
+    if args.make_proxy and args.render_semantic and args.dataset_name not in ("tnt", "colmap"):
+        ap.error("--make_proxy with --render_semantic writes a labelled scene: --dataset_name tnt or colmap (the layouts "
+                 "that carry semantic/*.pgm)")
+    if args.scale is None:
+        args.scale = 2.0 if args.make_proxy and args.render_semantic else 0.5
+    if args.render_semantic and (args.embed_msk or args.optimize_ext):
+        ap.error("--render_semantic combines with --embed_a and --random_bg, not with --embed_msk or --optimize_ext")
     if not 1 <= args.embed_a_len <= 32:
         ap.error("--embed_a_len must lie in [1, 32]")
     if args.perturb_poses and not args.optimize_ext:
         ap.error("--perturb_poses needs --optimize_ext")
+    return args
+
+
+def make_labelled_proxy(root, fmt, scene, n_quad=256):
+    """the analytic proxy with per-pixel labels in the tnt or colmap layout, every 8th view held out"""
+    from ngp_amd.datasets import export
+    n = scene.poses.shape[0]
+    images = export.render_scene_views(scene, range(n), rgba=False, n_quad=n_quad)
+    labels = export.render_scene_labels(scene, range(n), n_quad=n_quad)
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    if fmt == "colmap":
+        return export.export_colmap(root, images, c2w, K, labels=labels)
+    return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], labels=labels)
+
+
+def main():
+    args = parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(20220806)
     root = args.root_dir
@@ -178,11 +255,28 @@ def main():
         from ngp_amd.synthetic import LegoProxy
         wh = int(800 * args.downsample)
         scene = LegoProxy(n_images=108, img_wh=(wh, wh), device=dev)
-        root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
+        if args.render_semantic:
+            root = make_labelled_proxy(args.make_proxy, args.dataset_name, scene)
+            args.downsample = 1.0   # (these layouts are written at the size they are read at)
+        else:
+            root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
     loader = dataset_dict[args.dataset_name]
-    train_set = loader(root, "train", args.downsample, device=dev)
-    test_set = loader(root, "test", args.downsample, device=dev)
-    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len)
+    sem = dict(use_sem=True, num_classes=args.num_classes) if args.render_semantic else {}
+    train_set = loader(root, "train", args.downsample, device=dev, **sem)
+    test_set = loader(root, "test", args.downsample, device=dev, **sem)
+    if args.render_semantic and not hasattr(train_set, "labels"):
+        raise SystemExit(f"--render_semantic: {root} holds no labels (semantic/*.pgm) for the {args.dataset_name} loader")
+    if args.render_semantic:
+        labels_of_split(train_set)
+        if hasattr(test_set, "labels"):
+            labels_of_split(test_set)
+        far = cameras_outside(train_set, args.scale)
+        if far is not None:
+            print(f"warning: --render_semantic with cameras outside the volume (a camera coordinate of {far:.2f}, --scale "
+                  f"{args.scale}): the sky term rewards depth on rays labelled 4 and puts density at the far end of the volume, "
+                  "between the scene and the cameras opposite; held-out PSNR suffers.  Choose --scale so that the volume "
+                  "encloses the cameras.", file=sys.stderr)
+    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len, args.num_classes)
     msk_model = implicit_mask().to(dev) if args.embed_msk else None
     embedding_a = FrameEmbedding(args.embed_a_len, train_set.poses).to(dev) if args.embed_a else None
     pose_refiner = true_poses = None
@@ -193,12 +287,15 @@ def main():
     t0 = time.perf_counter()
     train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
-          msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr)
+          msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
+          semantic=args.render_semantic, num_classes=args.num_classes)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
     if embedding_a is not None:   # train.py:153-154: the test split is rendered with the code of training image 0
         more["embedding_a"] = embedding_a(0).detach()
+    if args.render_semantic or args.num_classes != 7:
+        more["num_classes"] = args.num_classes
     res = evaluate_split(model, test_set, on_image=_save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None,
                          exp_step_factor=args.exp_step_factor, **more)
     psnrs, ssims = res["psnr"], res["ssim"]
@@ -208,6 +305,11 @@ def main():
     out = {"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
            "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
            "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}
+    if "sem_acc" in res:
+        acc, miou = semantic_summary(res)   # accuracy over all valid pixels; images without a valid label take no part
+        out.update(test_sem_acc_mean=acc, test_sem_acc=res["sem_acc"], test_sem_miou_mean=miou,
+                   test_sem_miou=res["sem_miou"], test_sem_valid=res["sem_valid"],
+                   num_classes=args.num_classes)
     if pose_refiner is not None:   # mean translation (scene units) and rotation (degrees) error against the dataset's poses
         before = pose_errors(pose_refiner.poses.cpu(), true_poses.cpu())
         after = pose_errors(pose_refiner.refined_poses().detach().cpu(), true_poses.cpu())
