@@ -303,6 +303,28 @@ int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const floa
                               float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                               float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* sem_ws,
                               float* dL_dsem_logits, void* stream);
+/* The same launch for NeRFLoss's normal_mono term (losses.py:111-118): normals_gt (n_rays, 3), indexed by ray like
+ * target_rgb.  With N = normal_pred, N^ = N / max(|N|, 1e-12), g^ = g / max(|g|, 1e-12) (F.normalize's defaults):
+ * terms (5) = [loss, rgb, opacity, distortion, normal_mono],
+ *   normal_mono = lambda_nm / (3 n_rays) sum_r sum_c (|N^_c - g^_c| - 0.1 N^_c g^_c).
+ * A target whose three components are exactly 0 marks a pixel without a normal: the ray adds nothing to the term and
+ * its samples get a zero gradient; the divisor stays 3 n_rays.  With every target non-zero this is the module's term.
+ * dL_dnormal_head (N, 3), dense: the term through N^, the composited sum and the per-sample -normalize(head, eps 1e-6)
+ * with the weights held constant (composite_train_bw drops dL_dnormal_pred from dL_dsigmas, volumerendering.cu:234-241,
+ * so dL_dsigmas and dL_drgbs are those of ngp_render_loss_fused); exactly zero behind a ray's stop and for a sample
+ * without weight.  nrm_ws: device int32 (NGP_NRM_WS_INTS = 4, 8-byte aligned) workspace: the term's sum in double and the
+ * count of finished workgroups (one rounding instead of a float atomic per workgroup).  vr_samples may sit at terms + 6
+ * floats and nrm_ws at terms + 8 floats (one fill, one launch).  classes <= 8.  With lambda_nm = 0 every output shared
+ * with ngp_render_loss_fused is that entry's. */
+#define NGP_NRM_WS_INTS 4
+int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, const float* normals_gt, float lambda_nm,
+                              float T_threshold, int classes, int n_rays, float lambda_opacity, float lambda_distortion,
+                              int64_t* total_samples, int64_t* vr_samples, float* opacity, float* depth, float* rgb,
+                              float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
+                              float* dL_dsigmas, float* dL_drgbs, int* nrm_ws, float* dL_dnormal_head, void* stream);
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,
                        float* normals_diff, float* normals_ori, void* stream);
 int ngp_neg_normalize(const float* x, int64_t ldx, const float* scale3 /* device (3) or NULL */, int64_t n,

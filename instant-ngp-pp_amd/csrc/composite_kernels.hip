@@ -587,6 +587,13 @@ struct RenderLossArgs {
     int* sem_ws;
     float lam_sem, g_sky;
     float* d_sem;
+    // NRM only (NeRFLoss's normal_mono term, losses.py:111-118): the target normal of every ray (all three components
+    // exactly 0: the pixel has none), the workspace (NRM_WS_* below, cleared by the entry's fill), g_nm = lambda_nm / (3 R),
+    // and the loss's gradient w.r.t. the normal head's raw output, dense (n, 3)
+    const float* nrm_gt;
+    int* nrm_ws;
+    float g_nm;
+    float* d_np;
 };
 
 // The semantic tail's workspace, NGP_SEM_WS_INTS = 8 int32, 8-byte aligned: [0] n_valid, [2:4] and [4:6] two doubles, the
@@ -632,16 +639,28 @@ __global__ void __launch_bounds__(1024) count_valid_labels_kernel(const int64_t*
 //   terms[5] = lambda_sky / R sum [y == 4] exp(-depth) (the literal 4, losses.py:122), seed g_D = -g_sky [y == 4] exp(-D),
 //              which enters d_sigmas as delta_s g_D (t_s T_s - (D - d_s)), d_s the inclusive prefix of w t: the scan pass C
 //              forms for the distortion term anyway.
-template <int CMAX, int W, bool MASKED, bool SEM>
+// NRM: with N = normal_pred (the composited head normals, pass A's aN*), g the ray's target normal, N^ = N / max(|N|, 1e-12)
+// and g^ = g / max(|g|, 1e-12) (F.normalize's defaults) and a ray whose target is (0, 0, 0) left out of everything below,
+//   terms[4] = lambda_nm / (3 R) sum_r sum_c (|N^_c - g^_c| - 0.1 N^_c g^_c)        (NeRFLoss._normal_mono, mean over R x 3)
+//   seed q_c = lambda_nm / (3 R) (sign(N^_c - g^_c) - 0.1 g^_c), sign(0) = 0 (torch's abs backward),
+//        g_N = (q - N^ <N^, q>) / |N| where |N| > 1e-12, else q / 1e-12 (the clamp is then the divisor: rays without weight),
+//   d_np[s] = -(w_s / |h_s|) (g_N - h^ <h^, g_N>) with h the head's raw output of the sample and h^ = h / |h| where
+//        |h| > 1e-6, else -w_s g_N / 1e-6; exactly 0 behind the stop, for a sample without weight and on a ray without
+//        a target.  The weights are constants of this term (composite_train_bw drops dL_dnormal_pred from dL_dsigma,
+//        volumerendering.cu:234-241): d_sigmas and d_rgbs are the default entry's.
+// The term is summed in double through the workspace and rounded once by the last workgroup, as the SEM terms are.
+constexpr int NRM_WS_SUM = 0, NRM_WS_DONE = 2;   // NGP_NRM_WS_INTS = 4 int32, 8-byte aligned: one double, the workgroup count
+template <int CMAX, int W, bool MASKED, bool SEM, bool NRM>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
     static_assert(!(MASKED && SEM), "SEM x MASKED is not built");
+    static_assert(!(NRM && (MASKED || SEM)), "NRM x MASKED and NRM x SEM are not built");
     constexpr int RPB = 256 / W;          // rays per block
-    __shared__ float part[MASKED ? 4 : SEM ? 5 : 3][RPB];
+    __shared__ float part[MASKED ? 4 : SEM ? 5 : NRM ? 4 : 3][RPB];
     __shared__ unsigned long long part_n[RPB];
     Seg sg; int lane;
     const bool have = seg_load_w<W>(p.rays_a, p.n_rays, sg, lane);
-    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f, s_ce = 0.0f, s_sky = 0.0f;
+    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f, s_ce = 0.0f, s_sky = 0.0f, s_nm = 0.0f;
     unsigned long long n_used = 0;
     const int n_valid = SEM ? p.sem_ws[SEM_WS_NVALID] : 0;
     if (have) {
@@ -721,6 +740,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                     for (int cc = 0; cc < CMAX; cc++)
                         if (cc < p.classes) p.d_sem[s * p.classes + cc] = 0.0f;
                 }
+                if (NRM) { p.d_np[3 * s] = 0.0f; p.d_np[3 * s + 1] = 0.0f; p.d_np[3 * s + 2] = 0.0f; }
             }
         }
         const int n_live = stop >= 0 ? (stop / W + 1) * W : sg.n;   // passes B and C stop behind the stop sample's chunk
@@ -773,6 +793,30 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             if (y == 4) sky = expf(-aD);
             gD = -p.g_sky * sky;
         }
+        // NRM: the term of the ray and the seed of its composited normal (every lane holds the ray's sums)
+        float gNx = 0.0f, gNy = 0.0f, gNz = 0.0f, nm = 0.0f;
+        bool nm_live = false;
+        if (NRM) {
+            const float tx = p.nrm_gt[3 * r], ty = p.nrm_gt[3 * r + 1], tz = p.nrm_gt[3 * r + 2];
+            nm_live = tx != 0.0f || ty != 0.0f || tz != 0.0f;   // (0, 0, 0): a pixel without a normal
+            if (nm_live) {
+                const float nl = sqrtf(aNx * aNx + aNy * aNy + aNz * aNz), nd = fmaxf(nl, 1e-12f);
+                const float ux = aNx / nd, uy = aNy / nd, uz = aNz / nd;
+                const float td = fmaxf(sqrtf(tx * tx + ty * ty + tz * tz), 1e-12f);
+                const float vx = tx / td, vy = ty / td, vz = tz / td;
+                const float ex = ux - vx, ey = uy - vy, ez = uz - vz;
+                nm = (fabsf(ex) - 0.1f * ux * vx) + (fabsf(ey) - 0.1f * uy * vy) + (fabsf(ez) - 0.1f * uz * vz);
+                const float qx = p.g_nm * ((ex > 0.0f ? 1.0f : ex < 0.0f ? -1.0f : 0.0f) - 0.1f * vx);
+                const float qy = p.g_nm * ((ey > 0.0f ? 1.0f : ey < 0.0f ? -1.0f : 0.0f) - 0.1f * vy);
+                const float qz = p.g_nm * ((ez > 0.0f ? 1.0f : ez < 0.0f ? -1.0f : 0.0f) - 0.1f * vz);
+                if (nl > 1e-12f) {
+                    const float uq = ux * qx + uy * qy + uz * qz;
+                    gNx = (qx - ux * uq) / nl; gNy = (qy - uy * uq) / nl; gNz = (qz - uz * uq) / nl;
+                } else {
+                    gNx = qx / 1e-12f; gNy = qy / 1e-12f; gNz = qz / 1e-12f;
+                }
+            }
+        }
         if (lane == 0) {
             p.total_samples[r] = stop >= 0 ? stop : sg.n;
             p.opacity[r] = aO; p.depth[r] = aD;
@@ -789,6 +833,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 s_ms = mk * mk;
             }
             if (SEM) { s_ce = ce; s_sky = sky; }
+            if (NRM) s_nm = nm;
             n_used = (unsigned long long)(stop >= 0 ? stop : sg.n);
         }
         const float w_sum = w_run, wt_sum = wt_run;
@@ -863,6 +908,23 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                         for (int cc = 0; cc < CMAX; cc++)
                             if (cc < p.classes) p.d_sem[s * p.classes + cc] = winv * pr[cc] * (gS[cc] - dot);
                     }
+                    if (NRM) {
+                        // the head's raw output again (pass A kept none), then -normalize's backward of w g_N
+                        float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+                        if (nm_live && wa != 0.0f) {
+                            const float hx = p.np_raw[s * p.ld_np], hy = p.np_raw[s * p.ld_np + 1], hz = p.np_raw[s * p.ld_np + 2];
+                            const float hl = sqrtf(hx * hx + hy * hy + hz * hz);
+                            if (hl > 1e-6f) {
+                                const float ux = hx / hl, uy = hy / hl, uz = hz / hl;
+                                const float ug = ux * gNx + uy * gNy + uz * gNz, kk = -wa / hl;
+                                ox = kk * (gNx - ux * ug); oy = kk * (gNy - uy * ug); oz = kk * (gNz - uz * ug);
+                            } else {
+                                const float kk = -wa / 1e-6f;
+                                ox = kk * gNx; oy = kk * gNy; oz = kk * gNz;
+                            }
+                        }
+                        p.d_np[3 * s] = ox; p.d_np[3 * s + 1] = oy; p.d_np[3 * s + 2] = oz;
+                    }
                 }
                 if (c.first >= 0) break;
                 T2 = __shfl(c.T_after, W - 1, W);
@@ -877,6 +939,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
         part[0][hw] = s_rgb; part[1][hw] = s_op; part[2][hw] = s_dist; part_n[hw] = n_used;
         if (MASKED) part[3][hw] = s_ms;
         if (SEM) { part[3][hw] = s_ce; part[4][hw] = s_sky; }
+        if (NRM) part[3][hw] = s_nm;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -906,6 +969,20 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 p.terms[4] = t_ce;
                 p.terms[5] = t_sky;
                 atomicAdd(p.terms, t_ce + t_sky);
+            }
+        } else if (NRM) {
+            atomicAdd(p.terms, t0 + t1 + t2);
+            double n_sum = 0.0;
+            for (int q = 0; q < RPB; q++) n_sum += (double)part[3][q];
+            double* sum = reinterpret_cast<double*>(p.nrm_ws + NRM_WS_SUM);
+            atomicAdd(sum, n_sum);
+            __threadfence();
+            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(p.nrm_ws + NRM_WS_DONE), 1u);
+            if (done == gridDim.x - 1) {   // every workgroup's sum is in: round it once
+                __threadfence();
+                const float t_nm = (float)(atomicAdd(sum, 0.0) * (double)p.g_nm);
+                p.terms[4] = t_nm;
+                atomicAdd(p.terms, t_nm);
             }
         } else
             atomicAdd(p.terms, t0 + t1 + t2);
@@ -1153,12 +1230,13 @@ static int render_loss_fused_launch(const float* sigmas, const float* rgbs, cons
     a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
     a.mask = mask; a.g_ms = size_delta / n_rays; a.d_mask = dL_dmask;
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
+    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
     if (mask)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
 
@@ -1228,10 +1306,51 @@ int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const floa
     a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
     a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
     a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits;
+    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     if (classes <= 8)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((render_loss_fused_kernel<16, 32, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<16, 32, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+    return ngp_check_launch();
+}
+
+int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, const float* normals_gt, float lambda_nm,
+                              float T_threshold, int classes, int n_rays, float lambda_opacity, float lambda_distortion,
+                              int64_t* total_samples, int64_t* vr_samples, float* opacity, float* depth, float* rgb,
+                              float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
+                              float* dL_dsigmas, float* dL_drgbs, int* nrm_ws, float* dL_dnormal_head, void* stream)
+{
+    if (n_rays < 0 || classes < 0 || classes > 8 || ld_normal < 3 || ld_sem < classes) return NGP_EINVAL;
+    if (n_rays == 0) return NGP_OK;
+    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
+        (classes && !sem) || !loss_o || !loss_p || !terms || !normals_gt || !nrm_ws || !normal_head || !dL_dnormal_head ||
+        !dL_dsigmas || !dL_drgbs || !ws || (reinterpret_cast<uintptr_t>(nrm_ws) & 7)) return NGP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8: one fill
+    char* base = reinterpret_cast<char*>(terms);
+    if (reinterpret_cast<char*>(vr_samples) == base + 6 * sizeof(float) &&
+        reinterpret_cast<char*>(nrm_ws) == base + 8 * sizeof(float)) {
+        if (hipMemsetAsync(terms, 0, (8 + NGP_NRM_WS_INTS) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+    } else {
+        if (hipMemsetAsync(terms, 0, 5 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(nrm_ws, 0, NGP_NRM_WS_INTS * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
+    }
+    RenderLossArgs a;
+    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
+    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
+    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
+    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
+    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
+    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
+    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
+    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
+    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
+    a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head;
+    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
 

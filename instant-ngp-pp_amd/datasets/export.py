@@ -51,8 +51,10 @@ def export_blender(root, images, c2w, camera_angle_x, splits):
 
 
 def export_tnt(root, images, c2w, K, split_of, img_dir="images", labels=None, depths=None, camera_path=None,
-               flat_intrinsics=False):
+               flat_intrinsics=False, normals=None):
     """T&T / NSVF layout: split_of[i] in {0,1,2} is the file-name prefix of frame i.
+    normals (n,h,w,3) float, world space, (0,0,0) = no normal -> normal/*.npy as float32 (the loader rescales translations
+    only: no rotation applies),
     labels (n,h,w) uint8 or wider integers (256 and above are stored as 255) -> semantic/*.pgm, depths (n,h,w) float -> depth/*.npy,
     camera_path (m,3,4) -> camera_path/pose/<5 digits>.txt"""
     os.makedirs(os.path.join(root, "pose"), exist_ok=True)
@@ -68,6 +70,9 @@ def export_tnt(root, images, c2w, K, split_of, img_dir="images", labels=None, de
         if depths is not None:
             os.makedirs(os.path.join(root, "depth"), exist_ok=True)
             np.save(os.path.join(root, "depth", stem + ".npy"), depths[i])
+        if normals is not None:
+            os.makedirs(os.path.join(root, "normal"), exist_ok=True)
+            np.save(os.path.join(root, "normal", stem + ".npy"), np.asarray(normals[i], dtype=np.float32))
     if camera_path is not None:
         os.makedirs(os.path.join(root, "camera_path", "pose"), exist_ok=True)
         for j, pose in enumerate(camera_path):
@@ -164,6 +169,19 @@ def render_scene_labels(scene, idxs, n_quad=256):
     for i in idxs:
         o, d = scene.rays(torch.full((w * h,), int(i), dtype=torch.long, device=scene.device), pix)
         out.append(scene.ground_truth_labels(o, d, n_quad=n_quad).reshape(h, w).cpu().numpy())
+    return np.stack(out)
+
+
+@torch.no_grad()
+def render_scene_normals(scene, idxs, n_quad=256):
+    """per-pixel world-space normals of an analytic scene's views (synthetic.LegoProxy.ground_truth_normals: unit
+    vectors, (0, 0, 0) where the pixel has none) -> (n, h, w, 3) float32; export_tnt takes them as `normals`"""
+    w, h = scene.img_wh
+    pix = torch.arange(w * h, device=scene.device)
+    out = []
+    for i in idxs:
+        o, d = scene.rays(torch.full((w * h,), int(i), dtype=torch.long, device=scene.device), pix)
+        out.append(scene.ground_truth_normals(o, d, n_quad=n_quad).reshape(h, w, 3).cpu().numpy())
     return np.stack(out)
 
 

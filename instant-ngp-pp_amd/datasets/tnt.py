@@ -7,6 +7,7 @@ On disk:
   <root>/{images|rgb}/<p>_<name>.png    images (RGBA is blended on white)
   <root>/semantic/<p>_<name>.pgm        optional labels (use_sem)
   <root>/depth/<p>_<name>.npy           optional monocular depth (depth_mono)
+  <root>/normal/<p>_<name>.npy          optional normal maps (normal_mono): (h, w, 3) float, world space, (0,0,0) = none
   <root>/camera_path/pose/*.txt         optional render trajectory (test split)
 """
 import glob
@@ -58,6 +59,7 @@ class tntDataset(BaseDataset):
         imgs = listing(img_dir, '.png')
         semantics = listing('semantic', '.pgm') if kwargs.get('use_sem', False) else []
         depths = listing('depth', '.npy') if kwargs.get('depth_mono', False) else []
+        normal_maps = listing('normal', '.npy') if kwargs.get('normal_mono', False) else []
         pose_files = listing('pose', '.txt')
 
         from PIL import Image
@@ -115,6 +117,8 @@ class tntDataset(BaseDataset):
                                            .astype(np.int64))
         if depths:
             self.depths_2d = torch.from_numpy(np.stack([np.load(p).reshape(-1) for p in depths]).astype(np.float32))
+        if normal_maps:
+            self.normals = torch.from_numpy(np.stack([np.load(p).reshape(-1, 3) for p in normal_maps]).astype(np.float32))
         if not split.startswith('train') and path_c2w is not None:
             self.render_traj_rays = self.get_path_rays(path_c2w)
             self.render_c2w = torch.as_tensor(path_c2w, dtype=torch.float32)[:, :3]  # render.py:98

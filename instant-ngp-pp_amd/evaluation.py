@@ -11,10 +11,13 @@ a held-out split (what the reference's render.py:50-218 and validation step trai
                                                                    image size (ngp_resize_bicubic_u8, I3)
   evaluate_split(model, test_set, ...)                          -> {'psnr': [...], 'ssim': [...]} per held-out image,
                                                                    with labels also 'sem_acc', 'sem_miou', 'sem_valid'
+  normal_degrees(pred, target)                                  -> mean angle in degrees over the pixels that have a normal
+  normal_summary(res)                                           -> mean of 'normal_deg' over the images that have normals
   semantic_summary(res)                                         -> (pixel-weighted accuracy, mean IoU) of the split
   semantic_metrics(pred, label, classes)                        -> (accuracy, mean IoU) of one label image on the device
 """
 import torch
+import torch.nn.functional as F
 
 from ._lib import call, check_input
 from .colormap import turbo_lut
@@ -186,6 +189,25 @@ def semantic_summary(res):
     return sum(a * n for a, _, n in rows) / total, sum(m for _, m, _ in rows) / len(rows)
 
 
+def normal_summary(res):
+    """mean of evaluate_split's 'normal_deg' over the images that have pixels with a normal (NaN entries take no part);
+    None when no image has one"""
+    rows = [d for d in res["normal_deg"] if d == d]
+    return sum(rows) / len(rows) if rows else None
+
+
+@torch.no_grad()
+def normal_degrees(pred, target):
+    """mean angle in degrees between predicted and target normals, both (h*w, 3) and normalised here, over the pixels
+    whose target is non-zero ((0, 0, 0): the pixel has no normal) -> 0-dim tensor on pred's device; NaN when there is none"""
+    target = target.reshape(-1, 3).to(pred.device, torch.float32)
+    pred = pred.reshape(-1, 3).to(torch.float32)
+    have = (target != 0).any(-1)
+    cos = (F.normalize(pred, dim=-1) * F.normalize(target, dim=-1)).sum(-1).clamp(-1.0, 1.0)
+    ang = torch.rad2deg(torch.acos(cos))
+    return torch.where(have, ang, torch.zeros_like(ang)).sum() / have.sum()       # (0 / 0 = NaN: no such pixel)
+
+
 @torch.no_grad()
 def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs):
     """Per-image PSNR and SSIM of a held-out split through render(test_time=True) (train.py:347-392): rgb is clamped
@@ -194,8 +216,10 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
     on the device until every image is rendered: one read-back at the end.  When a test item carries 'label' the
     dictionary also holds 'sem_acc' and 'sem_miou' (semantic_metrics of results['semantic'] with render_kwargs'
     num_classes, default 7), one per image, NaN for an image without a valid label, and 'sem_valid', the number of valid
-    pixels of each image (the weights of an accuracy over the split; semantic_summary forms it)."""
-    psnrs, ssims, accs, mious, valids = [], [], [], [], []
+    pixels of each image (the weights of an accuracy over the split; semantic_summary forms it).  When the split has
+    `normals` (test items carry no 'normal', the reference's rule in datasets/base.py: test_set.normals[i] is read) the
+    dictionary also holds 'normal_deg', normal_degrees of results['normal_pred'] per image (NaN: no pixel has a normal)."""
+    psnrs, ssims, accs, mious, valids, degs = [], [], [], [], [], []
     classes = render_kwargs.get("num_classes", 7)
     for i in range(len(test_set)):
         s = test_set[i]
@@ -211,6 +235,8 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
             mious.append(m)
             lab = s["label"].reshape(-1)
             valids.append(((lab >= 0) & (lab < classes)).sum().to(a.device))
+        if hasattr(test_set, "normals"):
+            degs.append(normal_degrees(results["normal_pred"], test_set.normals[i]))
         if on_image is not None:
             on_image(i, rgb, results)
     if not psnrs:
@@ -219,4 +245,6 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
     if accs:
         out.update(sem_acc=torch.stack(accs).tolist(), sem_miou=torch.stack(mious).tolist(),
                    sem_valid=torch.stack(valids).tolist())
+    if degs:
+        out["normal_deg"] = torch.stack(degs).tolist()
     return out

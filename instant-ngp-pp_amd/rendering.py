@@ -472,10 +472,50 @@ class _RenderLossSemFn(torch.autograd.Function):
         return (d_sig, d_rgb, d_sem) + (None,) * 16
 
 
+class _RenderLossNrmFn(torch.autograd.Function):
+    """_RenderLossFn for NeRFLoss's normal_mono term (ngp_render_loss_fused_nrm): `normals_gt` (n_rays, 3) float32, one
+    target normal per ray; a row of three exact zeros marks a ray without a normal, which takes no part in the term (the
+    divisor stays 3 n_rays).  The normal head's raw output is a further differentiable input whose gradient the same
+    launch computes, and terms (5) = [loss, rgb, opacity, distortion, normal_mono].  Differentiable through terms[0]
+    only."""
+
+    @staticmethod
+    def forward(ctx, sig, rgb_o, np_raw, dsig_dx, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, normals_gt, scale3, T_thr,
+                classes, lambda_opa, lambda_dist, lambda_nm, rgb_bg=None):
+        n, nr = sig.shape[0], rays_a.shape[0]
+        dev = sig.device
+        f32 = torch.float32
+        if tuple(normals_gt.shape) != (nr, 3) or normals_gt.dtype != f32:
+            raise ValueError(f"normals must be ({nr}, 3) float32, one row per ray: got {tuple(normals_gt.shape)} "
+                             f"{normals_gt.dtype}")
+        total = torch.empty(nr, dtype=torch.int64, device=dev)
+        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
+        ws, d_sig, d_rgb, d_np = E(n), E(n), E(n, 3), E(n, 3)
+        acc = E(12)               # [terms (5) | - | vr_samples (int64) | workspace (NGP_NRM_WS_INTS)]: cleared by one memset
+        terms, vr, nrm_ws = acc[:5], acc[6:8].view(torch.int64), acc[8:12].view(torch.int32)
+        call("render_loss_fused_nrm", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
+             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, normals_gt.contiguous(), float(lambda_nm), float(T_thr), int(classes),
+             nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, terms,
+             d_sig, d_rgb, nrm_ws, d_np)
+        ctx.save_for_backward(d_sig, d_rgb, d_np)
+        ctx.pad = np_raw.shape[1] - 3
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
+        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
+
+    @staticmethod
+    def backward(ctx, g_terms, *_unused):
+        d_sig, d_rgb, d_np = ctx.saved_tensors
+        if ctx.pad:
+            d_np = F.pad(d_np, (0, ctx.pad))
+        return (d_sig, d_rgb, d_np) + (None,) * 15
+
+
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
     """fused = (rgb_gt, lambda_opa, lambda_distortion) or, for the embed_msk recipe, those three followed by
     (mask (n_rays[, 1]), size_delta), or, for the semantic recipe, by ('sem', labels (n_rays) int64, lambda_sem,
-    lambda_sky)"""
+    lambda_sky), or, for the normal_mono recipe, by ('nrm', normals_gt (n_rays, 3), lambda_nm)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
     rgb_gt, lambda_opa, lambda_dist = fused[:3]
     rgb_bg = None
@@ -486,6 +526,10 @@ def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes,
             sig, rgb_o, sem_logits, dsig_dx, np_raw, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
             rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5],
             fused[6], rgb_bg)
+    elif len(fused) == 6 and isinstance(fused[3], str) and fused[3] == 'nrm':
+        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossNrmFn.apply(
+            sig, rgb_o, np_raw, dsig_dx, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
+            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5], rgb_bg)
     elif len(fused) == 5:
         (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossMaskedFn.apply(
             sig, rgb_o, fused[3], dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,

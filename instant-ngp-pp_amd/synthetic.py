@@ -43,6 +43,28 @@ def analytic_part(x):
     return part
 
 
+# centres and half-widths of box1-3 and the shell's centre and radii, as _solids tests them
+BOX_CENTRES = ((0.0, 0.0, 0.0), (0.0, 0.0, -0.15), (0.15, -0.1, 0.0))
+BOX_HALVES = ((0.35, 0.10, 0.10), (0.10, 0.30, 0.08), (0.08, 0.08, 0.33))
+SHELL_CENTRE, SHELL_RADII = (-0.15, 0.12, 0.12), (0.15, 0.2)
+
+
+def analytic_normal(x, part):
+    """outward unit normal of solid `part` (analytic_part's numbering, -1: none -> zero vector) at the surface point
+    nearest to x (...,3), for x on or just inside the surface: a box's face nearest to x; the shell's outer sphere
+    (+radial) or inner sphere (-radial), whichever is nearer"""
+    out = torch.zeros_like(x)
+    for k, (c, h) in enumerate(zip(BOX_CENTRES, BOX_HALVES)):
+        rel = x - torch.tensor(c, device=x.device, dtype=x.dtype)
+        axis = (rel.abs() - torch.tensor(h, device=x.device, dtype=x.dtype)).argmax(-1, keepdim=True)
+        face = torch.zeros_like(x).scatter_(-1, axis, torch.sign(rel.gather(-1, axis)))
+        out = torch.where((part == k)[..., None], face, out)
+    rel = x - torch.tensor(SHELL_CENTRE, device=x.device, dtype=x.dtype)
+    r = rel.norm(dim=-1, keepdim=True)
+    radial = rel / r.clamp(min=1e-12) * torch.where(r > 0.5 * sum(SHELL_RADII), 1.0, -1.0)
+    return torch.where((part == 3)[..., None], radial, out)
+
+
 def analytic_rgb(x):
     return 0.5 + 0.5 * torch.sin(8 * math.pi * x)
 
@@ -144,6 +166,36 @@ class LegoProxy:
             best, lab = share.max(-1)
             lab = torch.where((op < 0.9) | (best < 0.6 * op), IGNORE_LABEL, lab)
             out[sl] = torch.where(op < 0.1, SKY_LABEL, lab)
+        return out
+
+    @torch.no_grad()
+    def ground_truth_normals(self, rays_o, rays_d, n_quad=1024):
+        """per-ray surface normal of the analytic scene by the quadrature of ground_truth -> float32 (N, 3), world space:
+        the outward unit normal (analytic_normal) of the solid the ray enters first, taken at the first quadrature point
+        inside it; the zero vector (no normal: the fused normal tail and evaluate_split leave such pixels out) where the
+        ray's opacity is below 0.5"""
+        inv = 1.0 / rays_d
+        a, b = (-0.5 - rays_o) * inv, (0.5 - rays_o) * inv
+        t1 = torch.minimum(a, b).amax(-1).clamp(min=0)
+        t2 = torch.maximum(a, b).amin(-1)
+        t2 = torch.where(t2 > t1, t2, t1)
+        out = torch.zeros(len(rays_o), 3, device=rays_o.device)
+        step = (t2 - t1) / n_quad
+        chunk = 16384
+        for s in range(0, len(rays_o), chunk):
+            sl = slice(s, s + chunk)
+            k = torch.arange(n_quad, device=rays_o.device, dtype=torch.float32) + 0.5
+            t = t1[sl, None] + step[sl, None] * k[None, :]
+            x = rays_o[sl, None, :] + rays_d[sl, None, :] * t[..., None]
+            part = analytic_part(x)
+            dl = step[sl, None] * rays_d[sl].norm(dim=-1, keepdim=True)
+            alpha = torch.where(part >= 0, 1 - torch.exp(-SIGMA_IN * dl), torch.zeros_like(dl))
+            T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1 - alpha], 1), 1)[:, :-1]
+            op = (alpha * T).sum(1)
+            first = (part >= 0).to(torch.int8).argmax(1)          # (the first point inside a solid; 0 if there is none)
+            rows = torch.arange(len(first), device=rays_o.device)
+            n = analytic_normal(x[rows, first], part[rows, first])
+            out[sl] = torch.where((op >= 0.5)[:, None], n, torch.zeros_like(n))
         return out
 
     @torch.no_grad()

@@ -157,8 +157,16 @@ class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
-                 semantic=False):
-        """semantic: the reference's render_semantic recipe (train.py:197, 293; NeRFLoss(semantic=True), losses.py:120-123)
+                 semantic=False, normal_mono=False):
+        """normal_mono: NeRFLoss's normal_mono term (losses.py:111-118: the predicted-normal head against per-pixel normal
+        maps, weight lambda_normal_mono) on the fused render + loss tail (ngp_render_loss_fused_nrm).  step() then needs
+        normals= (n_rays, 3) float; a row of three exact zeros marks a ray without a normal, which takes no part in the term
+        (the divisor stays 3 n_rays).  The normal head's backward adds to the colour table's gradient, outside the norm
+        bound: the step takes the exact gradient norm.  Combines with embedding_a and random_bg; not with msk_model,
+        pose_refiner, semantic=True, a skybox, a tone-mapped model, differentiable normals or an optional term in
+        loss_kwargs.  loss_kwargs={'normal_mono': True} with step(target={'normal': ...}) remains the launch-per-operation
+        route through the NeRFLoss module.
+        semantic: the reference's render_semantic recipe (train.py:197, 293; NeRFLoss(semantic=True), losses.py:120-123)
         on the fused render + loss tail (ngp_render_loss_fused_sem).  step() then needs labels= (n_rays) int64; a label
         outside [0, num_classes) is ignored (256, the reference's ignore_index, and the 255 an 8-bit label image holds in
         its place), and a batch without a valid label has a zero CE term where torch's cross-entropy gives NaN.  The
@@ -229,6 +237,17 @@ class NGPTrainer:
                                      f"{num_classes}", model.semantic_header.n_output_dims != int(num_classes))) if bad]
             if why:
                 raise ValueError("semantic=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
+        self.normal_mono = bool(normal_mono)
+        if self.normal_mono:
+            why = [w for w, bad in (("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                                    ("semantic=True", self.semantic),
+                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
+                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                                    ("an optional term in loss_kwargs", optional),
+                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
+                                    (f"num_classes = {num_classes} above 8", int(num_classes) > 8)) if bad]
+            if why:
+                raise ValueError("normal_mono=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -382,7 +401,7 @@ class NGPTrainer:
 
     def _unit_seed(self, terms):
         s = getattr(self, '_seed4', None)
-        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model, 6 semantic)
+        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model or normals, 6 semantic)
             s = self._seed4 = torch.tensor([1.0] + [0.0] * (terms.numel() - 1), device=terms.device)
         return s
 
@@ -403,8 +422,11 @@ class NGPTrainer:
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
     def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None, labels=None,
-             **loss_kwargs):
+             normals=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
+
+        normals: (n_rays, 3) float target normal of every ray (three exact zeros: none), required by a trainer built with
+        normal_mono=True (which then takes no target= and no per-step loss term).
 
         labels: (n_rays) int64 class of every ray, required by a trainer built with semantic=True (which then takes no
         target= and no per-step loss term).
@@ -439,6 +461,19 @@ class NGPTrainer:
                 raise RuntimeError("semantic=True needs CUDA tensors: the fused tail has no other route")
         elif labels is not None:
             raise ValueError("labels= is for a trainer built with semantic=True")
+        if self.normal_mono:
+            if normals is None:
+                raise ValueError("this trainer was built with normal_mono=True: step() needs normals= (the target normal of "
+                                 "every ray)")
+            if normals.dim() != 2 or tuple(normals.shape) != (rgb_gt.shape[0], 3) or not normals.is_floating_point():
+                raise ValueError(f"normals= must be ({rgb_gt.shape[0]}, 3) float: got {tuple(normals.shape)} {normals.dtype}")
+            if target or loss_kwargs:
+                raise ValueError("this trainer was built with normal_mono=True: the step stays on the fused render + loss "
+                                 "tail and takes no target= and no per-step loss term")
+            if not rays_o.is_cuda:
+                raise RuntimeError("normal_mono=True needs CUDA tensors: the fused tail has no other route")
+        elif normals is not None:
+            raise ValueError("normals= is for a trainer built with normal_mono=True")
         ref = self.pose_refiner
         if ref is not None:
             if rays_o is not None or rays_d is not None or next_rays is not None:
@@ -491,6 +526,12 @@ class NGPTrainer:
                     # (rgb_act or differentiable_normals changed after construction, ...): never a step without the labels
                     raise RuntimeError("semantic=True: the model no longer fits the fused semantic tail "
                                        "(rendering._fused_tail_ok); the labels would be left out of the loss")
+            if self.normal_mono:
+                extra['_fused_loss'] += ('nrm', normals.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_normal_mono)
+                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
+                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the normals
+                    raise RuntimeError("normal_mono=True: the model no longer fits the fused normal tail "
+                                       "(rendering._fused_tail_ok); the normals would be left out of the loss")
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
@@ -502,9 +543,9 @@ class NGPTrainer:
         self._norm_share_armed, self._norm_share_fired = True, 0   # one backward follows, then the optimizer step
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
         # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
-        # (the semantic head adds to the colour table's gradient: outside the bound, the exact norm from the start)
+        # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the start)
         self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
-                                and not self.semantic)
+                                and not self.semantic and not self.normal_mono)
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
@@ -512,6 +553,9 @@ class NGPTrainer:
             # (rgb_act / differentiable_normals changed after construction, a model without _field, ...)
             raise RuntimeError("semantic=True: render() did not take the fused semantic tail (rendering._fused_tail_ok); the "
                                "labels would be left out of the loss")
+        if self.normal_mono and ('_loss_terms' not in results or results['_loss_terms'].numel() != 5):
+            raise RuntimeError("normal_mono=True: render() did not take the fused normal tail (rendering._fused_tail_ok); the "
+                               "normals would be left out of the loss")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]

@@ -15,6 +15,8 @@ reference: train.py:82-392).  GPU only.
   python tools/train_dataset.py --make_proxy /tmp/proxy_sem --dataset_name tnt --downsample 0.125 --num_epochs 2 \
       --render_semantic --num_classes 5 --ckpt_path out/sem.ckpt   # semantic head on the labelled proxy: accuracy, mIoU
       # (--scale must enclose the cameras, here it defaults to 2: the sky term puts density at the far end of the volume on rays labelled 4)
+  python tools/train_dataset.py --make_proxy /tmp/proxy_nrm --dataset_name tnt --downsample 0.125 --num_epochs 2 \
+      --normal_mono --ckpt_path out/nrm.ckpt   # normal head on the proxy's analytic normal maps: held-out angle in degrees
 """
 import argparse
 import json
@@ -29,7 +31,7 @@ import ngp_amd  # noqa: F401
 from ngp_amd import ckpt
 from ngp_amd.appearance import FrameEmbedding
 from ngp_amd.datasets import dataset_dict, write_synthetic_dataset
-from ngp_amd.evaluation import evaluate_split, semantic_summary
+from ngp_amd.evaluation import evaluate_split, normal_summary, semantic_summary
 from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
@@ -72,13 +74,21 @@ def cameras_outside(train_set, scale):
 
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
           render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
-          num_classes=7):
+          num_classes=7, normal_mono=False, lambda_normal_mono=None):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
     with the sampler's image and pixel indices (the trainer then forms the rays itself, and nothing is marched ahead);
-    semantic: the semantic head of --render_semantic, fed with the sampler's labels (num_classes of them)"""
+    semantic: the semantic head of --render_semantic, fed with the sampler's labels (num_classes of them); normal_mono:
+    the normal head of --normal_mono, fed with the sampler's normals (lambda_normal_mono: the term's weight instead of
+    NeRFLoss's 1e-3)"""
     train_set.batch_size = batch_size
+    if normal_mono:
+        if not hasattr(train_set, "normals"):
+            raise ValueError("--normal_mono needs per-pixel normals: the dataset has none (the tnt layout reads "
+                             "normal/*.npy when loaded with normal_mono=True)")
+        dev = next(model.parameters()).device
+        train_set.normals = train_set.normals.to(dev)   # the sampler indexes them where the pixel indices are drawn
     if semantic:
         if not hasattr(train_set, "labels"):
             raise ValueError("--render_semantic needs per-pixel labels: the dataset has none (tnt / colmap layouts read "
@@ -93,8 +103,12 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         more.update(semantic=True)
     if semantic or num_classes != 7:
         more.update(num_classes=num_classes)
+    if normal_mono:
+        more.update(normal_mono=True)
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
                          exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
+    if lambda_normal_mono is not None:
+        trainer.loss_fn.lambda_normal_mono = float(lambda_normal_mono)
     n_imgs = len(train_set.poses)
 
     def next_batch():
@@ -105,7 +119,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             uvi = None
             if msk_model is not None:
                 uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(idx.device)
-            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None
+            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None, None
         o, d = train_set.batch_rays(s)
         uvi = None
         if msk_model is not None:
@@ -114,7 +128,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         if embedding_a is not None:   # one index per ray (the same_image strategy draws ONE image per batch)
             idx = torch.as_tensor(s["img_idxs"], device=o.device).to(torch.int64).reshape(-1).expand(o.shape[0]).contiguous()
         lab = s["label"].to(o.device, torch.int64).contiguous() if semantic else None
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab
+        nrm = s["normal"].to(o.device, torch.float32).contiguous() if normal_mono else None
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab, nrm
 
     import gc
     gc.collect()
@@ -129,6 +144,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             more["pix_idxs"] = cur[5]
         if cur[6] is not None:
             more["labels"] = cur[6]
+        if cur[7] is not None:
+            more["normals"] = cur[7]
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
         if log_every and (i + 1) % log_every == 0:
@@ -216,7 +233,16 @@ def parse_args(argv=None):
                          "reference's --render_semantic); the JSON line gains test_sem_acc_mean and test_sem_miou_mean.  "
                          "Choose --scale so that the volume encloses the cameras: the sky term rewards depth on rays labelled 4")
     ap.add_argument("--num_classes", type=int, default=7, help="classes of the semantic head, 1 to 16")
+    ap.add_argument("--normal_mono", action="store_true",
+                    help="load per-pixel normal maps (normal/*.npy of the tnt layout) and train the predicted-normal head on "
+                         "them (the reference's --normal_mono); the JSON line gains test_normal_deg_mean")
     args = ap.parse_args(argv)
+    if args.make_proxy and args.normal_mono and args.dataset_name != "tnt":
+        ap.error("--make_proxy with --normal_mono writes a scene with normal maps: --dataset_name tnt (the layout that "
+                 "carries normal/*.npy)")
+    if args.normal_mono and (args.embed_msk or args.optimize_ext or args.render_semantic):
+        ap.error("--normal_mono combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext or "
+                 "--render_semantic")
     if not 1 <= args.num_classes <= 16:
         ap.error("--num_classes must lie in [1, 16]")
     if args.make_proxy and args.render_semantic and args.dataset_name not in ("tnt", "colmap"):
@@ -246,6 +272,17 @@ def make_labelled_proxy(root, fmt, scene, n_quad=256):
     return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], labels=labels)
 
 
+def make_proxy_with_normals(root, scene, n_quad=256):
+    """the analytic proxy with per-pixel world-space normals in the tnt layout, every 8th view held out"""
+    from ngp_amd.datasets import export
+    n = scene.poses.shape[0]
+    images = export.render_scene_views(scene, range(n), rgba=False, n_quad=n_quad)
+    normals = export.render_scene_normals(scene, range(n), n_quad=n_quad)
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], normals=normals)
+
+
 def main():
     args = parse_args()
     dev = torch.device("cuda", 0)
@@ -258,14 +295,21 @@ def main():
         if args.render_semantic:
             root = make_labelled_proxy(args.make_proxy, args.dataset_name, scene)
             args.downsample = 1.0   # (these layouts are written at the size they are read at)
+        elif args.normal_mono:
+            root = make_proxy_with_normals(args.make_proxy, scene)
+            args.downsample = 1.0
         else:
             root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
     loader = dataset_dict[args.dataset_name]
     sem = dict(use_sem=True, num_classes=args.num_classes) if args.render_semantic else {}
+    if args.normal_mono:
+        sem["normal_mono"] = True
     train_set = loader(root, "train", args.downsample, device=dev, **sem)
     test_set = loader(root, "test", args.downsample, device=dev, **sem)
     if args.render_semantic and not hasattr(train_set, "labels"):
         raise SystemExit(f"--render_semantic: {root} holds no labels (semantic/*.pgm) for the {args.dataset_name} loader")
+    if args.normal_mono and not hasattr(train_set, "normals"):
+        raise SystemExit(f"--normal_mono: {root} holds no normal maps (normal/*.npy) for the {args.dataset_name} loader")
     if args.render_semantic:
         labels_of_split(train_set)
         if hasattr(test_set, "labels"):
@@ -288,7 +332,7 @@ def main():
     train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
           msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
-          semantic=args.render_semantic, num_classes=args.num_classes)
+          semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
@@ -310,6 +354,8 @@ def main():
         out.update(test_sem_acc_mean=acc, test_sem_acc=res["sem_acc"], test_sem_miou_mean=miou,
                    test_sem_miou=res["sem_miou"], test_sem_valid=res["sem_valid"],
                    num_classes=args.num_classes)
+    if "normal_deg" in res:   # mean over the held-out images that have pixels with a normal
+        out.update(test_normal_deg_mean=normal_summary(res), test_normal_deg=res["normal_deg"])
     if pose_refiner is not None:   # mean translation (scene units) and rotation (degrees) error against the dataset's poses
         before = pose_errors(pose_refiner.poses.cpu(), true_poses.cpu())
         after = pose_errors(pose_refiner.refined_poses().detach().cpu(), true_poses.cpu())
