@@ -325,6 +325,31 @@ int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const floa
                               int64_t* total_samples, int64_t* vr_samples, float* opacity, float* depth, float* rgb,
                               float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
                               float* dL_dsigmas, float* dL_drgbs, int* nrm_ws, float* dL_dnormal_head, void* stream);
+/* The same launch for NeRFLoss's depth_mono term (losses.py:7-30, 125-131): depth_gt (n_rays), the raw monocular depth,
+ * indexed by ray like target_rgb.  With z = depth_gt / 25 and D = depth, a ray is valid iff z > 0 (zero, negative and NaN
+ * targets add nothing to the fit, the term or any gradient); (a, b) is the least-squares scale and shift of a D + b ~ z over
+ * the batch's valid rays, D a constant of the fit, by Cramer's rule on the sums of D^2, D, 1, D z, z taken in double; a
+ * singular system (det == 0 in double: no valid ray, one valid ray) gives a = b = 0.
+ * terms (5) = [loss, rgb, opacity, distortion, depth_mono],
+ *   depth_mono = lambda_dm / n_rays sum_valid exp(-D / scene_scale) (a D + b - z)^2       (the falloff is a constant too).
+ * dL_dsigmas gains delta_s g_D (t_s T_s - (D - d_s)) with g_D = lambda_dm / n_rays [valid] exp(-D / scene_scale) 2 a
+ * (a D + b - z) and d_s the inclusive prefix of w t; dL_drgbs is that of ngp_render_loss_fused.  A fit kernel runs ahead of
+ * the tail on the same stream (no host read, no allocation: both launches can be captured).
+ * dep_ws: device int32 (NGP_DEP_WS_INTS = 18, 8-byte aligned) workspace, cleared by the entry:
+ *   [0:10] five doubles, the valid rays' sums of D^2, D, 1, D z, z; [10:12] one double, the sum of the rays' terms;
+ *   [12] a, [13] b (float32) and [14] n_valid (int32), left there by the fit; [15], [16] finished workgroups of the fit and
+ *   of the tail (one counter each); [17] unused.
+ * vr_samples may sit at terms + 6 floats and dep_ws at terms + 8 floats (one fill).  classes <= 8, scene_scale > 0.
+ * With lambda_dm = 0 every output shared with ngp_render_loss_fused is that entry's. */
+#define NGP_DEP_WS_INTS 18
+int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, const float* depth_gt, float lambda_dm,
+                              float scene_scale, float T_threshold, int classes, int n_rays, float lambda_opacity,
+                              float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
+                              float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
+                              float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* dep_ws, void* stream);
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,
                        float* normals_diff, float* normals_ori, void* stream);
 int ngp_neg_normalize(const float* x, int64_t ldx, const float* scale3 /* device (3) or NULL */, int64_t n,

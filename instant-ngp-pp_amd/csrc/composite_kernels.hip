@@ -594,6 +594,12 @@ struct RenderLossArgs {
     int* nrm_ws;
     float g_nm;
     float* d_np;
+    // DEP only (NeRFLoss's depth_mono term, losses.py:125-131): the raw monocular depth of every ray (z = depth / 25, valid
+    // iff z > 0), the workspace (DEP_WS_* below: depth_fit_kernel leaves the batch's scale and shift there ahead of this
+    // launch), g_dm = lambda_dm / R and the scene scale of the falloff exp(-D / scale)
+    const float* dep_gt;
+    int* dep_ws;
+    float g_dm, dm_scale;
 };
 
 // The semantic tail's workspace, NGP_SEM_WS_INTS = 8 int32, 8-byte aligned: [0] n_valid, [2:4] and [4:6] two doubles, the
@@ -650,19 +656,110 @@ __global__ void __launch_bounds__(1024) count_valid_labels_kernel(const int64_t*
 //        volumerendering.cu:234-241): d_sigmas and d_rgbs are the default entry's.
 // The term is summed in double through the workspace and rounded once by the last workgroup, as the SEM terms are.
 constexpr int NRM_WS_SUM = 0, NRM_WS_DONE = 2;   // NGP_NRM_WS_INTS = 4 int32, 8-byte aligned: one double, the workgroup count
-template <int CMAX, int W, bool MASKED, bool SEM, bool NRM>
+// DEP: with z_r = depth_gt_r / 25 (valid iff z_r > 0: zero, negative and NaN targets add nothing anywhere), D = depth and
+// (a, b) the least-squares scale and shift of a D + b ~ z over the batch's valid rays (depth_fit_kernel below; D is a
+// constant of the fit, a singular system gives (0, 0)),
+//   terms[4] = lambda_dm / R sum_valid exp(-D / scale) (a D + b - z)^2     (NeRFLoss._depth_mono, mean over all R rays; the
+//              falloff is a constant too),
+//   seed g_D = lambda_dm / R [valid] exp(-D / scale) 2 a (a D + b - z), which enters d_sigmas as the sky term's depth seed
+//              does: delta_s g_D (t_s T_s - (D - d_s)).  d_rgbs is the default entry's.
+// The depth_mono workspace, NGP_DEP_WS_INTS = 18 int32, 8-byte aligned, cleared by the entry's fill:
+//   [0:10]  five doubles, the valid rays' sums of D^2, D, 1, D z, z (depth_fit_kernel's workgroups add theirs)
+//   [10:12] one double, the batch's sum of exp(-D / scale) (a D + b - z)^2 (the tail's workgroups add theirs)
+//   [12] a, [13] b as float32 and [14] n_valid as int32: written by the last workgroup of depth_fit_kernel
+//   [15]    workgroups of depth_fit_kernel that have added their sums
+//   [16]    workgroups of the tail that have added theirs (a counter of its own: nothing is reset between the two launches)
+//   [17]    unused (keeps the size a multiple of 8 bytes)
+constexpr int DEP_WS_SUMS = 0, DEP_WS_TERM = 10, DEP_WS_A = 12, DEP_WS_B = 13, DEP_WS_NVALID = 14, DEP_WS_FIT_DONE = 15,
+              DEP_WS_TAIL_DONE = 16;
+
+// The fit of the depth_mono term: the composited depth of every ray by the tail's own decomposition (32 lanes per ray, the
+// same chunks, stop rule and accumulation order of w t, so D is the tail's `depth` output bit for bit), the five sums of the
+// normal equations added as doubles per workgroup, and the 2x2 system solved in double by the last workgroup to finish.
+// No per-sample output, no host read: the tail that follows on the stream reads (a, b) from the workspace.
+__global__ void __launch_bounds__(256) depth_fit_kernel(const float* __restrict__ sigmas, const float* __restrict__ deltas,
+                                                        const float* __restrict__ ts, const int64_t* __restrict__ rays_a,
+                                                        const float* __restrict__ depth_gt, int n_rays, float T_thr,
+                                                        int* __restrict__ dep_ws)
+{
+    constexpr int W = 32, RPB = 256 / W;
+    __shared__ float part_d[RPB], part_z[RPB];
+    Seg sg; int lane;
+    const bool have = seg_load_w<W>(rays_a, n_rays, sg, lane);
+    float aD = 0.0f, z = 0.0f;
+    if (have) {
+        float T_run = 1.0f;
+        for (int k0 = 0; k0 < sg.n; k0 += W) {
+            const int k = k0 + lane;
+            const int64_t s = sg.start + k;
+            const Chunk c = chunk_alpha_w<W>(sigmas, deltas, s, k < sg.n, T_run, T_thr, lane);
+            const float w = c.active ? c.a * c.T_before : 0.0f;
+            float tt = 0.0f;
+            if (c.valid) tt = ts[s];
+            {
+                // the tail rounds w t before it adds (the product also feeds its distortion scans, so it is never
+                // contracted into the sum): the same two roundings here
+#pragma clang fp contract(off)
+                if (c.active) aD += w * tt;
+            }
+            if (c.first >= 0) break;
+            T_run = __shfl(c.T_after, W - 1, W);
+        }
+        aD = grp_sum<W>(aD);
+        z = depth_gt[sg.ray] / 25.0f;
+    }
+    if ((threadIdx.x & (W - 1)) == 0) {
+        part_d[threadIdx.x / W] = aD;
+        part_z[threadIdx.x / W] = z > 0.0f ? z : 0.0f;   // (0: the ray takes no part; NaN compares false)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s_dd = 0.0, s_d = 0.0, s_n = 0.0, s_dz = 0.0, s_z = 0.0;
+        for (int q = 0; q < RPB; q++) {
+            if (part_z[q] > 0.0f) {
+                const double d = (double)part_d[q], t = (double)part_z[q];
+                s_dd += d * d; s_d += d; s_n += 1.0; s_dz += d * t; s_z += t;
+            }
+        }
+        double* sums = reinterpret_cast<double*>(dep_ws + DEP_WS_SUMS);
+        if (s_n > 0.0) {
+            atomicAdd(sums, s_dd); atomicAdd(sums + 1, s_d); atomicAdd(sums + 2, s_n);
+            atomicAdd(sums + 3, s_dz); atomicAdd(sums + 4, s_z);
+        }
+        __threadfence();
+        const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(dep_ws + DEP_WS_FIT_DONE), 1u);
+        if (done == gridDim.x - 1) {   // every workgroup's sums are in: solve by Cramer's rule
+            __threadfence();
+            const double a00 = atomicAdd(sums, 0.0), a01 = atomicAdd(sums + 1, 0.0), a11 = atomicAdd(sums + 2, 0.0);
+            const double b0 = atomicAdd(sums + 3, 0.0), b1 = atomicAdd(sums + 4, 0.0);
+            const double det = a00 * a11 - a01 * a01;
+            float fa = 0.0f, fb = 0.0f;
+            if (det != 0.0) {   // (no valid ray, one valid ray, ...: a singular system gives (0, 0))
+                fa = (float)((a11 * b0 - a01 * b1) / det);
+                fb = (float)((a00 * b1 - a01 * b0) / det);
+            }
+            dep_ws[DEP_WS_A] = __float_as_int(fa);
+            dep_ws[DEP_WS_B] = __float_as_int(fb);
+            dep_ws[DEP_WS_NVALID] = (int)a11;
+        }
+    }
+}
+
+template <int CMAX, int W, bool MASKED, bool SEM, bool NRM, bool DEP>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
     static_assert(!(MASKED && SEM), "SEM x MASKED is not built");
     static_assert(!(NRM && (MASKED || SEM)), "NRM x MASKED and NRM x SEM are not built");
+    static_assert(!(DEP && (MASKED || SEM || NRM)), "DEP x MASKED, DEP x SEM and DEP x NRM are not built");
     constexpr int RPB = 256 / W;          // rays per block
-    __shared__ float part[MASKED ? 4 : SEM ? 5 : NRM ? 4 : 3][RPB];
+    __shared__ float part[MASKED ? 4 : SEM ? 5 : (NRM || DEP) ? 4 : 3][RPB];
     __shared__ unsigned long long part_n[RPB];
     Seg sg; int lane;
     const bool have = seg_load_w<W>(p.rays_a, p.n_rays, sg, lane);
-    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f, s_ce = 0.0f, s_sky = 0.0f, s_nm = 0.0f;
+    float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f, s_ce = 0.0f, s_sky = 0.0f, s_nm = 0.0f, s_dm = 0.0f;
     unsigned long long n_used = 0;
     const int n_valid = SEM ? p.sem_ws[SEM_WS_NVALID] : 0;
+    const float fit_a = DEP ? __int_as_float(p.dep_ws[DEP_WS_A]) : 0.0f, fit_b = DEP ? __int_as_float(p.dep_ws[DEP_WS_B]) : 0.0f;
     if (have) {
         const size_t r = (size_t)sg.ray;
         const float sc0 = p.scale3 ? p.scale3[0] : 1.0f, sc1 = p.scale3 ? p.scale3[1] : 1.0f, sc2 = p.scale3 ? p.scale3[2] : 1.0f;
@@ -817,6 +914,16 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 }
             }
         }
+        // DEP: the term of the ray and the seed of its depth (every lane holds the ray's sums; gD is the SEM form's otherwise)
+        float dm = 0.0f;
+        if (DEP) {
+            const float z = p.dep_gt[r] / 25.0f;
+            if (z > 0.0f) {   // (zero, negative, NaN: the ray has no depth)
+                const float fall = expf(-aD / p.dm_scale), res = fit_a * aD + fit_b - z;
+                dm = fall * (res * res);
+                gD = p.g_dm * fall * (2.0f * fit_a * res);
+            }
+        }
         if (lane == 0) {
             p.total_samples[r] = stop >= 0 ? stop : sg.n;
             p.opacity[r] = aO; p.depth[r] = aD;
@@ -834,6 +941,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             }
             if (SEM) { s_ce = ce; s_sky = sky; }
             if (NRM) s_nm = nm;
+            if (DEP) s_dm = dm;
             n_used = (unsigned long long)(stop >= 0 ? stop : sg.n);
         }
         const float w_sum = w_run, wt_sum = wt_run;
@@ -885,7 +993,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                     const float T = c.T_after;
                     float v = dl * (gR * (cr * T - (aR - ri)) + gG * (cg * T - (aG - gi)) + gB * (cb * T - (aB - bi)) +
                                     gO * (1 - aO) + T * dws - (tot - pi));
-                    if (SEM) v += dl * gD * (tt * T - (wt_sum - wti));
+                    if (SEM || DEP) v += dl * gD * (tt * T - (wt_sum - wti));
                     p.d_sigmas[s] = c.active ? v : 0.0f;
                     if (SEM) {
                         // the sample's softmax again (pass A kept none), then the softmax backward of the seeds
@@ -940,6 +1048,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
         if (MASKED) part[3][hw] = s_ms;
         if (SEM) { part[3][hw] = s_ce; part[4][hw] = s_sky; }
         if (NRM) part[3][hw] = s_nm;
+        if (DEP) part[3][hw] = s_dm;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -983,6 +1092,20 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 const float t_nm = (float)(atomicAdd(sum, 0.0) * (double)p.g_nm);
                 p.terms[4] = t_nm;
                 atomicAdd(p.terms, t_nm);
+            }
+        } else if (DEP) {
+            atomicAdd(p.terms, t0 + t1 + t2);
+            double d_sum = 0.0;
+            for (int q = 0; q < RPB; q++) d_sum += (double)part[3][q];
+            double* sum = reinterpret_cast<double*>(p.dep_ws + DEP_WS_TERM);
+            atomicAdd(sum, d_sum);
+            __threadfence();
+            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(p.dep_ws + DEP_WS_TAIL_DONE), 1u);
+            if (done == gridDim.x - 1) {   // every workgroup's sum is in: round it once
+                __threadfence();
+                const float t_dm = (float)(atomicAdd(sum, 0.0) * (double)p.g_dm);
+                p.terms[4] = t_dm;
+                atomicAdd(p.terms, t_dm);
             }
         } else
             atomicAdd(p.terms, t0 + t1 + t2);
@@ -1231,12 +1354,13 @@ static int render_loss_fused_launch(const float* sigmas, const float* rgbs, cons
     a.mask = mask; a.g_ms = size_delta / n_rays; a.d_mask = dL_dmask;
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
+    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
     if (mask)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true, false, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
 
@@ -1307,10 +1431,11 @@ int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const floa
     a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
     a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
+    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
     if (classes <= 8)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((render_loss_fused_kernel<16, 32, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<16, 32, false, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
 
@@ -1350,7 +1475,52 @@ int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const floa
     a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head;
-    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
+    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+    return ngp_check_launch();
+}
+
+int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, const float* depth_gt, float lambda_dm,
+                              float scene_scale, float T_threshold, int classes, int n_rays, float lambda_opacity,
+                              float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
+                              float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
+                              float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* dep_ws, void* stream)
+{
+    if (n_rays < 0 || classes < 0 || classes > 8 || ld_normal < 3 || ld_sem < classes || !(scene_scale > 0.0f)) return NGP_EINVAL;
+    if (n_rays == 0) return NGP_OK;
+    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
+        (classes && !sem) || !loss_o || !loss_p || !terms || !depth_gt || !dep_ws || !dL_dsigmas || !dL_drgbs || !ws ||
+        (reinterpret_cast<uintptr_t>(dep_ws) & 7)) return NGP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8: one fill
+    char* base = reinterpret_cast<char*>(terms);
+    if (reinterpret_cast<char*>(vr_samples) == base + 6 * sizeof(float) &&
+        reinterpret_cast<char*>(dep_ws) == base + 8 * sizeof(float)) {
+        if (hipMemsetAsync(terms, 0, (8 + NGP_DEP_WS_INTS) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+    } else {
+        if (hipMemsetAsync(terms, 0, 5 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(dep_ws, 0, NGP_DEP_WS_INTS * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
+    }
+    // every seed needs the batch's scale and shift, which need every ray's depth: fitted on the same stream ahead of the tail
+    hipLaunchKernelGGL(depth_fit_kernel, seg_grid(n_rays), dim3(256), 0, st, sigmas, deltas, ts, rays_a, depth_gt, n_rays,
+                       T_threshold, dep_ws);
+    RenderLossArgs a;
+    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
+    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
+    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
+    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
+    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
+    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
+    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
+    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
+    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
+    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
+    a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale;
+    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
 

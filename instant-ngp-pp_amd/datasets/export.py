@@ -185,6 +185,19 @@ def render_scene_normals(scene, idxs, n_quad=256):
     return np.stack(out)
 
 
+@torch.no_grad()
+def render_scene_depths(scene, idxs, n_quad=256):
+    """per-pixel expected distance of an analytic scene's views (synthetic.LegoProxy.ground_truth_depths: 0 where the
+    pixel has none) -> (n, h, w) float32; export_tnt takes them, or an affine function of them, as `depths`"""
+    w, h = scene.img_wh
+    pix = torch.arange(w * h, device=scene.device)
+    out = []
+    for i in idxs:
+        o, d = scene.rays(torch.full((w * h,), int(i), dtype=torch.long, device=scene.device), pix)
+        out.append(scene.ground_truth_depths(o, d, n_quad=n_quad).reshape(h, w).cpu().numpy())
+    return np.stack(out)
+
+
 def write_synthetic_dataset(root_dir, scene, n_train=20, n_test=4, rgba=True, n_quad=256):
     """Exports views of `scene` as a NeRF-Synthetic directory.  The image size must be
     int(800*downsample) for the downsample used at load time."""

@@ -11,6 +11,9 @@ a held-out split (what the reference's render.py:50-218 and validation step trai
                                                                    image size (ngp_resize_bicubic_u8, I3)
   evaluate_split(model, test_set, ...)                          -> {'psnr': [...], 'ssim': [...]} per held-out image,
                                                                    with labels also 'sem_acc', 'sem_miou', 'sem_valid'
+  depth_absrel(depth, target)                                   -> mean |a D + b - z| / z over the pixels that have a depth,
+                                                                   (a, b) the image's own least-squares fit
+  depth_summary(res)                                            -> mean of 'depth_absrel' over the images that have depths
   normal_degrees(pred, target)                                  -> mean angle in degrees over the pixels that have a normal
   normal_summary(res)                                           -> mean of 'normal_deg' over the images that have normals
   semantic_summary(res)                                         -> (pixel-weighted accuracy, mean IoU) of the split
@@ -196,6 +199,34 @@ def normal_summary(res):
     return sum(rows) / len(rows) if rows else None
 
 
+def depth_summary(res):
+    """mean of evaluate_split's 'depth_absrel' over the images that have pixels with a depth (NaN entries take no part);
+    None when no image has one"""
+    rows = [d for d in res["depth_absrel"] if d == d]
+    return sum(rows) / len(rows) if rows else None
+
+
+@torch.no_grad()
+def depth_absrel(depth, target):
+    """absolute relative error of a rendered depth image against a monocular depth map, both (h*w): with z = target / 25
+    (NeRFLoss._depth_mono's unit) and the pixels with z > 0 valid, (a, b) is the least-squares scale and shift of
+    a depth + b ~ z over the valid pixels (Cramer's rule in float64, a singular system gives (0, 0)), and the result the mean
+    of |a depth + b - z| / z over them -> 0-dim tensor on depth's device; NaN when no pixel is valid.  No host read."""
+    D = depth.reshape(-1).to(torch.float64)
+    z = target.reshape(-1).to(D.device, torch.float64) / 25
+    valid = z > 0
+    zero = torch.zeros_like(D)
+    d, t = torch.where(valid, D, zero), torch.where(valid, z, zero)
+    n = valid.sum().to(torch.float64)
+    s_dd, s_d, s_dz, s_z = (d * d).sum(), d.sum(), (d * t).sum(), t.sum()
+    det = s_dd * n - s_d * s_d
+    safe = torch.where(det == 0, torch.ones_like(det), det)
+    a = torch.where(det == 0, torch.zeros_like(det), (n * s_dz - s_d * s_z) / safe)
+    b = torch.where(det == 0, torch.zeros_like(det), (s_dd * s_z - s_d * s_dz) / safe)
+    rel = torch.where(valid, (a * D + b - z).abs() / torch.where(valid, z, torch.ones_like(z)), zero)
+    return (rel.sum() / n).to(torch.float32)       # (0 / 0 = NaN: no such pixel)
+
+
 @torch.no_grad()
 def normal_degrees(pred, target):
     """mean angle in degrees between predicted and target normals, both (h*w, 3) and normalised here, over the pixels
@@ -218,8 +249,10 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
     num_classes, default 7), one per image, NaN for an image without a valid label, and 'sem_valid', the number of valid
     pixels of each image (the weights of an accuracy over the split; semantic_summary forms it).  When the split has
     `normals` (test items carry no 'normal', the reference's rule in datasets/base.py: test_set.normals[i] is read) the
-    dictionary also holds 'normal_deg', normal_degrees of results['normal_pred'] per image (NaN: no pixel has a normal)."""
-    psnrs, ssims, accs, mious, valids, degs = [], [], [], [], [], []
+    dictionary also holds 'normal_deg', normal_degrees of results['normal_pred'] per image (NaN: no pixel has a normal).
+    When the split has `depths_2d` (read as test_set.depths_2d[i], like the normals) it also holds 'depth_absrel',
+    depth_absrel of results['depth'] per image (NaN: no pixel has a depth)."""
+    psnrs, ssims, accs, mious, valids, degs, rels = [], [], [], [], [], [], []
     classes = render_kwargs.get("num_classes", 7)
     for i in range(len(test_set)):
         s = test_set[i]
@@ -237,6 +270,8 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
             valids.append(((lab >= 0) & (lab < classes)).sum().to(a.device))
         if hasattr(test_set, "normals"):
             degs.append(normal_degrees(results["normal_pred"], test_set.normals[i]))
+        if hasattr(test_set, "depths_2d"):
+            rels.append(depth_absrel(results["depth"], test_set.depths_2d[i]))
         if on_image is not None:
             on_image(i, rgb, results)
     if not psnrs:
@@ -247,4 +282,6 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
                    sem_valid=torch.stack(valids).tolist())
     if degs:
         out["normal_deg"] = torch.stack(degs).tolist()
+    if rels:
+        out["depth_absrel"] = torch.stack(rels).tolist()
     return out

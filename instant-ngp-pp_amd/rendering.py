@@ -512,10 +512,48 @@ class _RenderLossNrmFn(torch.autograd.Function):
         return (d_sig, d_rgb, d_np) + (None,) * 15
 
 
+class _RenderLossDepFn(torch.autograd.Function):
+    """_RenderLossFn for NeRFLoss's depth_mono term (ngp_render_loss_fused_dep): `depth_gt` (n_rays) float32, the raw
+    monocular depth of every ray (z = depth_gt / 25; zero, negative and NaN mark a ray without depth, which takes no part in
+    the fit, the term or any gradient).  A fit kernel ahead of the tail leaves the batch's least-squares scale and shift of
+    the composited depths in the workspace (a singular system: (0, 0)); the term reaches the field through d_sigmas alone, so
+    there is no further differentiable input, and terms (5) = [loss, rgb, opacity, distortion, depth_mono].  The workspace
+    (scale, shift, n_valid at int 12, 13, 14) is returned last.  Differentiable through terms[0] only."""
+
+    @staticmethod
+    def forward(ctx, sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, depth_gt, scale3, T_thr,
+                classes, lambda_opa, lambda_dist, lambda_dm, scene_scale, rgb_bg=None):
+        n, nr = sig.shape[0], rays_a.shape[0]
+        dev = sig.device
+        f32 = torch.float32
+        if tuple(depth_gt.shape) != (nr,) or depth_gt.dtype != f32:
+            raise ValueError(f"depths must be ({nr},) float32, one per ray: got {tuple(depth_gt.shape)} {depth_gt.dtype}")
+        total = torch.empty(nr, dtype=torch.int64, device=dev)
+        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
+        ws, d_sig, d_rgb = E(n), E(n), E(n, 3)
+        acc = E(26)               # [terms (5) | - | vr_samples (int64) | workspace (NGP_DEP_WS_INTS)]: cleared by one memset
+        terms, vr, dep_ws = acc[:5], acc[6:8].view(torch.int64), acc[8:26].view(torch.int32)
+        call("render_loss_fused_dep", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
+             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, depth_gt.contiguous(), float(lambda_dm), float(scene_scale), float(T_thr),
+             int(classes), nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp,
+             terms, d_sig, d_rgb, dep_ws)
+        ctx.save_for_backward(d_sig, d_rgb)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, dep_ws)
+        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, dep_ws
+
+    @staticmethod
+    def backward(ctx, g_terms, *_unused):
+        d_sig, d_rgb = ctx.saved_tensors
+        return (d_sig, d_rgb) + (None,) * 17
+
+
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
     """fused = (rgb_gt, lambda_opa, lambda_distortion) or, for the embed_msk recipe, those three followed by
     (mask (n_rays[, 1]), size_delta), or, for the semantic recipe, by ('sem', labels (n_rays) int64, lambda_sem,
-    lambda_sky), or, for the normal_mono recipe, by ('nrm', normals_gt (n_rays, 3), lambda_nm)"""
+    lambda_sky), or, for the normal_mono recipe, by ('nrm', normals_gt (n_rays, 3), lambda_nm), or, for the depth_mono
+    recipe, by ('dep', depth_gt (n_rays), lambda_dm, scene_scale)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
     rgb_gt, lambda_opa, lambda_dist = fused[:3]
     rgb_bg = None
@@ -530,6 +568,11 @@ def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes,
         (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossNrmFn.apply(
             sig, rgb_o, np_raw, dsig_dx, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
             rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5], rgb_bg)
+    elif len(fused) == 7 and isinstance(fused[3], str) and fused[3] == 'dep':
+        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, _) = _RenderLossDepFn.apply(
+            sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
+            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5],
+            fused[6], rgb_bg)
     elif len(fused) == 5:
         (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossMaskedFn.apply(
             sig, rgb_o, fused[3], dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,

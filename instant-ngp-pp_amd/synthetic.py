@@ -199,6 +199,33 @@ class LegoProxy:
         return out
 
     @torch.no_grad()
+    def ground_truth_depths(self, rays_o, rays_d, n_quad=1024):
+        """per-ray expected distance sum_s w_s t_s of the analytic scene by the quadrature of ground_truth -> float32 (N):
+        t in units of |rays_d| as the marcher's ts are; 0 (no depth: the fused depth tail and evaluate_split leave such
+        pixels out) where the ray's opacity is below 0.5"""
+        inv = 1.0 / rays_d
+        a, b = (-0.5 - rays_o) * inv, (0.5 - rays_o) * inv
+        t1 = torch.minimum(a, b).amax(-1).clamp(min=0)
+        t2 = torch.maximum(a, b).amin(-1)
+        t2 = torch.where(t2 > t1, t2, t1)
+        out = torch.zeros(len(rays_o), device=rays_o.device)
+        step = (t2 - t1) / n_quad
+        chunk = 16384
+        for s in range(0, len(rays_o), chunk):
+            sl = slice(s, s + chunk)
+            k = torch.arange(n_quad, device=rays_o.device, dtype=torch.float32) + 0.5
+            t = t1[sl, None] + step[sl, None] * k[None, :]
+            x = rays_o[sl, None, :] + rays_d[sl, None, :] * t[..., None]
+            part = analytic_part(x)
+            dl = step[sl, None] * rays_d[sl].norm(dim=-1, keepdim=True)
+            alpha = torch.where(part >= 0, 1 - torch.exp(-SIGMA_IN * dl), torch.zeros_like(dl))
+            T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1 - alpha], 1), 1)[:, :-1]
+            w = alpha * T
+            op = w.sum(1)
+            out[sl] = torch.where(op >= 0.5, (w * t).sum(1), torch.zeros_like(op))
+        return out
+
+    @torch.no_grad()
     def occupancy_from_analytic(self, model, supersample=2):
         """density_grid (K, G^3, morton order) from the analytic sigma: the steady-state occupancy
         the schedule converges to, used to put the micro-benchmark straight into that regime."""

@@ -157,8 +157,18 @@ class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
-                 semantic=False, normal_mono=False):
-        """normal_mono: NeRFLoss's normal_mono term (losses.py:111-118: the predicted-normal head against per-pixel normal
+                 semantic=False, normal_mono=False, depth_mono=False):
+        """depth_mono: NeRFLoss's depth_mono term (losses.py:7-30, 125-131: composited depth against per-pixel monocular depth
+        up to the batch's least-squares scale and shift, weight lambda_depth_mono) on the fused render + loss tail
+        (ngp_render_loss_fused_dep: a fit kernel, then the tail).  step() then needs depths= (n_rays) float, the raw depth
+        (z = depth / 25); zero, negative and NaN mark a ray without depth, which takes no part in the fit, the term or any
+        gradient (the mean stays over n_rays); the falloff's scene scale is the model's `scale`.  The term reaches the
+        parameters through d_sigmas alone, the density head's backward stays the one writer of its table's gradient, and the
+        step keeps the norm-bound clip.  Combines with embedding_a and random_bg; not with msk_model, pose_refiner,
+        semantic=True, normal_mono=True, a skybox, a tone-mapped model, differentiable normals or an optional term in
+        loss_kwargs.  loss_kwargs={'depth_mono': True} with step(target={'depth': ...}) remains the launch-per-operation route
+        through the NeRFLoss module.
+        normal_mono: NeRFLoss's normal_mono term (losses.py:111-118: the predicted-normal head against per-pixel normal
         maps, weight lambda_normal_mono) on the fused render + loss tail (ngp_render_loss_fused_nrm).  step() then needs
         normals= (n_rays, 3) float; a row of three exact zeros marks a ray without a normal, which takes no part in the term
         (the divisor stays 3 n_rays).  The normal head's backward adds to the colour table's gradient, outside the norm
@@ -248,6 +258,17 @@ class NGPTrainer:
                                     (f"num_classes = {num_classes} above 8", int(num_classes) > 8)) if bad]
             if why:
                 raise ValueError("normal_mono=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
+        self.depth_mono = bool(depth_mono)
+        if self.depth_mono:
+            why = [w for w, bad in (("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                                    ("semantic=True", self.semantic), ("normal_mono=True", self.normal_mono),
+                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
+                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                                    ("an optional term in loss_kwargs", optional),
+                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
+                                    (f"num_classes = {num_classes} above 8", int(num_classes) > 8)) if bad]
+            if why:
+                raise ValueError("depth_mono=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -401,7 +422,7 @@ class NGPTrainer:
 
     def _unit_seed(self, terms):
         s = getattr(self, '_seed4', None)
-        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model or normals, 6 semantic)
+        if s is None or s.device != terms.device or s.numel() != terms.numel():   # (4 terms, 5 with a mask model, normals or depths, 6 semantic)
             s = self._seed4 = torch.tensor([1.0] + [0.0] * (terms.numel() - 1), device=terms.device)
         return s
 
@@ -422,8 +443,11 @@ class NGPTrainer:
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
     def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None, labels=None,
-             normals=None, **loss_kwargs):
+             normals=None, depths=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
+
+        depths: (n_rays) float raw monocular depth of every ray (zero, negative, NaN: none), required by a trainer built with
+        depth_mono=True (which then takes no target= and no per-step loss term).
 
         normals: (n_rays, 3) float target normal of every ray (three exact zeros: none), required by a trainer built with
         normal_mono=True (which then takes no target= and no per-step loss term).
@@ -474,6 +498,19 @@ class NGPTrainer:
                 raise RuntimeError("normal_mono=True needs CUDA tensors: the fused tail has no other route")
         elif normals is not None:
             raise ValueError("normals= is for a trainer built with normal_mono=True")
+        if self.depth_mono:
+            if depths is None:
+                raise ValueError("this trainer was built with depth_mono=True: step() needs depths= (the monocular depth of "
+                                 "every ray)")
+            if tuple(depths.shape) != (rgb_gt.shape[0],) or not depths.is_floating_point():
+                raise ValueError(f"depths= must be ({rgb_gt.shape[0]},) float: got {tuple(depths.shape)} {depths.dtype}")
+            if target or loss_kwargs:
+                raise ValueError("this trainer was built with depth_mono=True: the step stays on the fused render + loss "
+                                 "tail and takes no target= and no per-step loss term")
+            if not rays_o.is_cuda:
+                raise RuntimeError("depth_mono=True needs CUDA tensors: the fused tail has no other route")
+        elif depths is not None:
+            raise ValueError("depths= is for a trainer built with depth_mono=True")
         ref = self.pose_refiner
         if ref is not None:
             if rays_o is not None or rays_d is not None or next_rays is not None:
@@ -532,6 +569,13 @@ class NGPTrainer:
                     # (rgb_act or differentiable_normals changed after construction, ...): never a step without the normals
                     raise RuntimeError("normal_mono=True: the model no longer fits the fused normal tail "
                                        "(rendering._fused_tail_ok); the normals would be left out of the loss")
+            if self.depth_mono:
+                extra['_fused_loss'] += ('dep', depths.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_depth_mono,
+                                         float(model.scale))
+                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
+                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the depths
+                    raise RuntimeError("depth_mono=True: the model no longer fits the fused depth tail "
+                                       "(rendering._fused_tail_ok); the depths would be left out of the loss")
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
@@ -543,7 +587,8 @@ class NGPTrainer:
         self._norm_share_armed, self._norm_share_fired = True, 0   # one backward follows, then the optimizer step
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
         # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
-        # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the start)
+        # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the
+        # start; the depth_mono term only changes d_sigmas, which the density head's backward notes: the bound holds)
         self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
                                 and not self.semantic and not self.normal_mono)
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
@@ -556,9 +601,14 @@ class NGPTrainer:
         if self.normal_mono and ('_loss_terms' not in results or results['_loss_terms'].numel() != 5):
             raise RuntimeError("normal_mono=True: render() did not take the fused normal tail (rendering._fused_tail_ok); the "
                                "normals would be left out of the loss")
+        if self.depth_mono and ('_loss_terms' not in results or results['_loss_terms'].numel() != 5):
+            raise RuntimeError("depth_mono=True: render() did not take the fused depth tail (rendering._fused_tail_ok); the "
+                               "depths would be left out of the loss")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]
+            if self.depth_mono:
+                results['loss_terms'] = terms.detach()   # [loss, rgb, opacity, distortion, depth_mono]: for a caller's log
             torch.autograd.backward([terms], [self._unit_seed(terms)])
         elif default_recipe and not masked:
             # same value and gradients as sum(term.mean()) over NeRFLoss's default terms; the

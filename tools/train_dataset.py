@@ -17,6 +17,8 @@ reference: train.py:82-392).  GPU only.
       # (--scale must enclose the cameras, here it defaults to 2: the sky term puts density at the far end of the volume on rays labelled 4)
   python tools/train_dataset.py --make_proxy /tmp/proxy_nrm --dataset_name tnt --downsample 0.125 --num_epochs 2 \
       --normal_mono --ckpt_path out/nrm.ckpt   # normal head on the proxy's analytic normal maps: held-out angle in degrees
+  python tools/train_dataset.py --make_proxy /tmp/proxy_dep --dataset_name tnt --downsample 0.125 --num_epochs 2 \
+      --depth_mono --ckpt_path out/dep.ckpt   # depth_mono term on the proxy's depth maps (right up to scale and shift): held-out abs-rel
 """
 import argparse
 import json
@@ -26,12 +28,13 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import numpy as np
 import torch
 import ngp_amd  # noqa: F401
 from ngp_amd import ckpt
 from ngp_amd.appearance import FrameEmbedding
 from ngp_amd.datasets import dataset_dict, write_synthetic_dataset
-from ngp_amd.evaluation import evaluate_split, normal_summary, semantic_summary
+from ngp_amd.evaluation import depth_summary, evaluate_split, normal_summary, semantic_summary
 from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
@@ -74,15 +77,23 @@ def cameras_outside(train_set, scale):
 
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
           render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
-          num_classes=7, normal_mono=False, lambda_normal_mono=None):
+          num_classes=7, normal_mono=False, lambda_normal_mono=None, depth_mono=False, lambda_depth_mono=None):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
     with the sampler's image and pixel indices (the trainer then forms the rays itself, and nothing is marched ahead);
     semantic: the semantic head of --render_semantic, fed with the sampler's labels (num_classes of them); normal_mono:
     the normal head of --normal_mono, fed with the sampler's normals (lambda_normal_mono: the term's weight instead of
-    NeRFLoss's 1e-3)"""
+    NeRFLoss's 1e-3); depth_mono: the depth_mono term of --depth_mono, fed with the sampler's depths (lambda_depth_mono: the
+    term's weight instead of NeRFLoss's 1); the trainer then carries `terms_log`, the loss terms of every step as device
+    tensors (read after the run: nothing is read while it trains)"""
     train_set.batch_size = batch_size
+    if depth_mono:
+        if not hasattr(train_set, "depths_2d"):
+            raise ValueError("--depth_mono needs per-pixel depths: the dataset has none (the tnt layout reads depth/*.npy "
+                             "when loaded with depth_mono=True)")
+        dev = next(model.parameters()).device
+        train_set.depths_2d = train_set.depths_2d.to(dev)   # the sampler indexes them where the pixel indices are drawn
     if normal_mono:
         if not hasattr(train_set, "normals"):
             raise ValueError("--normal_mono needs per-pixel normals: the dataset has none (the tnt layout reads "
@@ -105,10 +116,15 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         more.update(num_classes=num_classes)
     if normal_mono:
         more.update(normal_mono=True)
+    if depth_mono:
+        more.update(depth_mono=True)
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
                          exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
     if lambda_normal_mono is not None:
         trainer.loss_fn.lambda_normal_mono = float(lambda_normal_mono)
+    if lambda_depth_mono is not None:
+        trainer.loss_fn.lambda_depth_mono = float(lambda_depth_mono)
+    trainer.terms_log = []
     n_imgs = len(train_set.poses)
 
     def next_batch():
@@ -119,7 +135,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             uvi = None
             if msk_model is not None:
                 uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(idx.device)
-            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None, None
+            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None, None, None
         o, d = train_set.batch_rays(s)
         uvi = None
         if msk_model is not None:
@@ -129,7 +145,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             idx = torch.as_tensor(s["img_idxs"], device=o.device).to(torch.int64).reshape(-1).expand(o.shape[0]).contiguous()
         lab = s["label"].to(o.device, torch.int64).contiguous() if semantic else None
         nrm = s["normal"].to(o.device, torch.float32).contiguous() if normal_mono else None
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab, nrm
+        dep = s["depth"].to(o.device, torch.float32).reshape(-1).contiguous() if depth_mono else None
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab, nrm, dep
 
     import gc
     gc.collect()
@@ -146,8 +163,12 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             more["labels"] = cur[6]
         if cur[7] is not None:
             more["normals"] = cur[7]
+        if cur[8] is not None:
+            more["depths"] = cur[8]
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
+        if depth_mono:
+            trainer.terms_log.append(res["loss_terms"])
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
             print(json.dumps({"step": i + 1, "loss": float(loss), "train_psnr": float(psnr(res["rgb"].detach(), cur[2])),
@@ -236,7 +257,18 @@ def parse_args(argv=None):
     ap.add_argument("--normal_mono", action="store_true",
                     help="load per-pixel normal maps (normal/*.npy of the tnt layout) and train the predicted-normal head on "
                          "them (the reference's --normal_mono); the JSON line gains test_normal_deg_mean")
+    ap.add_argument("--depth_mono", action="store_true",
+                    help="load per-pixel monocular depth maps (depth/*.npy of the tnt layout) and train with NeRFLoss's "
+                         "depth_mono term (the reference's --depth_mono); the JSON line gains test_depth_absrel_mean")
+    ap.add_argument("--lambda_depth_mono", type=float, default=None, help="weight of the depth_mono term (NeRFLoss: 1)")
+    ap.add_argument("--proxy_views", type=int, default=108, help="views of the scene --make_proxy writes")
     args = ap.parse_args(argv)
+    if args.make_proxy and args.depth_mono and args.dataset_name != "tnt":
+        ap.error("--make_proxy with --depth_mono writes a scene with depth maps: --dataset_name tnt (the layout that "
+                 "carries depth/*.npy)")
+    if args.depth_mono and (args.embed_msk or args.optimize_ext or args.render_semantic or args.normal_mono):
+        ap.error("--depth_mono combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext, "
+                 "--render_semantic or --normal_mono")
     if args.make_proxy and args.normal_mono and args.dataset_name != "tnt":
         ap.error("--make_proxy with --normal_mono writes a scene with normal maps: --dataset_name tnt (the layout that "
                  "carries normal/*.npy)")
@@ -283,6 +315,30 @@ def make_proxy_with_normals(root, scene, n_quad=256):
     return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], normals=normals)
 
 
+PROXY_DEPTH_SCALE, PROXY_DEPTH_SHIFT = 0.37, 0.11
+
+
+def make_proxy_with_depths(root, scene, n_quad=256):
+    """the analytic proxy with per-pixel monocular depth maps in the tnt layout, every 8th view held out: the files hold
+    25 (0.37 D + 0.11) with D the scene's expected distance, so they are right up to a scale and a shift, which the term's
+    fit has to absorb; a pixel without depth stays 0"""
+    from ngp_amd.datasets import export
+    n = scene.poses.shape[0]
+    images = export.render_scene_views(scene, range(n), rgba=False, n_quad=n_quad)
+    D = export.render_scene_depths(scene, range(n), n_quad=n_quad)
+    depths = np.where(D > 0, 25.0 * (PROXY_DEPTH_SCALE * D + PROXY_DEPTH_SHIFT), 0.0).astype(np.float32)
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], depths=depths)
+
+
+def terms_summary(terms_log, k=10):
+    """(number of loss terms, mean of the last term over the first k steps, over the last k steps) of train()'s terms_log"""
+    t = torch.stack([v.detach() for v in terms_log]).cpu()
+    k = max(1, min(k, len(t) // 2))
+    return t.shape[1], float(t[:k, -1].mean()), float(t[-k:, -1].mean())
+
+
 def main():
     args = parse_args()
     dev = torch.device("cuda", 0)
@@ -291,12 +347,15 @@ def main():
     if args.make_proxy:
         from ngp_amd.synthetic import LegoProxy
         wh = int(800 * args.downsample)
-        scene = LegoProxy(n_images=108, img_wh=(wh, wh), device=dev)
+        scene = LegoProxy(n_images=args.proxy_views, img_wh=(wh, wh), device=dev)
         if args.render_semantic:
             root = make_labelled_proxy(args.make_proxy, args.dataset_name, scene)
             args.downsample = 1.0   # (these layouts are written at the size they are read at)
         elif args.normal_mono:
             root = make_proxy_with_normals(args.make_proxy, scene)
+            args.downsample = 1.0
+        elif args.depth_mono:
+            root = make_proxy_with_depths(args.make_proxy, scene)
             args.downsample = 1.0
         else:
             root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
@@ -304,12 +363,16 @@ def main():
     sem = dict(use_sem=True, num_classes=args.num_classes) if args.render_semantic else {}
     if args.normal_mono:
         sem["normal_mono"] = True
+    if args.depth_mono:
+        sem["depth_mono"] = True
     train_set = loader(root, "train", args.downsample, device=dev, **sem)
     test_set = loader(root, "test", args.downsample, device=dev, **sem)
     if args.render_semantic and not hasattr(train_set, "labels"):
         raise SystemExit(f"--render_semantic: {root} holds no labels (semantic/*.pgm) for the {args.dataset_name} loader")
     if args.normal_mono and not hasattr(train_set, "normals"):
         raise SystemExit(f"--normal_mono: {root} holds no normal maps (normal/*.npy) for the {args.dataset_name} loader")
+    if args.depth_mono and not hasattr(train_set, "depths_2d"):
+        raise SystemExit(f"--depth_mono: {root} holds no depth maps (depth/*.npy) for the {args.dataset_name} loader")
     if args.render_semantic:
         labels_of_split(train_set)
         if hasattr(test_set, "labels"):
@@ -329,10 +392,11 @@ def main():
         start = perturb_poses(true_poses, *args.perturb_poses, seed=20220806) if args.perturb_poses else true_poses
         pose_refiner = PoseRefiner(start, train_set.directions).to(dev)
     t0 = time.perf_counter()
-    train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
+    trainer = train(model, train_set, args.num_epochs, args.steps_per_epoch, args.batch_size, args.lr, log_every=500,
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
           msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
-          semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono)
+          semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono,
+                    depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
@@ -356,6 +420,12 @@ def main():
                    num_classes=args.num_classes)
     if "normal_deg" in res:   # mean over the held-out images that have pixels with a normal
         out.update(test_normal_deg_mean=normal_summary(res), test_normal_deg=res["normal_deg"])
+    if "depth_absrel" in res:   # mean over the held-out images that have pixels with a depth
+        out.update(test_depth_absrel_mean=depth_summary(res), test_depth_absrel=res["depth_absrel"])
+    if args.depth_mono:
+        n_terms, first, last = terms_summary(trainer.terms_log)
+        out.update(loss_terms=n_terms, depth_mono_term_first=first, depth_mono_term_last=last,
+                   lambda_depth_mono=trainer.loss_fn.lambda_depth_mono)
     if pose_refiner is not None:   # mean translation (scene units) and rotation (degrees) error against the dataset's poses
         before = pose_errors(pose_refiner.poses.cpu(), true_poses.cpu())
         after = pose_errors(pose_refiner.refined_poses().detach().cpu(), true_poses.cpu())
