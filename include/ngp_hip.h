@@ -350,6 +350,43 @@ int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const floa
                               float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
                               float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                               float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* dep_ws, void* stream);
+/* The same launch with two or three of those optional terms at once (the reference's street-scene recipes set
+ * render_semantic and normal_mono together and add depth_mono on top).  term_mask names them: NGP_TERM_SEM (labels,
+ * lambda_sem, lambda_sky, dL_dsem_logits), NGP_TERM_NRM (normals_gt, lambda_nm, dL_dnormal_head), NGP_TERM_DEP (depth_gt,
+ * lambda_dm, scene_scale); the arguments of a term that is not named are not looked at.  Each term's definition, validity
+ * rule and deviation from torch is that of its single entry above and nothing else: ngp_render_loss_fused_sem (valid labels,
+ * n_valid == 0, the literal sky class 4), ngp_render_loss_fused_nrm (a zero target row), ngp_render_loss_fused_dep (z > 0,
+ * the fit, a singular system).
+ * terms (8) = [loss, rgb, opacity, distortion, CELoss, sky_depth, normal_mono, depth_mono]; a term that is not named is
+ * exactly 0.  dL_dsigmas carries the sky term's and the depth_mono term's depth seeds added into one.
+ * multi_ws: device int32 (NGP_MULTI_WS_INTS = 30, 8-byte aligned) workspace, the three single workspaces back to back:
+ *   [0:8] sem_ws ([NGP_MULTI_WS_LABELS_NVALID] = n_valid of the labels), [8:12] nrm_ws, [12:30] dep_ws
+ *   ([NGP_MULTI_WS_FIT_A], [NGP_MULTI_WS_FIT_B] a, b as float32 and [NGP_MULTI_WS_FIT_NVALID] n_valid of the fit).
+ * With one term named this launches that term's own kernel; with more, every term is still summed in double and rounded
+ * once, behind one count of finished workgroups ([6] with NGP_TERM_SEM, else [10]).  The entry clears terms, vr_samples and
+ * the workspace (vr_samples may sit at terms + 8 floats and multi_ws at terms + 10 floats: one fill), then launches the
+ * label count (NGP_TERM_SEM), the depth fit (NGP_TERM_DEP) and the tail on the caller's stream: no host read, no allocation,
+ * capturable.  1 <= classes <= 16 with NGP_TERM_SEM, classes <= 8 without; scene_scale > 0 with NGP_TERM_DEP.  Unknown bits
+ * in term_mask are NGP_EINVAL, and so is a zero mask with rays to process (an empty batch is NGP_OK with it).  With every
+ * optional lambda 0 every output shared with ngp_render_loss_fused is that entry's. */
+#define NGP_TERM_SEM 1
+#define NGP_TERM_NRM 2
+#define NGP_TERM_DEP 4
+#define NGP_MULTI_WS_INTS 30
+#define NGP_MULTI_WS_LABELS_NVALID 0
+#define NGP_MULTI_WS_FIT_A 24
+#define NGP_MULTI_WS_FIT_B 25
+#define NGP_MULTI_WS_FIT_NVALID 26
+int ngp_render_loss_fused_multi(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                                const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                                const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                                const float* target_rgb, const float* rgb_bg, int term_mask, const int64_t* labels,
+                                float lambda_sem, float lambda_sky, const float* normals_gt, float lambda_nm,
+                                const float* depth_gt, float lambda_dm, float scene_scale, float T_threshold, int classes,
+                                int n_rays, float lambda_opacity, float lambda_distortion, int64_t* total_samples,
+                                int64_t* vr_samples, float* opacity, float* depth, float* rgb, float* normal_pred,
+                                float* sem, float* ws, float* loss_o, float* loss_p, float* terms, float* dL_dsigmas,
+                                float* dL_drgbs, int* multi_ws, float* dL_dsem_logits, float* dL_dnormal_head, void* stream);
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,
                        float* normals_diff, float* normals_ori, void* stream);
 int ngp_neg_normalize(const float* x, int64_t ldx, const float* scale3 /* device (3) or NULL */, int64_t n,

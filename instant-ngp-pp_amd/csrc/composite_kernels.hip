@@ -600,6 +600,9 @@ struct RenderLossArgs {
     const float* dep_gt;
     int* dep_ws;
     float g_dm, dm_scale;
+    // where the last workgroup puts the rounded normal_mono and depth_mono terms: terms[4] for the single entries,
+    // terms[6] and terms[7] for ngp_render_loss_fused_multi (CELoss and sky_depth are terms[4], terms[5] in both)
+    int slot_nm, slot_dm;
 };
 
 // The semantic tail's workspace, NGP_SEM_WS_INTS = 8 int32, 8-byte aligned: [0] n_valid, [2:4] and [4:6] two doubles, the
@@ -748,11 +751,12 @@ __global__ void __launch_bounds__(256) depth_fit_kernel(const float* __restrict_
 template <int CMAX, int W, bool MASKED, bool SEM, bool NRM, bool DEP>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
-    static_assert(!(MASKED && SEM), "SEM x MASKED is not built");
-    static_assert(!(NRM && (MASKED || SEM)), "NRM x MASKED and NRM x SEM are not built");
-    static_assert(!(DEP && (MASKED || SEM || NRM)), "DEP x MASKED, DEP x SEM and DEP x NRM are not built");
+    static_assert(!(MASKED && (SEM || NRM || DEP)), "MASKED x SEM, MASKED x NRM and MASKED x DEP are not built");
     constexpr int RPB = 256 / W;          // rays per block
-    __shared__ float part[MASKED ? 4 : SEM ? 5 : (NRM || DEP) ? 4 : 3][RPB];
+    // one row of partials per active term behind the three of the default recipe: [ms] or [ce, sky][nm][dm]
+    constexpr int ROW_SEM = 3, ROW_NRM = 3 + (SEM ? 2 : 0), ROW_DEP = ROW_NRM + (NRM ? 1 : 0);
+    constexpr bool MULTI = (SEM ? 1 : 0) + (NRM ? 1 : 0) + (DEP ? 1 : 0) > 1;
+    __shared__ float part[MASKED ? 4 : ROW_DEP + (DEP ? 1 : 0)][RPB];
     __shared__ unsigned long long part_n[RPB];
     Seg sg; int lane;
     const bool have = seg_load_w<W>(p.rays_a, p.n_rays, sg, lane);
@@ -784,7 +788,12 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             }
             if (c.active) {   // samples behind the stop carry no weight: their normals / classes are not needed
                 aO += w;
-                aD += w * tt;
+                {
+                    // a rounded product, then the add, in every form: depth_fit_kernel composites the same depth and its
+                    // (a, b) are only the tail's own if the two agree bit for bit
+#pragma clang fp contract(off)
+                    aD += w * tt;
+                }
                 aR += w * p.rgbs[3 * s]; aG += w * p.rgbs[3 * s + 1]; aB += w * p.rgbs[3 * s + 2];
                 // normals_raw = -normalize(d sigma/dx * scale3), normals_pred = -normalize(head), eps 1e-6 (F.normalize)
                 float gx = p.dsig_dx[3 * s] * sc0, gy = p.dsig_dx[3 * s + 1] * sc1, gz = p.dsig_dx[3 * s + 2] * sc2;
@@ -914,14 +923,16 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 }
             }
         }
-        // DEP: the term of the ray and the seed of its depth (every lane holds the ray's sums; gD is the SEM form's otherwise)
+        // DEP: the term of the ray and the seed of its depth (every lane holds the ray's sums).  With SEM the sky term's
+        // seed is already in gD and the two add: pass C's one depth line then serves both terms.
         float dm = 0.0f;
         if (DEP) {
             const float z = p.dep_gt[r] / 25.0f;
             if (z > 0.0f) {   // (zero, negative, NaN: the ray has no depth)
                 const float fall = expf(-aD / p.dm_scale), res = fit_a * aD + fit_b - z;
                 dm = fall * (res * res);
-                gD = p.g_dm * fall * (2.0f * fit_a * res);
+                const float gdm = p.g_dm * fall * (2.0f * fit_a * res);
+                gD = SEM ? gD + gdm : gdm;
             }
         }
         if (lane == 0) {
@@ -1046,9 +1057,9 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
     if ((threadIdx.x & (W - 1)) == 0) {
         part[0][hw] = s_rgb; part[1][hw] = s_op; part[2][hw] = s_dist; part_n[hw] = n_used;
         if (MASKED) part[3][hw] = s_ms;
-        if (SEM) { part[3][hw] = s_ce; part[4][hw] = s_sky; }
-        if (NRM) part[3][hw] = s_nm;
-        if (DEP) part[3][hw] = s_dm;
+        if (SEM) { part[ROW_SEM][hw] = s_ce; part[ROW_SEM + 1][hw] = s_sky; }
+        if (NRM) part[ROW_NRM][hw] = s_nm;
+        if (DEP) part[ROW_DEP][hw] = s_dm;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1061,6 +1072,56 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             t3 *= p.g_ms;
             atomicAdd(p.terms, (t0 + t1 + t2) + t3);
             atomicAdd(p.terms + 4, t3);
+        } else if (MULTI) {
+            // two or three optional terms: each is summed in double into its own term's workspace slot, exactly as in
+            // the single forms below, behind ONE count of finished workgroups (the SEM block's when SEM is built, else
+            // the NRM block's); the last workgroup rounds every term once and adds their float sum to terms[0]
+            atomicAdd(p.terms, t0 + t1 + t2);
+            double* sem_sums = SEM ? reinterpret_cast<double*>(p.sem_ws + SEM_WS_SUMS) : nullptr;
+            double* nrm_sum = NRM ? reinterpret_cast<double*>(p.nrm_ws + NRM_WS_SUM) : nullptr;
+            double* dep_sum = DEP ? reinterpret_cast<double*>(p.dep_ws + DEP_WS_TERM) : nullptr;
+            if (SEM) {
+                double c_sum = 0.0, s_sum = 0.0;
+                for (int q = 0; q < RPB; q++) { c_sum += (double)part[ROW_SEM][q]; s_sum += (double)part[ROW_SEM + 1][q]; }
+                atomicAdd(sem_sums, c_sum);
+                atomicAdd(sem_sums + 1, s_sum);
+            }
+            if (NRM) {
+                double n_sum = 0.0;
+                for (int q = 0; q < RPB; q++) n_sum += (double)part[ROW_NRM][q];
+                atomicAdd(nrm_sum, n_sum);
+            }
+            if (DEP) {
+                double d_sum = 0.0;
+                for (int q = 0; q < RPB; q++) d_sum += (double)part[ROW_DEP][q];
+                atomicAdd(dep_sum, d_sum);
+            }
+            __threadfence();
+            unsigned* cnt = reinterpret_cast<unsigned*>(SEM ? p.sem_ws + SEM_WS_DONE : p.nrm_ws + NRM_WS_DONE);
+            const unsigned done = atomicAdd(cnt, 1u);
+            if (done == gridDim.x - 1) {   // every workgroup's sums are in: round them once
+                __threadfence();
+                float opt = 0.0f;
+                if (SEM) {
+                    const double ce_all = atomicAdd(sem_sums, 0.0), sky_all = atomicAdd(sem_sums + 1, 0.0);
+                    const float t_ce = n_valid > 0 ? (float)(ce_all * ((double)p.lam_sem / (double)n_valid)) : 0.0f;
+                    const float t_sky = (float)(sky_all * (double)p.g_sky);
+                    p.terms[4] = t_ce;
+                    p.terms[5] = t_sky;
+                    opt = t_ce + t_sky;
+                }
+                if (NRM) {
+                    const float t_nm = (float)(atomicAdd(nrm_sum, 0.0) * (double)p.g_nm);
+                    p.terms[p.slot_nm] = t_nm;
+                    opt += t_nm;
+                }
+                if (DEP) {
+                    const float t_dm = (float)(atomicAdd(dep_sum, 0.0) * (double)p.g_dm);
+                    p.terms[p.slot_dm] = t_dm;
+                    opt += t_dm;
+                }
+                atomicAdd(p.terms, opt);
+            }
         } else if (SEM) {
             atomicAdd(p.terms, t0 + t1 + t2);
             double c_sum = 0.0, s_sum = 0.0;
@@ -1090,7 +1151,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             if (done == gridDim.x - 1) {   // every workgroup's sum is in: round it once
                 __threadfence();
                 const float t_nm = (float)(atomicAdd(sum, 0.0) * (double)p.g_nm);
-                p.terms[4] = t_nm;
+                p.terms[p.slot_nm] = t_nm;
                 atomicAdd(p.terms, t_nm);
             }
         } else if (DEP) {
@@ -1104,7 +1165,7 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             if (done == gridDim.x - 1) {   // every workgroup's sum is in: round it once
                 __threadfence();
                 const float t_dm = (float)(atomicAdd(sum, 0.0) * (double)p.g_dm);
-                p.terms[4] = t_dm;
+                p.terms[p.slot_dm] = t_dm;
                 atomicAdd(p.terms, t_dm);
             }
         } else
@@ -1355,6 +1416,7 @@ static int render_loss_fused_launch(const float* sigmas, const float* rgbs, cons
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
+    a.slot_nm = a.slot_dm = 4;
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
     if (mask)
@@ -1432,6 +1494,7 @@ int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const floa
     a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
+    a.slot_nm = a.slot_dm = 4;
     if (classes <= 8)
         hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     else
@@ -1476,6 +1539,7 @@ int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const floa
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head;
     a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
+    a.slot_nm = a.slot_dm = 4;
     hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
     return ngp_check_launch();
 }
@@ -1520,7 +1584,86 @@ int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const floa
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale;
+    a.slot_nm = a.slot_dm = 4;
     hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
+    return ngp_check_launch();
+}
+
+// The multi workspace, NGP_MULTI_WS_INTS = 30 int32, 8-byte aligned: the three single workspaces back to back
+constexpr int MULTI_WS_SEM = 0, MULTI_WS_NRM = NGP_SEM_WS_INTS, MULTI_WS_DEP = NGP_SEM_WS_INTS + NGP_NRM_WS_INTS;
+static_assert(MULTI_WS_DEP + NGP_DEP_WS_INTS == NGP_MULTI_WS_INTS && NGP_MULTI_WS_INTS % 2 == 0 && MULTI_WS_NRM % 2 == 0 &&
+              MULTI_WS_DEP % 2 == 0, "the multi workspace is the three single ones, each 8-byte aligned");
+
+int ngp_render_loss_fused_multi(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                                const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                                const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                                const float* target_rgb, const float* rgb_bg, int term_mask, const int64_t* labels,
+                                float lambda_sem, float lambda_sky, const float* normals_gt, float lambda_nm,
+                                const float* depth_gt, float lambda_dm, float scene_scale, float T_threshold, int classes,
+                                int n_rays, float lambda_opacity, float lambda_distortion, int64_t* total_samples,
+                                int64_t* vr_samples, float* opacity, float* depth, float* rgb, float* normal_pred,
+                                float* sem, float* ws, float* loss_o, float* loss_p, float* terms, float* dL_dsigmas,
+                                float* dL_drgbs, int* multi_ws, float* dL_dsem_logits, float* dL_dnormal_head, void* stream)
+{
+    // (a zero mask names nothing to compute: refused with rays to process; an empty batch is valid whatever it names)
+    if (term_mask < 0 || (term_mask & ~(NGP_TERM_SEM | NGP_TERM_NRM | NGP_TERM_DEP)) || (term_mask == 0 && n_rays != 0))
+        return NGP_EINVAL;
+    const bool SEM = term_mask & NGP_TERM_SEM, NRM = term_mask & NGP_TERM_NRM, DEP = term_mask & NGP_TERM_DEP;
+    if (n_rays < 0 || classes < (SEM ? 1 : 0) || classes > (SEM ? 16 : 8) || ld_normal < 3 || ld_sem < classes ||
+        (DEP && !(scene_scale > 0.0f))) return NGP_EINVAL;
+    if (n_rays == 0) return NGP_OK;
+    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
+        (classes && !sem) || !loss_o || !loss_p || !terms || !dL_dsigmas || !dL_drgbs || !ws || !multi_ws ||
+        (reinterpret_cast<uintptr_t>(multi_ws) & 7)) return NGP_EINVAL;
+    if (SEM && (!labels || !sem_logits || !dL_dsem_logits)) return NGP_EINVAL;
+    if (NRM && (!normals_gt || !normal_head || !dL_dnormal_head)) return NGP_EINVAL;
+    if (DEP && !depth_gt) return NGP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    // terms (8) with vr_samples behind them at float 8 and the workspace at float 10: one fill
+    char* base = reinterpret_cast<char*>(terms);
+    if (reinterpret_cast<char*>(vr_samples) == base + 8 * sizeof(float) &&
+        reinterpret_cast<char*>(multi_ws) == base + 10 * sizeof(float)) {
+        if (hipMemsetAsync(terms, 0, (10 + NGP_MULTI_WS_INTS) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+    } else {
+        if (hipMemsetAsync(terms, 0, 8 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+        if (hipMemsetAsync(multi_ws, 0, NGP_MULTI_WS_INTS * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
+    }
+    int *sem_ws = multi_ws + MULTI_WS_SEM, *nrm_ws = multi_ws + MULTI_WS_NRM, *dep_ws = multi_ws + MULTI_WS_DEP;
+    // what every seed needs of the whole batch, on the same stream ahead of the tail: the count of valid labels, the fit
+    if (SEM) hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, rays_a, n_rays, classes, sem_ws);
+    if (DEP)
+        hipLaunchKernelGGL(depth_fit_kernel, seg_grid(n_rays), dim3(256), 0, st, sigmas, deltas, ts, rays_a, depth_gt, n_rays,
+                           T_threshold, dep_ws);
+    RenderLossArgs a;
+    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
+    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
+    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
+    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
+    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
+    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
+    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
+    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
+    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
+    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
+    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
+    a.slot_nm = 6; a.slot_dm = 7;
+    if (SEM) { a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits; }
+    if (NRM) { a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head; }
+    if (DEP) { a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale; }
+    const dim3 grid = seg_grid(n_rays), block(256);
+#define NGP_TAIL(CM, S, N, D) hipLaunchKernelGGL((render_loss_fused_kernel<CM, 32, false, S, N, D>), grid, block, 0, st, a)
+    const bool wide = classes > 8;   // (only with SEM: checked above)
+    switch (term_mask) {
+    case NGP_TERM_SEM: if (wide) NGP_TAIL(16, true, false, false); else NGP_TAIL(8, true, false, false); break;
+    case NGP_TERM_NRM: NGP_TAIL(8, false, true, false); break;
+    case NGP_TERM_DEP: NGP_TAIL(8, false, false, true); break;
+    case NGP_TERM_SEM | NGP_TERM_NRM: if (wide) NGP_TAIL(16, true, true, false); else NGP_TAIL(8, true, true, false); break;
+    case NGP_TERM_SEM | NGP_TERM_DEP: if (wide) NGP_TAIL(16, true, false, true); else NGP_TAIL(8, true, false, true); break;
+    case NGP_TERM_NRM | NGP_TERM_DEP: NGP_TAIL(8, false, true, true); break;
+    default: if (wide) NGP_TAIL(16, true, true, true); else NGP_TAIL(8, true, true, true); break;
+    }
+#undef NGP_TAIL
     return ngp_check_launch();
 }
 

@@ -355,8 +355,9 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
 def _fused_tail_ok(model, kwargs, exp_step_factor, classes, fused=None):
     """the one-launch render + loss tail covers the default recipe: sigmoid colours (no tone mapper), black or random
     constant background (no skybox network), detached analytic normals, at most 8 classes (the semantic form of the
-    tail, fused[3] == 'sem': 1 to 16)"""
-    sem = fused is not None and len(fused) > 3 and isinstance(fused[3], str) and fused[3] == 'sem'
+    tail, fused[3] == 'sem', or fused[3] == 'multi' with the semantic term named: 1 to 16)"""
+    sem = fused is not None and len(fused) > 3 and isinstance(fused[3], str) and (
+        fused[3] == 'sem' or (fused[3] == 'multi' and 'semantic' in fused[4]))
     return (getattr(model, 'rgb_act', 'Sigmoid') == 'Sigmoid' and not kwargs.get('use_skybox', False)
             and not getattr(model, 'differentiable_normals', False) and (1 <= classes <= 16 if sem else classes <= 8)
             and hasattr(model, '_field'))
@@ -549,17 +550,103 @@ class _RenderLossDepFn(torch.autograd.Function):
         return (d_sig, d_rgb) + (None,) * 17
 
 
+MULTI_TERMS = ('semantic', 'normal_mono', 'depth_mono')   # bit i of ngp_render_loss_fused_multi's term_mask
+MULTI_WS_INTS = 30                                        # NGP_MULTI_WS_INTS
+
+
+class _RenderLossMultiFn(torch.autograd.Function):
+    """_RenderLossFn for two or three of NeRFLoss's semantic, normal_mono and depth_mono terms in one tail
+    (ngp_render_loss_fused_multi; one term alone takes that term's own kernel).  `named` maps a term's name to its target
+    and weights: 'semantic' -> (labels (n_rays) int64, lambda_sem, lambda_sky), 'normal_mono' -> (normals_gt (n_rays, 3)
+    float32, lambda_nm), 'depth_mono' -> (depth_gt (n_rays) float32, lambda_dm, scene_scale); each term is that of its
+    single Function above.  The class logits and the normal head's raw output get a gradient only when their term is
+    named.  terms (8) = [loss, rgb, opacity, distortion, CELoss, sky_depth, normal_mono, depth_mono], a term that is not
+    named exactly 0.  The workspace (NGP_MULTI_WS_INTS: the labels' n_valid at int 0, the fit's scale, shift and n_valid at
+    int 24, 25, 26) is returned last.  Differentiable through terms[0] only."""
+
+    @staticmethod
+    def forward(ctx, sig, rgb_o, sem_logits, np_raw, dsig_dx, dirs, deltas, ts, rays_a, rgb_gt, named, scale3, T_thr,
+                classes, lambda_opa, lambda_dist, rgb_bg=None):
+        n, nr = sig.shape[0], rays_a.shape[0]
+        dev = sig.device
+        f32 = torch.float32
+        unknown = [k for k in named if k not in MULTI_TERMS]
+        if unknown or not named:
+            raise ValueError(f"the multi tail takes a non-empty subset of {MULTI_TERMS}: got {tuple(named)}")
+        mask = sum(1 << i for i, k in enumerate(MULTI_TERMS) if k in named)
+        labels = normals_gt = depth_gt = None
+        lambda_sem = lambda_sky = lambda_nm = lambda_dm = 0.0
+        scene_scale = 1.0
+        if 'semantic' in named:
+            labels, lambda_sem, lambda_sky = named['semantic']
+            if labels.numel() != nr or labels.dtype != torch.int64:
+                raise ValueError(f"labels must be {nr} int64 entries, one per ray: got {tuple(labels.shape)} {labels.dtype}")
+            if not 1 <= classes <= 16 or sem_logits.shape[1] < classes:
+                raise ValueError(f"the semantic tail takes 1 to 16 classes: got {classes} for logits {tuple(sem_logits.shape)}")
+            labels = labels.contiguous().view(-1)
+        if 'normal_mono' in named:
+            normals_gt, lambda_nm = named['normal_mono']
+            if tuple(normals_gt.shape) != (nr, 3) or normals_gt.dtype != f32:
+                raise ValueError(f"normals must be ({nr}, 3) float32, one row per ray: got {tuple(normals_gt.shape)} "
+                                 f"{normals_gt.dtype}")
+            normals_gt = normals_gt.contiguous()
+        if 'depth_mono' in named:
+            depth_gt, lambda_dm, scene_scale = named['depth_mono']
+            if tuple(depth_gt.shape) != (nr,) or depth_gt.dtype != f32:
+                raise ValueError(f"depths must be ({nr},) float32, one per ray: got {tuple(depth_gt.shape)} {depth_gt.dtype}")
+            depth_gt = depth_gt.contiguous()
+        total = torch.empty(nr, dtype=torch.int64, device=dev)
+        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
+        ws, d_sig, d_rgb = E(n), E(n), E(n, 3)
+        d_sem = E(n, classes) if labels is not None else None
+        d_np = E(n, 3) if normals_gt is not None else None
+        acc = E(10 + MULTI_WS_INTS)   # [terms (8) | vr_samples (int64) | workspace (NGP_MULTI_WS_INTS)]: cleared by one memset
+        terms, vr, multi_ws = acc[:8], acc[8:10].view(torch.int64), acc[10:].view(torch.int32)
+        call("render_loss_fused_multi", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
+             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, mask, labels, float(lambda_sem), float(lambda_sky), normals_gt,
+             float(lambda_nm), depth_gt, float(lambda_dm), float(scene_scale), float(T_thr), int(classes), nr,
+             float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, terms, d_sig,
+             d_rgb, multi_ws, d_sem, d_np)
+        ctx.have_sem, ctx.have_np = d_sem is not None, d_np is not None
+        ctx.save_for_backward(*[t for t in (d_sig, d_rgb, d_sem, d_np) if t is not None])
+        ctx.pad_sem, ctx.pad_np = sem_logits.shape[1] - classes, np_raw.shape[1] - 3
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, multi_ws)
+        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, multi_ws
+
+    @staticmethod
+    def backward(ctx, g_terms, *_unused):
+        saved = list(ctx.saved_tensors)
+        d_sig, d_rgb = saved[0], saved[1]
+        d_sem = d_np = None
+        if ctx.have_sem:
+            d_sem = saved[2]
+            if ctx.pad_sem:
+                d_sem = F.pad(d_sem, (0, ctx.pad_sem))
+        if ctx.have_np:
+            d_np = saved[-1]
+            if ctx.pad_np:
+                d_np = F.pad(d_np, (0, ctx.pad_np))
+        return (d_sig, d_rgb, d_sem, d_np) + (None,) * 13
+
+
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
     """fused = (rgb_gt, lambda_opa, lambda_distortion) or, for the embed_msk recipe, those three followed by
     (mask (n_rays[, 1]), size_delta), or, for the semantic recipe, by ('sem', labels (n_rays) int64, lambda_sem,
     lambda_sky), or, for the normal_mono recipe, by ('nrm', normals_gt (n_rays, 3), lambda_nm), or, for the depth_mono
-    recipe, by ('dep', depth_gt (n_rays), lambda_dm, scene_scale)"""
+    recipe, by ('dep', depth_gt (n_rays), lambda_dm, scene_scale), or, for several of those three terms at once, by
+    ('multi', {term: (target, weights...)}) as _RenderLossMultiFn documents"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
     rgb_gt, lambda_opa, lambda_dist = fused[:3]
     rgb_bg = None
     if kwargs.get('exp_step_factor', 0.) != 0 and kwargs.get('random_bg', False):
         rgb_bg = torch.rand(3, device=xyzs.device)      # rendering.py:239 (drawn at the same place in the RNG stream)
-    if len(fused) == 7 and fused[3] == 'sem':
+    if len(fused) == 5 and isinstance(fused[3], str) and fused[3] == 'multi':
+        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, _) = _RenderLossMultiFn.apply(
+            sig, rgb_o, sem_logits, np_raw, dsig_dx, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
+            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, rgb_bg)
+    elif len(fused) == 7 and fused[3] == 'sem':
         (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossSemFn.apply(
             sig, rgb_o, sem_logits, dsig_dx, np_raw, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
             rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5],

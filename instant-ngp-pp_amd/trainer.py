@@ -27,7 +27,7 @@ import torch.distributed as dist
 from ._lib import call
 from .appearance import RayCodes
 from .losses import NeRFLoss, nerf_loss_and_grads
-from .rendering import MAX_SAMPLES, MarchAhead, _fused_tail_ok, render
+from .rendering import MAX_SAMPLES, MULTI_TERMS, MarchAhead, _fused_tail_ok, render
 
 _f32 = torch.float32
 
@@ -157,8 +157,17 @@ class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
-                 semantic=False, normal_mono=False, depth_mono=False):
-        """depth_mono: NeRFLoss's depth_mono term (losses.py:7-30, 125-131: composited depth against per-pixel monocular depth
+                 semantic=False, normal_mono=False, depth_mono=False, multi_terms=()):
+        """multi_terms: a non-empty subset of ('semantic', 'normal_mono', 'depth_mono'): those of NeRFLoss's optional terms
+        TOGETHER on the fused render + loss tail (ngp_render_loss_fused_multi), as the reference's street-scene recipes use
+        them.  Each term is the one its own flag below trains; step() then needs exactly the named terms' targets (labels=,
+        normals=, depths=), and results['loss_terms'] holds the 8 terms [loss, rgb, opacity, distortion, CELoss, sky_depth,
+        normal_mono, depth_mono].  The step takes the exact gradient norm when semantic or normal_mono is named and keeps
+        the norm-bound clip for ('depth_mono',) alone.  Combines with embedding_a and random_bg; not with semantic=True,
+        normal_mono=True, depth_mono=True (each of those is one term alone), msk_model, pose_refiner, a skybox, a tone-mapped
+        model, differentiable normals, an optional term in loss_kwargs (normal_ref included) or a num_classes that is not the
+        model's head (1..16 with the semantic term, at most 8 without).
+        depth_mono: NeRFLoss's depth_mono term (losses.py:7-30, 125-131: composited depth against per-pixel monocular depth
         up to the batch's least-squares scale and shift, weight lambda_depth_mono) on the fused render + loss tail
         (ngp_render_loss_fused_dep: a fit kernel, then the tail).  step() then needs depths= (n_rays) float, the raw depth
         (z = depth / 25); zero, negative and NaN mark a ray without depth, which takes no part in the fit, the term or any
@@ -269,6 +278,30 @@ class NGPTrainer:
                                     (f"num_classes = {num_classes} above 8", int(num_classes) > 8)) if bad]
             if why:
                 raise ValueError("depth_mono=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
+        if isinstance(multi_terms, str):
+            multi_terms = (multi_terms,)
+        multi_terms = tuple(multi_terms or ())
+        unknown = [t for t in multi_terms if t not in MULTI_TERMS]
+        if unknown or len(set(multi_terms)) != len(multi_terms):
+            raise ValueError(f"multi_terms is a subset of {MULTI_TERMS} without repeats: got {multi_terms}")
+        self.multi_terms = tuple(t for t in MULTI_TERMS if t in multi_terms)
+        if self.multi_terms:
+            with_sem = "semantic" in self.multi_terms
+            head = getattr(getattr(model, "semantic_header", None), "n_output_dims", None)
+            why = [w for w, bad in (("semantic=True", self.semantic), ("normal_mono=True", self.normal_mono),
+                                    ("depth_mono=True", self.depth_mono),
+                                    ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
+                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                                    ("an optional term in loss_kwargs", optional),
+                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
+                                    (f"num_classes = {num_classes} outside 1..16", with_sem and not 1 <= int(num_classes) <= 16),
+                                    (f"num_classes = {num_classes} above 8", not with_sem and int(num_classes) > 8),
+                                    (f"a model with {head} classes for num_classes = {num_classes}",
+                                     with_sem and head != int(num_classes))) if bad]
+            if why:
+                raise ValueError(f"multi_terms={self.multi_terms} runs on the fused render + loss tail, which does not take "
+                                 + ", ".join(why))
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -446,6 +479,9 @@ class NGPTrainer:
              normals=None, depths=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
 
+        A trainer built with multi_terms= needs exactly the named terms' targets among labels=, normals=, depths= (as
+        described below), and takes no target= and no per-step loss term.
+
         depths: (n_rays) float raw monocular depth of every ray (zero, negative, NaN: none), required by a trainer built with
         depth_mono=True (which then takes no target= and no per-step loss term).
 
@@ -475,6 +511,26 @@ class NGPTrainer:
             raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
         if self.embedding_a is not None and img_idxs is None:
             raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
+        multi = getattr(self, 'multi_terms', ())   # (stand-ins in the host tests carry only the single flags)
+        if multi:
+            for name, arg, given in (("semantic", "labels", labels), ("normal_mono", "normals", normals),
+                                     ("depth_mono", "depths", depths)):
+                if name in multi and given is None:
+                    raise ValueError(f"this trainer was built with multi_terms={multi}: step() needs {arg}=")
+                if name not in multi and given is not None:
+                    raise ValueError(f"{arg}= is for a trainer whose multi_terms name '{name}': this one has {multi}")
+            if "semantic" in multi and labels.numel() != rgb_gt.shape[0]:
+                raise ValueError(f"labels= must hold {rgb_gt.shape[0]} entries, one per ray: got {tuple(labels.shape)}")
+            if "normal_mono" in multi and (normals.dim() != 2 or tuple(normals.shape) != (rgb_gt.shape[0], 3)
+                                           or not normals.is_floating_point()):
+                raise ValueError(f"normals= must be ({rgb_gt.shape[0]}, 3) float: got {tuple(normals.shape)} {normals.dtype}")
+            if "depth_mono" in multi and (tuple(depths.shape) != (rgb_gt.shape[0],) or not depths.is_floating_point()):
+                raise ValueError(f"depths= must be ({rgb_gt.shape[0]},) float: got {tuple(depths.shape)} {depths.dtype}")
+            if target or loss_kwargs:
+                raise ValueError(f"this trainer was built with multi_terms={multi}: the step stays on the fused render + loss "
+                                 "tail and takes no target= and no per-step loss term")
+            if not rays_o.is_cuda:
+                raise RuntimeError("multi_terms needs CUDA tensors: the fused tail has no other route")
         if self.semantic:
             if labels is None:
                 raise ValueError("this trainer was built with semantic=True: step() needs labels= (the class of every ray)")
@@ -483,7 +539,7 @@ class NGPTrainer:
                                  "and takes no target= and no per-step loss term")
             if not rays_o.is_cuda:
                 raise RuntimeError("semantic=True needs CUDA tensors: the fused tail has no other route")
-        elif labels is not None:
+        elif labels is not None and "semantic" not in multi:
             raise ValueError("labels= is for a trainer built with semantic=True")
         if self.normal_mono:
             if normals is None:
@@ -496,7 +552,7 @@ class NGPTrainer:
                                  "tail and takes no target= and no per-step loss term")
             if not rays_o.is_cuda:
                 raise RuntimeError("normal_mono=True needs CUDA tensors: the fused tail has no other route")
-        elif normals is not None:
+        elif normals is not None and "normal_mono" not in multi:
             raise ValueError("normals= is for a trainer built with normal_mono=True")
         if self.depth_mono:
             if depths is None:
@@ -509,7 +565,7 @@ class NGPTrainer:
                                  "tail and takes no target= and no per-step loss term")
             if not rays_o.is_cuda:
                 raise RuntimeError("depth_mono=True needs CUDA tensors: the fused tail has no other route")
-        elif depths is not None:
+        elif depths is not None and "depth_mono" not in multi:
             raise ValueError("depths= is for a trainer built with depth_mono=True")
         ref = self.pose_refiner
         if ref is not None:
@@ -576,6 +632,20 @@ class NGPTrainer:
                     # (rgb_act or differentiable_normals changed after construction, ...): never a step without the depths
                     raise RuntimeError("depth_mono=True: the model no longer fits the fused depth tail "
                                        "(rendering._fused_tail_ok); the depths would be left out of the loss")
+            if multi:
+                named = {}
+                if "semantic" in multi:
+                    named["semantic"] = (labels.view(-1).to(torch.int64), self.loss_fn.lambda_semantic, self.loss_fn.lambda_sky)
+                if "normal_mono" in multi:
+                    named["normal_mono"] = (normals.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_normal_mono)
+                if "depth_mono" in multi:
+                    named["depth_mono"] = (depths.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_depth_mono,
+                                           float(model.scale))
+                extra['_fused_loss'] += ('multi', named)
+                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
+                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the targets
+                    raise RuntimeError(f"multi_terms={multi}: the model no longer fits the fused tail "
+                                       "(rendering._fused_tail_ok); the targets would be left out of the loss")
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
@@ -590,7 +660,8 @@ class NGPTrainer:
         # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the
         # start; the depth_mono term only changes d_sigmas, which the density head's backward notes: the bound holds)
         self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
-                                and not self.semantic and not self.normal_mono)
+                                and not self.semantic and not self.normal_mono
+                                and "semantic" not in multi and "normal_mono" not in multi)
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
@@ -604,9 +675,14 @@ class NGPTrainer:
         if self.depth_mono and ('_loss_terms' not in results or results['_loss_terms'].numel() != 5):
             raise RuntimeError("depth_mono=True: render() did not take the fused depth tail (rendering._fused_tail_ok); the "
                                "depths would be left out of the loss")
+        if multi and ('_loss_terms' not in results or results['_loss_terms'].numel() != 8):
+            raise RuntimeError(f"multi_terms={multi}: render() did not take the fused tail (rendering._fused_tail_ok); the "
+                               "targets would be left out of the loss")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]
+            if multi:
+                results['loss_terms'] = terms.detach()   # the 8 terms of ngp_render_loss_fused_multi: for a caller's log
             if self.depth_mono:
                 results['loss_terms'] = terms.detach()   # [loss, rgb, opacity, distortion, depth_mono]: for a caller's log
             torch.autograd.backward([terms], [self._unit_seed(terms)])

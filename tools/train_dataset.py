@@ -19,6 +19,8 @@ reference: train.py:82-392).  GPU only.
       --normal_mono --ckpt_path out/nrm.ckpt   # normal head on the proxy's analytic normal maps: held-out angle in degrees
   python tools/train_dataset.py --make_proxy /tmp/proxy_dep --dataset_name tnt --downsample 0.125 --num_epochs 2 \
       --depth_mono --ckpt_path out/dep.ckpt   # depth_mono term on the proxy's depth maps (right up to scale and shift): held-out abs-rel
+  python tools/train_dataset.py --make_proxy /tmp/proxy_all --dataset_name tnt --downsample 0.125 --num_epochs 2 \
+      --multi_terms semantic normal_mono depth_mono --num_classes 5   # the three terms together on one fused tail
 """
 import argparse
 import json
@@ -39,6 +41,7 @@ from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
 from ngp_amd.pose import PoseRefiner, perturb_poses, pose_errors
+from ngp_amd.rendering import MULTI_TERMS
 from ngp_amd.trainer import NGPTrainer
 
 
@@ -77,7 +80,8 @@ def cameras_outside(train_set, scale):
 
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
           render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
-          num_classes=7, normal_mono=False, lambda_normal_mono=None, depth_mono=False, lambda_depth_mono=None):
+          num_classes=7, normal_mono=False, lambda_normal_mono=None, depth_mono=False, lambda_depth_mono=None,
+          multi_terms=()):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
@@ -86,8 +90,16 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     the normal head of --normal_mono, fed with the sampler's normals (lambda_normal_mono: the term's weight instead of
     NeRFLoss's 1e-3); depth_mono: the depth_mono term of --depth_mono, fed with the sampler's depths (lambda_depth_mono: the
     term's weight instead of NeRFLoss's 1); the trainer then carries `terms_log`, the loss terms of every step as device
-    tensors (read after the run: nothing is read while it trains)"""
+    tensors (read after the run: nothing is read while it trains); multi_terms: the terms of --multi_terms, together on one
+    tail (NGPTrainer(multi_terms=...)): the sampler feeds each named term as its own flag would, and `terms_log` holds the
+    8 terms of every step"""
     train_set.batch_size = batch_size
+    multi_terms = tuple(multi_terms or ())
+    if multi_terms and (semantic or normal_mono or depth_mono):
+        raise ValueError("multi_terms names the terms itself: not together with semantic, normal_mono or depth_mono")
+    semantic = semantic or "semantic" in multi_terms
+    normal_mono = normal_mono or "normal_mono" in multi_terms
+    depth_mono = depth_mono or "depth_mono" in multi_terms
     if depth_mono:
         if not hasattr(train_set, "depths_2d"):
             raise ValueError("--depth_mono needs per-pixel depths: the dataset has none (the tnt layout reads depth/*.npy "
@@ -110,14 +122,17 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     more = {} if embedding_a is None else {"embedding_a": embedding_a}
     if pose_refiner is not None:
         more.update(pose_refiner=pose_refiner, pose_lr=pose_lr)
-    if semantic:
-        more.update(semantic=True)
     if semantic or num_classes != 7:
         more.update(num_classes=num_classes)
-    if normal_mono:
-        more.update(normal_mono=True)
-    if depth_mono:
-        more.update(depth_mono=True)
+    if multi_terms:
+        more.update(multi_terms=multi_terms)
+    else:
+        if semantic:
+            more.update(semantic=True)
+        if normal_mono:
+            more.update(normal_mono=True)
+        if depth_mono:
+            more.update(depth_mono=True)
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
                          exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
     if lambda_normal_mono is not None:
@@ -167,7 +182,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             more["depths"] = cur[8]
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
-        if depth_mono:
+        if depth_mono or multi_terms:
             trainer.terms_log.append(res["loss_terms"])
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
@@ -261,8 +276,21 @@ def parse_args(argv=None):
                     help="load per-pixel monocular depth maps (depth/*.npy of the tnt layout) and train with NeRFLoss's "
                          "depth_mono term (the reference's --depth_mono); the JSON line gains test_depth_absrel_mean")
     ap.add_argument("--lambda_depth_mono", type=float, default=None, help="weight of the depth_mono term (NeRFLoss: 1)")
+    ap.add_argument("--multi_terms", nargs="+", choices=MULTI_TERMS, default=(),
+                    help="train several of the semantic, normal_mono and depth_mono terms together on one fused tail "
+                         "(the reference's street-scene recipes set --render_semantic and --normal_mono together and add "
+                         "depth_mono): each named term loads its maps and reports its metrics as its own flag does; the "
+                         "JSON line gains loss_terms (8) and every optional term's mean over the first and last ten steps")
     ap.add_argument("--proxy_views", type=int, default=108, help="views of the scene --make_proxy writes")
     args = ap.parse_args(argv)
+    args.multi_terms = tuple(t for t in MULTI_TERMS if t in args.multi_terms)
+    if args.multi_terms and (args.render_semantic or args.normal_mono or args.depth_mono):
+        ap.error("--multi_terms names the terms itself: not together with --render_semantic, --normal_mono or --depth_mono")
+    if args.multi_terms and (args.embed_msk or args.optimize_ext):
+        ap.error("--multi_terms combines with --embed_a and --random_bg, not with --embed_msk or --optimize_ext")
+    if args.make_proxy and args.multi_terms and args.dataset_name != "tnt":
+        ap.error("--make_proxy with --multi_terms writes a scene with labels, normal and depth maps: --dataset_name tnt "
+                 "(the layout that carries all three)")
     if args.make_proxy and args.depth_mono and args.dataset_name != "tnt":
         ap.error("--make_proxy with --depth_mono writes a scene with depth maps: --dataset_name tnt (the layout that "
                  "carries depth/*.npy)")
@@ -281,7 +309,7 @@ def parse_args(argv=None):
         ap.error("--make_proxy with --render_semantic writes a labelled scene: --dataset_name tnt or colmap (the layouts "
                  "that carry semantic/*.pgm)")
     if args.scale is None:
-        args.scale = 2.0 if args.make_proxy and args.render_semantic else 0.5
+        args.scale = 2.0 if args.make_proxy and (args.render_semantic or "semantic" in args.multi_terms) else 0.5
     if args.render_semantic and (args.embed_msk or args.optimize_ext):
         ap.error("--render_semantic combines with --embed_a and --random_bg, not with --embed_msk or --optimize_ext")
     if not 1 <= args.embed_a_len <= 32:
@@ -332,6 +360,30 @@ def make_proxy_with_depths(root, scene, n_quad=256):
     return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], depths=depths)
 
 
+def make_proxy_with_all_maps(root, scene, n_quad=256):
+    """the analytic proxy with labels, world-space normals and monocular depth maps (as make_proxy_with_depths writes them)
+    together in the tnt layout, every 8th view held out"""
+    from ngp_amd.datasets import export
+    n = scene.poses.shape[0]
+    images = export.render_scene_views(scene, range(n), rgba=False, n_quad=n_quad)
+    labels = export.render_scene_labels(scene, range(n), n_quad=n_quad)
+    normals = export.render_scene_normals(scene, range(n), n_quad=n_quad)
+    D = export.render_scene_depths(scene, range(n), n_quad=n_quad)
+    depths = np.where(D > 0, 25.0 * (PROXY_DEPTH_SCALE * D + PROXY_DEPTH_SHIFT), 0.0).astype(np.float32)
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], labels=labels,
+                             normals=normals, depths=depths)
+
+
+def multi_terms_summary(terms_log, k=10):
+    """{term: (mean over the first k steps, over the last k steps)} for terms[4:8] of train()'s terms_log"""
+    t = torch.stack([v.detach() for v in terms_log]).cpu()
+    k = max(1, min(k, len(t) // 2))
+    names = ("CELoss", "sky_depth", "normal_mono", "depth_mono")
+    return {nm: (float(t[:k, 4 + i].mean()), float(t[-k:, 4 + i].mean())) for i, nm in enumerate(names)}
+
+
 def terms_summary(terms_log, k=10):
     """(number of loss terms, mean of the last term over the first k steps, over the last k steps) of train()'s terms_log"""
     t = torch.stack([v.detach() for v in terms_log]).cpu()
@@ -348,9 +400,12 @@ def main():
         from ngp_amd.synthetic import LegoProxy
         wh = int(800 * args.downsample)
         scene = LegoProxy(n_images=args.proxy_views, img_wh=(wh, wh), device=dev)
-        if args.render_semantic:
-            root = make_labelled_proxy(args.make_proxy, args.dataset_name, scene)
+        if args.multi_terms:
+            root = make_proxy_with_all_maps(args.make_proxy, scene)
             args.downsample = 1.0   # (these layouts are written at the size they are read at)
+        elif args.render_semantic:
+            root = make_labelled_proxy(args.make_proxy, args.dataset_name, scene)
+            args.downsample = 1.0
         elif args.normal_mono:
             root = make_proxy_with_normals(args.make_proxy, scene)
             args.downsample = 1.0
@@ -360,20 +415,24 @@ def main():
         else:
             root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
     loader = dataset_dict[args.dataset_name]
-    sem = dict(use_sem=True, num_classes=args.num_classes) if args.render_semantic else {}
-    if args.normal_mono:
+    with_sem = args.render_semantic or "semantic" in args.multi_terms
+    with_nrm = args.normal_mono or "normal_mono" in args.multi_terms
+    with_dep = args.depth_mono or "depth_mono" in args.multi_terms
+    flag = "--multi_terms" if args.multi_terms else None
+    sem = dict(use_sem=True, num_classes=args.num_classes) if with_sem else {}
+    if with_nrm:
         sem["normal_mono"] = True
-    if args.depth_mono:
+    if with_dep:
         sem["depth_mono"] = True
     train_set = loader(root, "train", args.downsample, device=dev, **sem)
     test_set = loader(root, "test", args.downsample, device=dev, **sem)
-    if args.render_semantic and not hasattr(train_set, "labels"):
-        raise SystemExit(f"--render_semantic: {root} holds no labels (semantic/*.pgm) for the {args.dataset_name} loader")
-    if args.normal_mono and not hasattr(train_set, "normals"):
-        raise SystemExit(f"--normal_mono: {root} holds no normal maps (normal/*.npy) for the {args.dataset_name} loader")
-    if args.depth_mono and not hasattr(train_set, "depths_2d"):
-        raise SystemExit(f"--depth_mono: {root} holds no depth maps (depth/*.npy) for the {args.dataset_name} loader")
-    if args.render_semantic:
+    if with_sem and not hasattr(train_set, "labels"):
+        raise SystemExit(f"{flag or '--render_semantic'}: {root} holds no labels (semantic/*.pgm) for the {args.dataset_name} loader")
+    if with_nrm and not hasattr(train_set, "normals"):
+        raise SystemExit(f"{flag or '--normal_mono'}: {root} holds no normal maps (normal/*.npy) for the {args.dataset_name} loader")
+    if with_dep and not hasattr(train_set, "depths_2d"):
+        raise SystemExit(f"{flag or '--depth_mono'}: {root} holds no depth maps (depth/*.npy) for the {args.dataset_name} loader")
+    if with_sem:
         labels_of_split(train_set)
         if hasattr(test_set, "labels"):
             labels_of_split(test_set)
@@ -396,13 +455,13 @@ def main():
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
           msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
           semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono,
-                    depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono)
+                    depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono, multi_terms=args.multi_terms)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
     if embedding_a is not None:   # train.py:153-154: the test split is rendered with the code of training image 0
         more["embedding_a"] = embedding_a(0).detach()
-    if args.render_semantic or args.num_classes != 7:
+    if with_sem or args.num_classes != 7:
         more["num_classes"] = args.num_classes
     res = evaluate_split(model, test_set, on_image=_save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None,
                          exp_step_factor=args.exp_step_factor, **more)
@@ -426,6 +485,11 @@ def main():
         n_terms, first, last = terms_summary(trainer.terms_log)
         out.update(loss_terms=n_terms, depth_mono_term_first=first, depth_mono_term_last=last,
                    lambda_depth_mono=trainer.loss_fn.lambda_depth_mono)
+    if args.multi_terms:
+        out.update(loss_terms=int(trainer.terms_log[0].numel()), multi_terms=list(args.multi_terms),
+                   lambda_depth_mono=trainer.loss_fn.lambda_depth_mono)
+        for nm, (first, last) in multi_terms_summary(trainer.terms_log).items():
+            out[f"{nm}_term_first"], out[f"{nm}_term_last"] = first, last
     if pose_refiner is not None:   # mean translation (scene units) and rotation (degrees) error against the dataset's poses
         before = pose_errors(pose_refiner.poses.cpu(), true_poses.cpu())
         after = pose_errors(pose_refiner.refined_poses().detach().cpu(), true_poses.cpu())
