@@ -1381,29 +1381,18 @@ int ngp_nerf_loss(const float* rgb, const float* target_rgb, const float* opacit
     return ngp_check_launch();
 }
 
-// shared body of ngp_render_loss_fused / ngp_render_loss_fused_masked (mask == NULL: the unmasked kernel, 4 terms)
-static int render_loss_fused_launch(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
-                                    const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
-                                    const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
-                                    const float* target_rgb, const float* rgb_bg, const float* mask, float size_delta,
-                                    float T_threshold, int classes, int n_rays, float lambda_opacity,
-                                    float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
-                                    float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
-                                    float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, float* dL_dmask,
-                                    void* stream)
+// ---- the fused render + loss tail: six entries on one host path.  Every entry: tail_args plus its own few fields, tail_check
+// with its own extra checks, tail_clear, its pre-kernels (the label count, the depth fit), tail_launch.
+
+// the one place that fills RenderLossArgs from the arguments every entry shares; every optional field is set to "absent"
+static RenderLossArgs tail_args(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                                const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                                const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                                const float* target_rgb, const float* rgb_bg, float T_threshold, int classes, int n_rays,
+                                float lambda_opacity, float lambda_distortion, int64_t* total_samples, int64_t* vr_samples,
+                                float* opacity, float* depth, float* rgb, float* normal_pred, float* sem, float* ws,
+                                float* loss_o, float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs)
 {
-    if (n_rays < 0 || classes < 0 || classes > 8 || ld_normal < 3 || ld_sem < classes) return NGP_EINVAL;
-    if (n_rays == 0) return NGP_OK;
-    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
-        (classes && !sem) || !loss_o || !loss_p || !terms) return NGP_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n_terms = mask ? 5 : 4, gap = mask ? 6 : 4;   // (an int64 behind 5 floats sits at float 6)
-    if (reinterpret_cast<char*>(vr_samples) == reinterpret_cast<char*>(terms) + gap * sizeof(float)) {   // adjacent: one fill
-        if (hipMemsetAsync(terms, 0, gap * sizeof(float) + sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-    } else {
-        if (hipMemsetAsync(terms, 0, n_terms * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-    }
     RenderLossArgs a;
     a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
     a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
@@ -1412,18 +1401,87 @@ static int render_loss_fused_launch(const float* sigmas, const float* rgbs, cons
     a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
     a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
     a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
-    a.mask = mask; a.g_ms = size_delta / n_rays; a.d_mask = dL_dmask;
+    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
     a.slot_nm = a.slot_dm = 4;
+    return a;
+}
+
+// The checks every entry shares, in the order every entry answers them: the ranges (a bad one is refused for an empty
+// batch too), an empty batch is NGP_OK, then the pointers.  `ranges_ok` and `ptrs_ok` are the entry's own checks of either
+// kind; TAIL_GO: neither refused nor empty, the entry goes on.
+constexpr int TAIL_GO = 1;
+static int tail_check(const RenderLossArgs& a, int classes_min, int classes_max, bool ranges_ok, bool ptrs_ok)
+{
+    if (!ranges_ok || a.n_rays < 0 || a.classes < classes_min || a.classes > classes_max || a.ld_np < 3 ||
+        a.ld_sem < a.classes) return NGP_EINVAL;
+    if (a.n_rays == 0) return NGP_OK;
+    if (!ptrs_ok || !a.rays_a || !a.gt || !a.total_samples || !a.vr_samples || !a.opacity || !a.depth || !a.rgb ||
+        !a.normal || (a.classes && !a.sem) || !a.Ro || !a.Rp || !a.terms) return NGP_EINVAL;
+    return TAIL_GO;
+}
+
+// what the entries with an optional term ask on top: every gradient and ws, the workspace 8-byte aligned (it holds doubles)
+static bool tail_trained_ok(const RenderLossArgs& a, const int* term_ws)
+{
+    return a.d_sigmas && a.d_rgbs && a.ws && term_ws && !(reinterpret_cast<uintptr_t>(term_ws) & 7);
+}
+
+// terms (n_terms floats), vr_samples (an int64) and the workspace (ws_ints int32; NULL: none to clear) start at 0.  One
+// fill when vr_samples sits vr_at floats behind terms and the workspace ws_at floats behind them, else one fill each.
+static int tail_clear(float* terms, size_t n_terms, size_t vr_at, int64_t* vr_samples, int* ws, size_t ws_at, size_t ws_ints,
+                      hipStream_t st)
+{
+    char* base = reinterpret_cast<char*>(terms);
+    if (reinterpret_cast<char*>(vr_samples) == base + vr_at * sizeof(float) &&
+        (!ws || reinterpret_cast<char*>(ws) == base + ws_at * sizeof(float))) {
+        if (hipMemsetAsync(terms, 0, (ws ? ws_at + ws_ints : vr_at + 2) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+        return NGP_OK;
+    }
+    if (hipMemsetAsync(terms, 0, n_terms * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
+    if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
+    if (ws && hipMemsetAsync(ws, 0, ws_ints * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
+    return NGP_OK;
+}
+
+// the 13 instantiations of the tail: the default and the masked one, and every non-empty set of the three optional terms,
+// those with the semantic term at 8 and at 16 classes
+static int tail_launch(bool masked, int term_mask, int classes, int n_rays, hipStream_t st, const RenderLossArgs& a)
+{
+    const dim3 grid = seg_grid(n_rays), block(256);
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
-    if (mask)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, true, false, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
+#define NGP_TAIL(CM, M, S, N, D) hipLaunchKernelGGL((render_loss_fused_kernel<CM, 32, M, S, N, D>), grid, block, 0, st, a)
+    const bool wide = classes > 8;   // (only with SEM: the entries check it)
+    switch (masked ? -1 : term_mask) {
+    case -1: NGP_TAIL(8, true, false, false, false); break;
+    case 0: NGP_TAIL(8, false, false, false, false); break;
+    case NGP_TERM_SEM: if (wide) NGP_TAIL(16, false, true, false, false); else NGP_TAIL(8, false, true, false, false); break;
+    case NGP_TERM_NRM: NGP_TAIL(8, false, false, true, false); break;
+    case NGP_TERM_DEP: NGP_TAIL(8, false, false, false, true); break;
+    case NGP_TERM_SEM | NGP_TERM_NRM:
+        if (wide) NGP_TAIL(16, false, true, true, false); else NGP_TAIL(8, false, true, true, false); break;
+    case NGP_TERM_SEM | NGP_TERM_DEP:
+        if (wide) NGP_TAIL(16, false, true, false, true); else NGP_TAIL(8, false, true, false, true); break;
+    case NGP_TERM_NRM | NGP_TERM_DEP: NGP_TAIL(8, false, false, true, true); break;
+    default: if (wide) NGP_TAIL(16, false, true, true, true); else NGP_TAIL(8, false, true, true, true); break;
+    }
+#undef NGP_TAIL
     return ngp_check_launch();
+}
+
+// shared body of ngp_render_loss_fused / ngp_render_loss_fused_masked (mask == NULL: the unmasked kernel, 4 terms)
+static int render_loss_fused_launch(RenderLossArgs a, const float* mask, float size_delta, float* dL_dmask, void* stream)
+{
+    const int rc = tail_check(a, 0, 8, true, true);
+    if (rc != TAIL_GO) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // (an int64 behind 5 floats sits at float 6)
+    if (tail_clear(a.terms, mask ? 5 : 4, mask ? 6 : 4, a.vr_samples, nullptr, 0, 0, st) != NGP_OK) return NGP_ELAUNCH;
+    a.mask = mask; a.g_ms = size_delta / a.n_rays; a.d_mask = dL_dmask;
+    return tail_launch(mask != nullptr, 0, a.classes, a.n_rays, st, a);
 }
 
 int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1434,10 +1492,11 @@ int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* d
                           float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                           float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, void* stream)
 {
-    return render_loss_fused_launch(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas,
-                                    ts, rays_a, target_rgb, rgb_bg, nullptr, 0.0f, T_threshold, classes, n_rays,
-                                    lambda_opacity, lambda_distortion, total_samples, vr_samples, opacity, depth, rgb,
-                                    normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs, nullptr, stream);
+    return render_loss_fused_launch(
+        tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts, rays_a,
+                  target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
+                  vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
+        nullptr, 0.0f, nullptr, stream);
 }
 
 int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1450,10 +1509,11 @@ int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const f
                                  float* dL_dsigmas, float* dL_drgbs, float* dL_dmask, void* stream)
 {
     if (n_rays > 0 && (!mask || !dL_dmask)) return NGP_EINVAL;
-    return render_loss_fused_launch(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas,
-                                    ts, rays_a, target_rgb, rgb_bg, mask, size_delta, T_threshold, classes, n_rays,
-                                    lambda_opacity, lambda_distortion, total_samples, vr_samples, opacity, depth, rgb,
-                                    normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs, dL_dmask, stream);
+    return render_loss_fused_launch(
+        tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts, rays_a,
+                  target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
+                  vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
+        mask, size_delta, dL_dmask, stream);
 }
 
 int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1466,40 +1526,20 @@ int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const floa
                               float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* sem_ws,
                               float* dL_dsem_logits, void* stream)
 {
-    if (n_rays < 0 || classes < 1 || classes > 16 || ld_normal < 3 || ld_sem < classes) return NGP_EINVAL;
-    if (n_rays == 0) return NGP_OK;
-    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred || !sem ||
-        !loss_o || !loss_p || !terms || !labels || !sem_ws || !sem_logits || !dL_dsem_logits || !dL_dsigmas || !dL_drgbs ||
-        !ws || (reinterpret_cast<uintptr_t>(sem_ws) & 7)) return NGP_EINVAL;
+    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
+                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
+                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
+                                 dL_dsigmas, dL_drgbs);
+    const int rc = tail_check(a, 1, 16, true, tail_trained_ok(a, sem_ws) && labels && sem_logits && dL_dsem_logits);
+    if (rc != TAIL_GO) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // terms (6) with vr_samples right behind them (float 6): one fill
-    if (reinterpret_cast<char*>(vr_samples) == reinterpret_cast<char*>(terms) + 6 * sizeof(float)) {
-        if (hipMemsetAsync(terms, 0, 6 * sizeof(float) + sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-    } else {
-        if (hipMemsetAsync(terms, 0, 6 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-    }
+    // terms (6) with vr_samples right behind them (float 6); the label count below clears the workspace
+    if (tail_clear(terms, 6, 6, vr_samples, nullptr, 0, 0, st) != NGP_OK) return NGP_ELAUNCH;
     // n_valid depends on the labels alone and every seed needs it: counted (and the workspace cleared) on the same stream
     // ahead of the tail
     hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, rays_a, n_rays, classes, sem_ws);
-    RenderLossArgs a;
-    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
-    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
-    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
-    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
-    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
-    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
-    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
-    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
     a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits;
-    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
-    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
-    a.slot_nm = a.slot_dm = 4;
-    if (classes <= 8)
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((render_loss_fused_kernel<16, 32, false, true, false, false>), seg_grid(n_rays), dim3(256), 0, st, a);
-    return ngp_check_launch();
+    return tail_launch(false, NGP_TERM_SEM, classes, n_rays, st, a);
 }
 
 int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1511,37 +1551,17 @@ int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const floa
                               float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
                               float* dL_dsigmas, float* dL_drgbs, int* nrm_ws, float* dL_dnormal_head, void* stream)
 {
-    if (n_rays < 0 || classes < 0 || classes > 8 || ld_normal < 3 || ld_sem < classes) return NGP_EINVAL;
-    if (n_rays == 0) return NGP_OK;
-    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
-        (classes && !sem) || !loss_o || !loss_p || !terms || !normals_gt || !nrm_ws || !normal_head || !dL_dnormal_head ||
-        !dL_dsigmas || !dL_drgbs || !ws || (reinterpret_cast<uintptr_t>(nrm_ws) & 7)) return NGP_EINVAL;
+    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
+                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
+                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
+                                 dL_dsigmas, dL_drgbs);
+    const int rc = tail_check(a, 0, 8, true, tail_trained_ok(a, nrm_ws) && normals_gt && normal_head && dL_dnormal_head);
+    if (rc != TAIL_GO) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8: one fill
-    char* base = reinterpret_cast<char*>(terms);
-    if (reinterpret_cast<char*>(vr_samples) == base + 6 * sizeof(float) &&
-        reinterpret_cast<char*>(nrm_ws) == base + 8 * sizeof(float)) {
-        if (hipMemsetAsync(terms, 0, (8 + NGP_NRM_WS_INTS) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-    } else {
-        if (hipMemsetAsync(terms, 0, 5 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(nrm_ws, 0, NGP_NRM_WS_INTS * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
-    }
-    RenderLossArgs a;
-    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
-    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
-    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
-    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
-    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
-    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
-    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
-    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
-    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
+    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8
+    if (tail_clear(terms, 5, 6, vr_samples, nrm_ws, 8, NGP_NRM_WS_INTS, st) != NGP_OK) return NGP_ELAUNCH;
     a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head;
-    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
-    a.slot_nm = a.slot_dm = 4;
-    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, true, false>), seg_grid(n_rays), dim3(256), 0, st, a);
-    return ngp_check_launch();
+    return tail_launch(false, NGP_TERM_NRM, classes, n_rays, st, a);
 }
 
 int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1553,40 +1573,20 @@ int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const floa
                               float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                               float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* dep_ws, void* stream)
 {
-    if (n_rays < 0 || classes < 0 || classes > 8 || ld_normal < 3 || ld_sem < classes || !(scene_scale > 0.0f)) return NGP_EINVAL;
-    if (n_rays == 0) return NGP_OK;
-    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
-        (classes && !sem) || !loss_o || !loss_p || !terms || !depth_gt || !dep_ws || !dL_dsigmas || !dL_drgbs || !ws ||
-        (reinterpret_cast<uintptr_t>(dep_ws) & 7)) return NGP_EINVAL;
+    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
+                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
+                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
+                                 dL_dsigmas, dL_drgbs);
+    const int rc = tail_check(a, 0, 8, scene_scale > 0.0f, tail_trained_ok(a, dep_ws) && depth_gt);
+    if (rc != TAIL_GO) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8: one fill
-    char* base = reinterpret_cast<char*>(terms);
-    if (reinterpret_cast<char*>(vr_samples) == base + 6 * sizeof(float) &&
-        reinterpret_cast<char*>(dep_ws) == base + 8 * sizeof(float)) {
-        if (hipMemsetAsync(terms, 0, (8 + NGP_DEP_WS_INTS) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-    } else {
-        if (hipMemsetAsync(terms, 0, 5 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(dep_ws, 0, NGP_DEP_WS_INTS * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
-    }
+    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8
+    if (tail_clear(terms, 5, 6, vr_samples, dep_ws, 8, NGP_DEP_WS_INTS, st) != NGP_OK) return NGP_ELAUNCH;
     // every seed needs the batch's scale and shift, which need every ray's depth: fitted on the same stream ahead of the tail
     hipLaunchKernelGGL(depth_fit_kernel, seg_grid(n_rays), dim3(256), 0, st, sigmas, deltas, ts, rays_a, depth_gt, n_rays,
                        T_threshold, dep_ws);
-    RenderLossArgs a;
-    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
-    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
-    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
-    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
-    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
-    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
-    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
-    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
-    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
-    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale;
-    a.slot_nm = a.slot_dm = 4;
-    hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, true>), seg_grid(n_rays), dim3(256), 0, st, a);
-    return ngp_check_launch();
+    return tail_launch(false, NGP_TERM_DEP, classes, n_rays, st, a);
 }
 
 // The multi workspace, NGP_MULTI_WS_INTS = 30 int32, 8-byte aligned: the three single workspaces back to back
@@ -1609,62 +1609,29 @@ int ngp_render_loss_fused_multi(const float* sigmas, const float* rgbs, const fl
     if (term_mask < 0 || (term_mask & ~(NGP_TERM_SEM | NGP_TERM_NRM | NGP_TERM_DEP)) || (term_mask == 0 && n_rays != 0))
         return NGP_EINVAL;
     const bool SEM = term_mask & NGP_TERM_SEM, NRM = term_mask & NGP_TERM_NRM, DEP = term_mask & NGP_TERM_DEP;
-    if (n_rays < 0 || classes < (SEM ? 1 : 0) || classes > (SEM ? 16 : 8) || ld_normal < 3 || ld_sem < classes ||
-        (DEP && !(scene_scale > 0.0f))) return NGP_EINVAL;
-    if (n_rays == 0) return NGP_OK;
-    if (!rays_a || !target_rgb || !total_samples || !vr_samples || !opacity || !depth || !rgb || !normal_pred ||
-        (classes && !sem) || !loss_o || !loss_p || !terms || !dL_dsigmas || !dL_drgbs || !ws || !multi_ws ||
-        (reinterpret_cast<uintptr_t>(multi_ws) & 7)) return NGP_EINVAL;
-    if (SEM && (!labels || !sem_logits || !dL_dsem_logits)) return NGP_EINVAL;
-    if (NRM && (!normals_gt || !normal_head || !dL_dnormal_head)) return NGP_EINVAL;
-    if (DEP && !depth_gt) return NGP_EINVAL;
+    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
+                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
+                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
+                                 dL_dsigmas, dL_drgbs);
+    const int rc = tail_check(a, SEM ? 1 : 0, SEM ? 16 : 8, !DEP || scene_scale > 0.0f,
+                              tail_trained_ok(a, multi_ws) && (!SEM || (labels && sem_logits && dL_dsem_logits)) &&
+                                  (!NRM || (normals_gt && normal_head && dL_dnormal_head)) && (!DEP || depth_gt));
+    if (rc != TAIL_GO) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // terms (8) with vr_samples behind them at float 8 and the workspace at float 10: one fill
-    char* base = reinterpret_cast<char*>(terms);
-    if (reinterpret_cast<char*>(vr_samples) == base + 8 * sizeof(float) &&
-        reinterpret_cast<char*>(multi_ws) == base + 10 * sizeof(float)) {
-        if (hipMemsetAsync(terms, 0, (10 + NGP_MULTI_WS_INTS) * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-    } else {
-        if (hipMemsetAsync(terms, 0, 8 * sizeof(float), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(vr_samples, 0, sizeof(int64_t), st) != hipSuccess) return NGP_ELAUNCH;
-        if (hipMemsetAsync(multi_ws, 0, NGP_MULTI_WS_INTS * sizeof(int), st) != hipSuccess) return NGP_ELAUNCH;
-    }
+    // terms (8) with vr_samples behind them at float 8 and the workspace at float 10
+    if (tail_clear(terms, 8, 8, vr_samples, multi_ws, 10, NGP_MULTI_WS_INTS, st) != NGP_OK) return NGP_ELAUNCH;
     int *sem_ws = multi_ws + MULTI_WS_SEM, *nrm_ws = multi_ws + MULTI_WS_NRM, *dep_ws = multi_ws + MULTI_WS_DEP;
     // what every seed needs of the whole batch, on the same stream ahead of the tail: the count of valid labels, the fit
     if (SEM) hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, rays_a, n_rays, classes, sem_ws);
     if (DEP)
         hipLaunchKernelGGL(depth_fit_kernel, seg_grid(n_rays), dim3(256), 0, st, sigmas, deltas, ts, rays_a, depth_gt, n_rays,
                            T_threshold, dep_ws);
-    RenderLossArgs a;
-    a.sigmas = sigmas; a.rgbs = rgbs; a.dsig_dx = dsigma_dx; a.np_raw = normal_head; a.sem_logits = sem_logits;
-    a.dirs = dirs; a.deltas = deltas; a.ts = ts; a.gt = target_rgb; a.scale3 = scale3; a.rays_a = rays_a; a.bg = rgb_bg;
-    a.ld_np = ld_normal; a.ld_sem = ld_sem; a.T_thr = T_threshold;
-    a.g_rgb = 1.0f / (3.0f * n_rays); a.g_op = lambda_opacity / n_rays; a.g_dist = lambda_distortion / n_rays;
-    a.classes = classes; a.n_rays = n_rays; a.total_samples = total_samples; a.vr_samples = vr_samples;
-    a.opacity = opacity; a.depth = depth; a.rgb = rgb; a.normal = normal_pred; a.sem = sem; a.ws = ws;
-    a.Ro = loss_o; a.Rp = loss_p; a.terms = terms; a.d_sigmas = dL_dsigmas; a.d_rgbs = dL_drgbs;
-    a.mask = nullptr; a.g_ms = 0.0f; a.d_mask = nullptr;
-    a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
-    a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
-    a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
     a.slot_nm = 6; a.slot_dm = 7;
     if (SEM) { a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits; }
     if (NRM) { a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head; }
     if (DEP) { a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale; }
-    const dim3 grid = seg_grid(n_rays), block(256);
-#define NGP_TAIL(CM, S, N, D) hipLaunchKernelGGL((render_loss_fused_kernel<CM, 32, false, S, N, D>), grid, block, 0, st, a)
-    const bool wide = classes > 8;   // (only with SEM: checked above)
-    switch (term_mask) {
-    case NGP_TERM_SEM: if (wide) NGP_TAIL(16, true, false, false); else NGP_TAIL(8, true, false, false); break;
-    case NGP_TERM_NRM: NGP_TAIL(8, false, true, false); break;
-    case NGP_TERM_DEP: NGP_TAIL(8, false, false, true); break;
-    case NGP_TERM_SEM | NGP_TERM_NRM: if (wide) NGP_TAIL(16, true, true, false); else NGP_TAIL(8, true, true, false); break;
-    case NGP_TERM_SEM | NGP_TERM_DEP: if (wide) NGP_TAIL(16, true, false, true); else NGP_TAIL(8, true, false, true); break;
-    case NGP_TERM_NRM | NGP_TERM_DEP: NGP_TAIL(8, false, true, true); break;
-    default: if (wide) NGP_TAIL(16, true, true, true); else NGP_TAIL(8, true, true, true); break;
-    }
-#undef NGP_TAIL
-    return ngp_check_launch();
+    // (one bit alone launches that term's own instantiation)
+    return tail_launch(false, term_mask, classes, n_rays, st, a);
 }
 
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,

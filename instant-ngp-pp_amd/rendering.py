@@ -9,6 +9,8 @@ kwargs read: test_time, to_cpu, to_numpy, exp_step_factor, embedding_a, num_clas
              T_threshold, use_skybox, random_bg (+ passed through to the model).
 embedding_a: a (n_rays, E) tensor (expanded per sample here) or, at training time, appearance.RayCodes(table, img_idxs).
 """
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn.functional as F
 
@@ -354,229 +356,103 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
 
 def _fused_tail_ok(model, kwargs, exp_step_factor, classes, fused=None):
     """the one-launch render + loss tail covers the default recipe: sigmoid colours (no tone mapper), black or random
-    constant background (no skybox network), detached analytic normals, at most 8 classes (the semantic form of the
-    tail, fused[3] == 'sem', or fused[3] == 'multi' with the semantic term named: 1 to 16)"""
-    sem = fused is not None and len(fused) > 3 and isinstance(fused[3], str) and (
-        fused[3] == 'sem' or (fused[3] == 'multi' and 'semantic' in fused[4]))
+    constant background (no skybox network), detached analytic normals, at most 8 classes (1 to 16 when `fused`, a
+    FusedTail, names the semantic term)"""
+    sem = fused is not None and 'semantic' in fused.terms
     return (getattr(model, 'rgb_act', 'Sigmoid') == 'Sigmoid' and not kwargs.get('use_skybox', False)
             and not getattr(model, 'differentiable_normals', False) and (1 <= classes <= 16 if sem else classes <= 8)
             and hasattr(model, '_field'))
-
-
-class _RenderLossFn(torch.autograd.Function):
-    """Default-recipe tail of a training step as ONE launch (ngp_render_loss_fused): normals, softmax, compositing,
-    Ref-NeRF regularisers, distortion loss, NeRFLoss's default terms AND their gradients w.r.t. the field's outputs.
-    forward returns (terms (4) = [loss, rgb, opacity, distortion], per-ray results ..., ws); only terms is
-    differentiable, and only through terms[0] with a unit seed (NGPTrainer's use): backward hands the gradients
-    computed in forward to the field."""
-
-    @staticmethod
-    def forward(ctx, sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, scale3, T_thr, classes,
-                lambda_opa, lambda_dist, rgb_bg=None):
-        n, nr = sig.shape[0], rays_a.shape[0]
-        dev = sig.device
-        f32 = torch.float32
-        total = torch.empty(nr, dtype=torch.int64, device=dev)
-        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)   # (the caching allocator launches nothing)
-        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
-        ws, d_sig, d_rgb = E(n), E(n), E(n, 3)
-        acc = E(8)                                   # [terms (4) | vr_samples (int64) | -]: adjacent, cleared by one memset
-        terms, vr = acc[:4], acc[4:6].view(torch.int64)
-        call("render_loss_fused", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
-             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, float(T_thr), int(classes), nr, float(lambda_opa), float(lambda_dist),
-             total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, terms, d_sig, d_rgb)
-        ctx.save_for_backward(d_sig, d_rgb)
-        ctx.set_materialize_grads(False)             # no zero-filled gradient tensors for the ten other outputs
-        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
-        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
-
-    @staticmethod
-    def backward(ctx, g_terms, *_unused):
-        d_sig, d_rgb = ctx.saved_tensors
-        return (d_sig, d_rgb) + (None,) * 14
-
-
-class _RenderLossMaskedFn(torch.autograd.Function):
-    """_RenderLossFn for NeRFLoss(embed_msk=True) (ngp_render_loss_fused_masked): `mask` (n_rays) or (n_rays, 1) is a
-    further differentiable input — its gradient is computed by the same launch and handed back by backward — and
-    terms (5) = [loss, rgb, opacity, distortion, r_ms]."""
-
-    @staticmethod
-    def forward(ctx, sig, rgb_o, mask, dsig_dx, np_raw, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, scale3, T_thr, classes,
-                lambda_opa, lambda_dist, size_delta, rgb_bg=None):
-        n, nr = sig.shape[0], rays_a.shape[0]
-        dev = sig.device
-        f32 = torch.float32
-        if mask.numel() != nr:
-            raise ValueError(f"mask has {mask.numel()} entries for {nr} rays")
-        total = torch.empty(nr, dtype=torch.int64, device=dev)
-        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
-        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
-        ws, d_sig, d_rgb, d_mask = E(n), E(n), E(n, 3), E(nr)
-        acc = E(8)                                   # [terms (5) | - | vr_samples (int64)]: cleared by one memset
-        terms, vr = acc[:5], acc[6:8].view(torch.int64)
-        call("render_loss_fused_masked", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits,
-             sem_logits.stride(0), dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, mask.contiguous(), float(size_delta), float(T_thr),
-             int(classes), nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp,
-             terms, d_sig, d_rgb, d_mask)
-        ctx.save_for_backward(d_sig, d_rgb, d_mask)
-        ctx.mask_shape = mask.shape
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
-        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
-
-    @staticmethod
-    def backward(ctx, g_terms, *_unused):
-        d_sig, d_rgb, d_mask = ctx.saved_tensors
-        return (d_sig, d_rgb, d_mask.view(ctx.mask_shape)) + (None,) * 15
-
-
-class _RenderLossSemFn(torch.autograd.Function):
-    """_RenderLossFn for NeRFLoss(semantic=True) (ngp_render_loss_fused_sem): `labels` (n_rays) int64, one per ray; a label
-    outside [0, classes) is ignored (256, the reference's ignore_index, and an 8-bit 255 among them).  The class logits
-    are a further differentiable input whose gradient the same launch computes, and terms (6) = [loss, rgb, opacity,
-    distortion, CELoss, sky_depth].  A batch without a valid label has CELoss = 0 and a zero logit gradient, where torch's
-    cross-entropy gives NaN.  Differentiable through terms[0] only."""
-
-    @staticmethod
-    def forward(ctx, sig, rgb_o, sem_logits, dsig_dx, np_raw, dirs, deltas, ts, rays_a, rgb_gt, labels, scale3, T_thr,
-                classes, lambda_opa, lambda_dist, lambda_sem, lambda_sky, rgb_bg=None):
-        n, nr = sig.shape[0], rays_a.shape[0]
-        dev = sig.device
-        f32 = torch.float32
-        if labels.numel() != nr or labels.dtype != torch.int64:
-            raise ValueError(f"labels must be {nr} int64 entries, one per ray: got {tuple(labels.shape)} {labels.dtype}")
-        if not 1 <= classes <= 16 or sem_logits.shape[1] < classes:
-            raise ValueError(f"the semantic tail takes 1 to 16 classes: got {classes} for logits {tuple(sem_logits.shape)}")
-        total = torch.empty(nr, dtype=torch.int64, device=dev)
-        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
-        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
-        ws, d_sig, d_rgb, d_sem = E(n), E(n), E(n, 3), E(n, classes)
-        acc = E(8)                                   # [terms (6) | vr_samples (int64)]: adjacent, cleared by one memset
-        terms, vr = acc[:6], acc[6:8].view(torch.int64)
-        n_valid = torch.empty(8, dtype=torch.int32, device=dev)    # NGP_SEM_WS_INTS: [n_valid | - | two double sums | count | -]
-        call("render_loss_fused_sem", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
-             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, labels.contiguous().view(-1), float(lambda_sem), float(lambda_sky),
-             float(T_thr), int(classes), nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal,
-             sem, ws, Ro, Rp, terms, d_sig, d_rgb, n_valid, d_sem)
-        ctx.save_for_backward(d_sig, d_rgb, d_sem)
-        ctx.pad = sem_logits.shape[1] - classes
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
-        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
-
-    @staticmethod
-    def backward(ctx, g_terms, *_unused):
-        d_sig, d_rgb, d_sem = ctx.saved_tensors
-        if ctx.pad:
-            d_sem = F.pad(d_sem, (0, ctx.pad))
-        return (d_sig, d_rgb, d_sem) + (None,) * 16
-
-
-class _RenderLossNrmFn(torch.autograd.Function):
-    """_RenderLossFn for NeRFLoss's normal_mono term (ngp_render_loss_fused_nrm): `normals_gt` (n_rays, 3) float32, one
-    target normal per ray; a row of three exact zeros marks a ray without a normal, which takes no part in the term (the
-    divisor stays 3 n_rays).  The normal head's raw output is a further differentiable input whose gradient the same
-    launch computes, and terms (5) = [loss, rgb, opacity, distortion, normal_mono].  Differentiable through terms[0]
-    only."""
-
-    @staticmethod
-    def forward(ctx, sig, rgb_o, np_raw, dsig_dx, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, normals_gt, scale3, T_thr,
-                classes, lambda_opa, lambda_dist, lambda_nm, rgb_bg=None):
-        n, nr = sig.shape[0], rays_a.shape[0]
-        dev = sig.device
-        f32 = torch.float32
-        if tuple(normals_gt.shape) != (nr, 3) or normals_gt.dtype != f32:
-            raise ValueError(f"normals must be ({nr}, 3) float32, one row per ray: got {tuple(normals_gt.shape)} "
-                             f"{normals_gt.dtype}")
-        total = torch.empty(nr, dtype=torch.int64, device=dev)
-        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
-        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
-        ws, d_sig, d_rgb, d_np = E(n), E(n), E(n, 3), E(n, 3)
-        acc = E(12)               # [terms (5) | - | vr_samples (int64) | workspace (NGP_NRM_WS_INTS)]: cleared by one memset
-        terms, vr, nrm_ws = acc[:5], acc[6:8].view(torch.int64), acc[8:12].view(torch.int32)
-        call("render_loss_fused_nrm", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
-             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, normals_gt.contiguous(), float(lambda_nm), float(T_thr), int(classes),
-             nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, terms,
-             d_sig, d_rgb, nrm_ws, d_np)
-        ctx.save_for_backward(d_sig, d_rgb, d_np)
-        ctx.pad = np_raw.shape[1] - 3
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp)
-        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp
-
-    @staticmethod
-    def backward(ctx, g_terms, *_unused):
-        d_sig, d_rgb, d_np = ctx.saved_tensors
-        if ctx.pad:
-            d_np = F.pad(d_np, (0, ctx.pad))
-        return (d_sig, d_rgb, d_np) + (None,) * 15
-
-
-class _RenderLossDepFn(torch.autograd.Function):
-    """_RenderLossFn for NeRFLoss's depth_mono term (ngp_render_loss_fused_dep): `depth_gt` (n_rays) float32, the raw
-    monocular depth of every ray (z = depth_gt / 25; zero, negative and NaN mark a ray without depth, which takes no part in
-    the fit, the term or any gradient).  A fit kernel ahead of the tail leaves the batch's least-squares scale and shift of
-    the composited depths in the workspace (a singular system: (0, 0)); the term reaches the field through d_sigmas alone, so
-    there is no further differentiable input, and terms (5) = [loss, rgb, opacity, distortion, depth_mono].  The workspace
-    (scale, shift, n_valid at int 12, 13, 14) is returned last.  Differentiable through terms[0] only."""
-
-    @staticmethod
-    def forward(ctx, sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs, deltas, ts, rays_a, rgb_gt, depth_gt, scale3, T_thr,
-                classes, lambda_opa, lambda_dist, lambda_dm, scene_scale, rgb_bg=None):
-        n, nr = sig.shape[0], rays_a.shape[0]
-        dev = sig.device
-        f32 = torch.float32
-        if tuple(depth_gt.shape) != (nr,) or depth_gt.dtype != f32:
-            raise ValueError(f"depths must be ({nr},) float32, one per ray: got {tuple(depth_gt.shape)} {depth_gt.dtype}")
-        total = torch.empty(nr, dtype=torch.int64, device=dev)
-        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
-        opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
-        ws, d_sig, d_rgb = E(n), E(n), E(n, 3)
-        acc = E(26)               # [terms (5) | - | vr_samples (int64) | workspace (NGP_DEP_WS_INTS)]: cleared by one memset
-        terms, vr, dep_ws = acc[:5], acc[6:8].view(torch.int64), acc[8:26].view(torch.int32)
-        call("render_loss_fused_dep", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
-             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, depth_gt.contiguous(), float(lambda_dm), float(scene_scale), float(T_thr),
-             int(classes), nr, float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp,
-             terms, d_sig, d_rgb, dep_ws)
-        ctx.save_for_backward(d_sig, d_rgb)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, dep_ws)
-        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, dep_ws
-
-    @staticmethod
-    def backward(ctx, g_terms, *_unused):
-        d_sig, d_rgb = ctx.saved_tensors
-        return (d_sig, d_rgb) + (None,) * 17
 
 
 MULTI_TERMS = ('semantic', 'normal_mono', 'depth_mono')   # bit i of ngp_render_loss_fused_multi's term_mask
 MULTI_WS_INTS = 30                                        # NGP_MULTI_WS_INTS
 
 
-class _RenderLossMultiFn(torch.autograd.Function):
-    """_RenderLossFn for two or three of NeRFLoss's semantic, normal_mono and depth_mono terms in one tail
-    (ngp_render_loss_fused_multi; one term alone takes that term's own kernel).  `named` maps a term's name to its target
-    and weights: 'semantic' -> (labels (n_rays) int64, lambda_sem, lambda_sky), 'normal_mono' -> (normals_gt (n_rays, 3)
-    float32, lambda_nm), 'depth_mono' -> (depth_gt (n_rays) float32, lambda_dm, scene_scale); each term is that of its
-    single Function above.  The class logits and the normal head's raw output get a gradient only when their term is
-    named.  terms (8) = [loss, rgb, opacity, distortion, CELoss, sky_depth, normal_mono, depth_mono], a term that is not
-    named exactly 0.  The workspace (NGP_MULTI_WS_INTS: the labels' n_valid at int 0, the fit's scale, shift and n_valid at
-    int 24, 25, 26) is returned last.  Differentiable through terms[0] only."""
+class TailLayout(NamedTuple):
+    """one float32 accumulator per launch, [terms (n_terms) | - | vr_samples (int64) at float vr_at | workspace (ws_ints
+    int32) at float ws_at], laid out so that the entry clears it with one memset.  ws_at None: no workspace inside the
+    accumulator (the semantic entry's is an allocation of its own, which its label count clears)."""
+    n_terms: int
+    acc: int
+    vr_at: int
+    ws_at: Optional[int]
+    ws_ints: int
+
+
+# entry ngp_render_loss_fused[_<key>] -> its layout (ws_ints: NGP_SEM_WS_INTS, NGP_NRM_WS_INTS, NGP_DEP_WS_INTS, NGP_MULTI_WS_INTS)
+TAIL_LAYOUT = {
+    'default': TailLayout(4, 6, 4, None, 0),
+    'masked': TailLayout(5, 8, 6, None, 0),
+    'sem': TailLayout(6, 8, 6, None, 8),
+    'nrm': TailLayout(5, 12, 6, 8, 4),
+    'dep': TailLayout(5, 26, 6, 8, 18),
+    'multi': TailLayout(8, 10 + MULTI_WS_INTS, 8, 10, MULTI_WS_INTS),
+}
+_PACKED_ENTRY = dict(zip(MULTI_TERMS, ('sem', 'nrm', 'dep')))
+
+
+class FusedTail:
+    """what render(..., _fused_loss=) takes: the colour target and NeRFLoss's default weights, and at most one of
+    mask (n_rays[, 1]) with size_delta: the embed_msk recipe (ngp_render_loss_fused_masked);
+    terms: {'semantic': (labels (n_rays) int64, lambda_sem, lambda_sky), 'normal_mono': (normals_gt (n_rays, 3) float32,
+        lambda_nm), 'depth_mono': (depth_gt (n_rays) float32, lambda_dm, scene_scale)}, a non-empty subset.  packed=True
+        takes exactly one term and selects that term's own entry with its packed terms (ngp_render_loss_fused_sem / _nrm /
+        _dep); packed=False selects ngp_render_loss_fused_multi and its 8 terms.
+    `entry` is the key of TAIL_LAYOUT the combination selects."""
+    __slots__ = ('rgb_gt', 'lambda_opa', 'lambda_dist', 'mask', 'size_delta', 'terms', 'packed', 'entry')
+
+    def __init__(self, rgb_gt, lambda_opa, lambda_dist, mask=None, size_delta=0.0, terms=None, packed=False):
+        if terms is not None and (not terms or any(k not in MULTI_TERMS for k in terms)):
+            raise ValueError(f"the multi tail takes a non-empty subset of {MULTI_TERMS}: got {tuple(terms)}")
+        if mask is not None and terms is not None:
+            raise ValueError("the fused tail takes a mask or optional terms, not both")
+        if packed and (terms is None or len(terms) != 1):
+            raise ValueError(f"packed=True selects one term's own entry: got {tuple(terms or ())}")
+        self.rgb_gt, self.lambda_opa, self.lambda_dist = rgb_gt, lambda_opa, lambda_dist
+        self.mask, self.size_delta, self.terms, self.packed = mask, size_delta, dict(terms or {}), bool(packed)
+        if terms is None:
+            self.entry = 'default' if mask is None else 'masked'
+        else:
+            self.entry = _PACKED_ENTRY[next(iter(terms))] if packed else 'multi'
+
+
+class _RenderLossFn(torch.autograd.Function):
+    """The tail of a training step as ONE launch (ngp_render_loss_fused and its five siblings, chosen by `tail`, a
+    FusedTail): normals, softmax, compositing, Ref-NeRF regularisers, distortion loss, NeRFLoss's default terms, the terms
+    `tail` adds, AND their gradients w.r.t. the field's outputs.
+    mask: (n_rays) or (n_rays, 1), the transient mask of the embed_msk recipe (None without one): terms (5) = [loss, rgb,
+        opacity, distortion, r_ms], and the mask gets the gradient the same launch computes.
+    'semantic': a label outside [0, classes) is ignored (256, the reference's ignore_index, and an 8-bit 255 among them); a
+        batch without a valid label has CELoss = 0 and a zero logit gradient, where torch's cross-entropy gives NaN.
+    'normal_mono': a row of three exact zeros marks a ray without a normal, which takes no part in the term (the divisor
+        stays 3 n_rays).
+    'depth_mono': the raw monocular depth (z = depth_gt / 25; zero, negative and NaN mark a ray without depth, which takes
+        no part in the fit, the term or any gradient).  A fit kernel ahead of the tail leaves the batch's least-squares
+        scale and shift of the composited depths in the workspace (a singular system: (0, 0)); the term reaches the field
+        through d_sigmas alone.
+    terms: (4) = [loss, rgb, opacity, distortion]; packed, one of [CELoss, sky_depth], [normal_mono], [depth_mono] behind
+        them; the multi entry's (8) = [loss, rgb, opacity, distortion, CELoss, sky_depth, normal_mono, depth_mono], a term
+        that is not named exactly 0.  The class logits and the normal head's raw output get a gradient only when their
+        term is named.
+    forward returns (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, workspace): the workspace as int32
+    (the labels' n_valid at int 0; the fit's scale, shift and n_valid at int 12, 13, 14 of the depth entry's and at int
+    24, 25, 26 of the multi entry's), None where the entry has none.  Only terms is differentiable, and only through
+    terms[0] with a unit seed (NGPTrainer's use): backward hands the gradients computed in forward to the field."""
 
     @staticmethod
-    def forward(ctx, sig, rgb_o, sem_logits, np_raw, dsig_dx, dirs, deltas, ts, rays_a, rgb_gt, named, scale3, T_thr,
-                classes, lambda_opa, lambda_dist, rgb_bg=None):
+    def forward(ctx, sig, rgb_o, sem_logits, np_raw, mask, dsig_dx, dirs, deltas, ts, rays_a, tail, scale3, T_thr, classes,
+                rgb_bg=None):
         n, nr = sig.shape[0], rays_a.shape[0]
         dev = sig.device
         f32 = torch.float32
-        unknown = [k for k in named if k not in MULTI_TERMS]
-        if unknown or not named:
-            raise ValueError(f"the multi tail takes a non-empty subset of {MULTI_TERMS}: got {tuple(named)}")
-        mask = sum(1 << i for i, k in enumerate(MULTI_TERMS) if k in named)
-        labels = normals_gt = depth_gt = None
+        named = tail.terms
+        labels = normals_gt = depth_gt = mask_c = None
         lambda_sem = lambda_sky = lambda_nm = lambda_dm = 0.0
         scene_scale = 1.0
+        if mask is not None:
+            if mask.numel() != nr:
+                raise ValueError(f"mask has {mask.numel()} entries for {nr} rays")
+            mask_c = mask.contiguous()
         if 'semantic' in named:
             labels, lambda_sem, lambda_sky = named['semantic']
             if labels.numel() != nr or labels.dtype != torch.int64:
@@ -596,78 +472,63 @@ class _RenderLossMultiFn(torch.autograd.Function):
                 raise ValueError(f"depths must be ({nr},) float32, one per ray: got {tuple(depth_gt.shape)} {depth_gt.dtype}")
             depth_gt = depth_gt.contiguous()
         total = torch.empty(nr, dtype=torch.int64, device=dev)
-        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        E = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)   # (the caching allocator launches nothing)
         opacity, depth, rgb, normal, Ro, Rp, sem = E(nr), E(nr), E(nr, 3), E(nr, 3), E(nr), E(nr, 3), E(nr, classes)
         ws, d_sig, d_rgb = E(n), E(n), E(n, 3)
         d_sem = E(n, classes) if labels is not None else None
         d_np = E(n, 3) if normals_gt is not None else None
-        acc = E(10 + MULTI_WS_INTS)   # [terms (8) | vr_samples (int64) | workspace (NGP_MULTI_WS_INTS)]: cleared by one memset
-        terms, vr, multi_ws = acc[:8], acc[8:10].view(torch.int64), acc[10:].view(torch.int32)
-        call("render_loss_fused_multi", sig, rgb_o, dsig_dx, scale3, np_raw, np_raw.stride(0), sem_logits, sem_logits.stride(0),
-             dirs, deltas, ts, rays_a, rgb_gt, rgb_bg, mask, labels, float(lambda_sem), float(lambda_sky), normals_gt,
-             float(lambda_nm), depth_gt, float(lambda_dm), float(scene_scale), float(T_thr), int(classes), nr,
-             float(lambda_opa), float(lambda_dist), total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, terms, d_sig,
-             d_rgb, multi_ws, d_sem, d_np)
-        ctx.have_sem, ctx.have_np = d_sem is not None, d_np is not None
-        ctx.save_for_backward(*[t for t in (d_sig, d_rgb, d_sem, d_np) if t is not None])
+        d_mask = E(nr) if mask is not None else None
+        lay = TAIL_LAYOUT[tail.entry]
+        acc = E(lay.acc)
+        terms, vr = acc[:lay.n_terms], acc[lay.vr_at:lay.vr_at + 2].view(torch.int64)
+        if lay.ws_at is not None:
+            wsp = acc[lay.ws_at:].view(torch.int32)
+        else:
+            wsp = torch.empty(lay.ws_ints, dtype=torch.int32, device=dev) if lay.ws_ints else None
+        # what each entry takes behind rgb_bg, and behind dL_drgbs
+        sem_a, nrm_a = (labels, float(lambda_sem), float(lambda_sky)), (normals_gt, float(lambda_nm))
+        dep_a = (depth_gt, float(lambda_dm), float(scene_scale))
+        bits = sum(1 << i for i, k in enumerate(MULTI_TERMS) if k in named)
+        own_in, own_out = {
+            'default': ((), ()),
+            'masked': ((mask_c, float(tail.size_delta)), (d_mask,)),
+            'sem': (sem_a, (wsp, d_sem)),
+            'nrm': (nrm_a, (wsp, d_np)),
+            'dep': (dep_a, (wsp,)),
+            'multi': ((bits,) + sem_a + nrm_a + dep_a, (wsp, d_sem, d_np)),
+        }[tail.entry]
+        call("render_loss_fused" + ("" if tail.entry == 'default' else "_" + tail.entry), sig, rgb_o, dsig_dx, scale3, np_raw,
+             np_raw.stride(0), sem_logits, sem_logits.stride(0), dirs, deltas, ts, rays_a, tail.rgb_gt.contiguous(), rgb_bg,
+             *own_in, float(T_thr), int(classes), nr, float(tail.lambda_opa), float(tail.lambda_dist), total, vr, opacity,
+             depth, rgb, normal, sem, ws, Ro, Rp, terms, d_sig, d_rgb, *own_out)
+        ctx.save_for_backward(d_sig, d_rgb, d_sem, d_np, d_mask)
         ctx.pad_sem, ctx.pad_np = sem_logits.shape[1] - classes, np_raw.shape[1] - 3
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, multi_ws)
-        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, multi_ws
+        ctx.mask_shape = mask.shape if mask is not None else None
+        ctx.set_materialize_grads(False)             # no zero-filled gradient tensors for the other outputs
+        ctx.mark_non_differentiable(*[t for t in (total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, wsp) if t is not None])
+        return terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, wsp
 
     @staticmethod
     def backward(ctx, g_terms, *_unused):
-        saved = list(ctx.saved_tensors)
-        d_sig, d_rgb = saved[0], saved[1]
-        d_sem = d_np = None
-        if ctx.have_sem:
-            d_sem = saved[2]
-            if ctx.pad_sem:
-                d_sem = F.pad(d_sem, (0, ctx.pad_sem))
-        if ctx.have_np:
-            d_np = saved[-1]
-            if ctx.pad_np:
-                d_np = F.pad(d_np, (0, ctx.pad_np))
-        return (d_sig, d_rgb, d_sem, d_np) + (None,) * 13
+        d_sig, d_rgb, d_sem, d_np, d_mask = ctx.saved_tensors
+        if d_sem is not None and ctx.pad_sem:
+            d_sem = F.pad(d_sem, (0, ctx.pad_sem))
+        if d_np is not None and ctx.pad_np:
+            d_np = F.pad(d_np, (0, ctx.pad_np))
+        if d_mask is not None:
+            d_mask = d_mask.view(ctx.mask_shape)
+        return (d_sig, d_rgb, d_sem, d_np, d_mask) + (None,) * 10
 
 
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
-    """fused = (rgb_gt, lambda_opa, lambda_distortion) or, for the embed_msk recipe, those three followed by
-    (mask (n_rays[, 1]), size_delta), or, for the semantic recipe, by ('sem', labels (n_rays) int64, lambda_sem,
-    lambda_sky), or, for the normal_mono recipe, by ('nrm', normals_gt (n_rays, 3), lambda_nm), or, for the depth_mono
-    recipe, by ('dep', depth_gt (n_rays), lambda_dm, scene_scale), or, for several of those three terms at once, by
-    ('multi', {term: (target, weights...)}) as _RenderLossMultiFn documents"""
+    """fused: the FusedTail of render(..., _fused_loss=)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
-    rgb_gt, lambda_opa, lambda_dist = fused[:3]
     rgb_bg = None
     if kwargs.get('exp_step_factor', 0.) != 0 and kwargs.get('random_bg', False):
         rgb_bg = torch.rand(3, device=xyzs.device)      # rendering.py:239 (drawn at the same place in the RNG stream)
-    if len(fused) == 5 and isinstance(fused[3], str) and fused[3] == 'multi':
-        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, _) = _RenderLossMultiFn.apply(
-            sig, rgb_o, sem_logits, np_raw, dsig_dx, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, rgb_bg)
-    elif len(fused) == 7 and fused[3] == 'sem':
-        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossSemFn.apply(
-            sig, rgb_o, sem_logits, dsig_dx, np_raw, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5],
-            fused[6], rgb_bg)
-    elif len(fused) == 6 and isinstance(fused[3], str) and fused[3] == 'nrm':
-        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossNrmFn.apply(
-            sig, rgb_o, np_raw, dsig_dx, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5], rgb_bg)
-    elif len(fused) == 7 and isinstance(fused[3], str) and fused[3] == 'dep':
-        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, _) = _RenderLossDepFn.apply(
-            sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-            rgb_gt.contiguous(), fused[4], model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[5],
-            fused[6], rgb_bg)
-    elif len(fused) == 5:
-        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossMaskedFn.apply(
-            sig, rgb_o, fused[3], dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-            rgb_gt.contiguous(), model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, fused[4], rgb_bg)
-    else:
-        (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp) = _RenderLossFn.apply(
-            sig, rgb_o, dsig_dx, np_raw, sem_logits, dirs.contiguous(), results['deltas'], results['ts'], rays_a,
-            rgb_gt.contiguous(), model._inv_span(), T_threshold, classes, lambda_opa, lambda_dist, rgb_bg)
+    (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, _) = _RenderLossFn.apply(
+        sig, rgb_o, sem_logits, np_raw, fused.mask, dsig_dx, dirs.contiguous(), results['deltas'], results['ts'], rays_a, fused,
+        model._inv_span(), T_threshold, classes, rgb_bg)
     results['sigma'] = sig
     results['xyzs'] = xyzs
     results['vr_samples'] = vr[0]

@@ -20,6 +20,7 @@ MI355X-specific structure:
 """
 import math
 import os
+from typing import Callable, NamedTuple, Tuple
 
 import torch
 import torch.distributed as dist
@@ -27,9 +28,53 @@ import torch.distributed as dist
 from ._lib import call
 from .appearance import RayCodes
 from .losses import NeRFLoss, nerf_loss_and_grads
-from .rendering import MAX_SAMPLES, MULTI_TERMS, MarchAhead, _fused_tail_ok, render
+from .rendering import MAX_SAMPLES, MULTI_TERMS, TAIL_LAYOUT, FusedTail, MarchAhead, _fused_tail_ok, render
 
 _f32 = torch.float32
+
+
+class _TailTerm(NamedTuple):
+    """one of NeRFLoss's optional terms on the fused render + loss tail, as NGPTrainer sees it"""
+    arg: str                 # step()'s argument that carries the term's target
+    what: str
+    bad: Callable            # (target, n_rays) -> what the target must do instead, None for a good one
+    entry: Callable          # (trainer, target, device) -> the term's entry of FusedTail.terms
+    classes: Tuple[int, int]   # num_classes the tail takes with this term (of several terms: the larger of either end)
+    exact_norm: bool         # the term's head adds to the colour table's gradient, outside the norm bound
+
+
+_TAIL_TERMS = {
+    "semantic": _TailTerm(
+        "labels", "the class of every ray",
+        lambda x, n: None if x.numel() == n else f"hold {n} entries, one per ray: got {tuple(x.shape)}",
+        lambda tr, x, dev: (x.view(-1).to(torch.int64), tr.loss_fn.lambda_semantic, tr.loss_fn.lambda_sky),
+        (1, 16), True),
+    "normal_mono": _TailTerm(
+        "normals", "the target normal of every ray",
+        lambda x, n: None if x.dim() == 2 and tuple(x.shape) == (n, 3) and x.is_floating_point()
+        else f"be ({n}, 3) float: got {tuple(x.shape)} {x.dtype}",
+        lambda tr, x, dev: (x.to(dev, _f32).contiguous(), tr.loss_fn.lambda_normal_mono),
+        (0, 8), True),
+    "depth_mono": _TailTerm(
+        "depths", "the monocular depth of every ray",
+        lambda x, n: None if tuple(x.shape) == (n,) and x.is_floating_point()
+        else f"be ({n},) float: got {tuple(x.shape)} {x.dtype}",
+        lambda tr, x, dev: (x.to(dev, _f32).contiguous(), tr.loss_fn.lambda_depth_mono, float(tr.model.scale)),
+        (0, 8), False),
+}
+assert tuple(_TAIL_TERMS) == MULTI_TERMS
+
+
+def _tail_terms(trainer):
+    """(the optional terms `trainer` trains on the fused tail, in MULTI_TERMS' order; whether they take one term's own
+    entry; the option that asked for them).  getattr: the stand-ins of the host tests carry only some of the flags"""
+    multi = getattr(trainer, 'multi_terms', ())
+    if multi:
+        return multi, False, f"multi_terms={multi}"
+    for name in MULTI_TERMS:
+        if getattr(trainer, name, False):
+            return (name,), True, f"{name}=True"
+    return (), False, None
 
 
 class GradBuckets:
@@ -244,40 +289,7 @@ class NGPTrainer:
             # gradient for dirs), a skybox (a function of rays_d) and second-order normals would leave it silently incomplete
             raise ValueError("pose refinement runs on the fused render + loss tail: a trainer with a pose_refiner takes no "
                              "optional loss term, no skybox and no differentiable normals")
-        self.semantic = bool(semantic)
-        if self.semantic:
-            why = [w for w, bad in (("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
-                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                                    ("an optional term in loss_kwargs", optional),
-                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
-                                    (f"num_classes = {num_classes} outside 1..16", not 1 <= int(num_classes) <= 16),
-                                    (f"a model with {model.semantic_header.n_output_dims} classes for num_classes = "
-                                     f"{num_classes}", model.semantic_header.n_output_dims != int(num_classes))) if bad]
-            if why:
-                raise ValueError("semantic=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
-        self.normal_mono = bool(normal_mono)
-        if self.normal_mono:
-            why = [w for w, bad in (("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                                    ("semantic=True", self.semantic),
-                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
-                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                                    ("an optional term in loss_kwargs", optional),
-                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
-                                    (f"num_classes = {num_classes} above 8", int(num_classes) > 8)) if bad]
-            if why:
-                raise ValueError("normal_mono=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
-        self.depth_mono = bool(depth_mono)
-        if self.depth_mono:
-            why = [w for w, bad in (("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                                    ("semantic=True", self.semantic), ("normal_mono=True", self.normal_mono),
-                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
-                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                                    ("an optional term in loss_kwargs", optional),
-                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
-                                    (f"num_classes = {num_classes} above 8", int(num_classes) > 8)) if bad]
-            if why:
-                raise ValueError("depth_mono=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
+        self.semantic, self.normal_mono, self.depth_mono = bool(semantic), bool(normal_mono), bool(depth_mono)
         if isinstance(multi_terms, str):
             multi_terms = (multi_terms,)
         multi_terms = tuple(multi_terms or ())
@@ -285,23 +297,26 @@ class NGPTrainer:
         if unknown or len(set(multi_terms)) != len(multi_terms):
             raise ValueError(f"multi_terms is a subset of {MULTI_TERMS} without repeats: got {multi_terms}")
         self.multi_terms = tuple(t for t in MULTI_TERMS if t in multi_terms)
+        # the options that put optional terms on the fused tail: one at a time (the last one speaks, the others are refused)
+        asked = [f"{t}=True" for t in MULTI_TERMS if getattr(self, t)]
         if self.multi_terms:
-            with_sem = "semantic" in self.multi_terms
+            asked.append(f"multi_terms={self.multi_terms}")
+        if asked:
+            named = [t for t in MULTI_TERMS if getattr(self, t) or t in self.multi_terms]
+            lo, hi = (max(_TAIL_TERMS[t].classes[k] for t in named) for k in (0, 1))
             head = getattr(getattr(model, "semantic_header", None), "n_output_dims", None)
-            why = [w for w, bad in (("semantic=True", self.semantic), ("normal_mono=True", self.normal_mono),
-                                    ("depth_mono=True", self.depth_mono),
-                                    ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                                    ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
-                                    ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                                    ("an optional term in loss_kwargs", optional),
-                                    ("differentiable normals", getattr(model, "differentiable_normals", False)),
-                                    (f"num_classes = {num_classes} outside 1..16", with_sem and not 1 <= int(num_classes) <= 16),
-                                    (f"num_classes = {num_classes} above 8", not with_sem and int(num_classes) > 8),
-                                    (f"a model with {head} classes for num_classes = {num_classes}",
-                                     with_sem and head != int(num_classes))) if bad]
+            why = asked[:-1] + [w for w, bad in (
+                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
+                ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                ("an optional term in loss_kwargs", optional),
+                ("differentiable normals", getattr(model, "differentiable_normals", False)),
+                (f"num_classes = {num_classes} " + (f"outside {lo}..{hi}" if lo else f"above {hi}"),
+                 not lo <= int(num_classes) <= hi),
+                (f"a model with {head} classes for num_classes = {num_classes}",
+                 "semantic" in named and head != int(num_classes))) if bad]
             if why:
-                raise ValueError(f"multi_terms={self.multi_terms} runs on the fused render + loss tail, which does not take "
-                                 + ", ".join(why))
+                raise ValueError(f"{asked[-1]} runs on the fused render + loss tail, which does not take " + ", ".join(why))
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -511,62 +526,25 @@ class NGPTrainer:
             raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
         if self.embedding_a is not None and img_idxs is None:
             raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
-        multi = getattr(self, 'multi_terms', ())   # (stand-ins in the host tests carry only the single flags)
-        if multi:
-            for name, arg, given in (("semantic", "labels", labels), ("normal_mono", "normals", normals),
-                                     ("depth_mono", "depths", depths)):
-                if name in multi and given is None:
-                    raise ValueError(f"this trainer was built with multi_terms={multi}: step() needs {arg}=")
-                if name not in multi and given is not None:
-                    raise ValueError(f"{arg}= is for a trainer whose multi_terms name '{name}': this one has {multi}")
-            if "semantic" in multi and labels.numel() != rgb_gt.shape[0]:
-                raise ValueError(f"labels= must hold {rgb_gt.shape[0]} entries, one per ray: got {tuple(labels.shape)}")
-            if "normal_mono" in multi and (normals.dim() != 2 or tuple(normals.shape) != (rgb_gt.shape[0], 3)
-                                           or not normals.is_floating_point()):
-                raise ValueError(f"normals= must be ({rgb_gt.shape[0]}, 3) float: got {tuple(normals.shape)} {normals.dtype}")
-            if "depth_mono" in multi and (tuple(depths.shape) != (rgb_gt.shape[0],) or not depths.is_floating_point()):
-                raise ValueError(f"depths= must be ({rgb_gt.shape[0]},) float: got {tuple(depths.shape)} {depths.dtype}")
+        tail_terms, packed, asked = _tail_terms(self)
+        given = {"labels": labels, "normals": normals, "depths": depths}
+        for name in MULTI_TERMS:
+            t = _TAIL_TERMS[name]
+            if name in tail_terms:
+                if given[t.arg] is None:
+                    raise ValueError(f"this trainer was built with {asked}: step() needs {t.arg}= ({t.what})")
+                why = t.bad(given[t.arg], rgb_gt.shape[0])
+                if why:
+                    raise ValueError(f"{t.arg}= must {why}")
+            elif given[t.arg] is not None:
+                raise ValueError(f"{t.arg}= is for a trainer built with {name}=True or with multi_terms naming '{name}'"
+                                 + (f": this one has {asked}" if asked else ""))
+        if tail_terms:
             if target or loss_kwargs:
-                raise ValueError(f"this trainer was built with multi_terms={multi}: the step stays on the fused render + loss "
-                                 "tail and takes no target= and no per-step loss term")
+                raise ValueError(f"this trainer was built with {asked}: the step stays on the fused render + loss tail and "
+                                 "takes no target= and no per-step loss term")
             if not rays_o.is_cuda:
-                raise RuntimeError("multi_terms needs CUDA tensors: the fused tail has no other route")
-        if self.semantic:
-            if labels is None:
-                raise ValueError("this trainer was built with semantic=True: step() needs labels= (the class of every ray)")
-            if target or loss_kwargs:
-                raise ValueError("this trainer was built with semantic=True: the step stays on the fused render + loss tail "
-                                 "and takes no target= and no per-step loss term")
-            if not rays_o.is_cuda:
-                raise RuntimeError("semantic=True needs CUDA tensors: the fused tail has no other route")
-        elif labels is not None and "semantic" not in multi:
-            raise ValueError("labels= is for a trainer built with semantic=True")
-        if self.normal_mono:
-            if normals is None:
-                raise ValueError("this trainer was built with normal_mono=True: step() needs normals= (the target normal of "
-                                 "every ray)")
-            if normals.dim() != 2 or tuple(normals.shape) != (rgb_gt.shape[0], 3) or not normals.is_floating_point():
-                raise ValueError(f"normals= must be ({rgb_gt.shape[0]}, 3) float: got {tuple(normals.shape)} {normals.dtype}")
-            if target or loss_kwargs:
-                raise ValueError("this trainer was built with normal_mono=True: the step stays on the fused render + loss "
-                                 "tail and takes no target= and no per-step loss term")
-            if not rays_o.is_cuda:
-                raise RuntimeError("normal_mono=True needs CUDA tensors: the fused tail has no other route")
-        elif normals is not None and "normal_mono" not in multi:
-            raise ValueError("normals= is for a trainer built with normal_mono=True")
-        if self.depth_mono:
-            if depths is None:
-                raise ValueError("this trainer was built with depth_mono=True: step() needs depths= (the monocular depth of "
-                                 "every ray)")
-            if tuple(depths.shape) != (rgb_gt.shape[0],) or not depths.is_floating_point():
-                raise ValueError(f"depths= must be ({rgb_gt.shape[0]},) float: got {tuple(depths.shape)} {depths.dtype}")
-            if target or loss_kwargs:
-                raise ValueError("this trainer was built with depth_mono=True: the step stays on the fused render + loss "
-                                 "tail and takes no target= and no per-step loss term")
-            if not rays_o.is_cuda:
-                raise RuntimeError("depth_mono=True needs CUDA tensors: the fused tail has no other route")
-        elif depths is not None and "depth_mono" not in multi:
-            raise ValueError("depths= is for a trainer built with depth_mono=True")
+                raise RuntimeError(f"{asked} needs CUDA tensors: the fused tail has no other route")
         ref = self.pose_refiner
         if ref is not None:
             if rays_o is not None or rays_d is not None or next_rays is not None:
@@ -609,43 +587,17 @@ class NGPTrainer:
             mask = self.msk_model(uvi)
         if default_recipe and rays_o.is_cuda:
             # render + loss + the loss's gradients as one launch behind the field (rendering._RenderLossFn)
-            extra['_fused_loss'] = (rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion)
-            if masked:   # size_delta of the step being taken (losses.py:60-69, 85)
-                extra['_fused_loss'] += (mask, self.loss_fn.Annealing.getWeight(self.global_step))
-            if self.semantic:
-                extra['_fused_loss'] += ('sem', labels.view(-1).to(torch.int64), self.loss_fn.lambda_semantic,
-                                         self.loss_fn.lambda_sky)
-                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
-                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the labels
-                    raise RuntimeError("semantic=True: the model no longer fits the fused semantic tail "
-                                       "(rendering._fused_tail_ok); the labels would be left out of the loss")
-            if self.normal_mono:
-                extra['_fused_loss'] += ('nrm', normals.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_normal_mono)
-                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
-                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the normals
-                    raise RuntimeError("normal_mono=True: the model no longer fits the fused normal tail "
-                                       "(rendering._fused_tail_ok); the normals would be left out of the loss")
-            if self.depth_mono:
-                extra['_fused_loss'] += ('dep', depths.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_depth_mono,
-                                         float(model.scale))
-                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
-                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the depths
-                    raise RuntimeError("depth_mono=True: the model no longer fits the fused depth tail "
-                                       "(rendering._fused_tail_ok); the depths would be left out of the loss")
-            if multi:
-                named = {}
-                if "semantic" in multi:
-                    named["semantic"] = (labels.view(-1).to(torch.int64), self.loss_fn.lambda_semantic, self.loss_fn.lambda_sky)
-                if "normal_mono" in multi:
-                    named["normal_mono"] = (normals.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_normal_mono)
-                if "depth_mono" in multi:
-                    named["depth_mono"] = (depths.to(rays_o.device, _f32).contiguous(), self.loss_fn.lambda_depth_mono,
-                                           float(model.scale))
-                extra['_fused_loss'] += ('multi', named)
-                if not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes, extra['_fused_loss']):
-                    # (rgb_act or differentiable_normals changed after construction, ...): never a step without the targets
-                    raise RuntimeError(f"multi_terms={multi}: the model no longer fits the fused tail "
-                                       "(rendering._fused_tail_ok); the targets would be left out of the loss")
+            extra['_fused_loss'] = FusedTail(
+                rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion, mask=mask,
+                # size_delta of the step being taken (losses.py:60-69, 85)
+                size_delta=self.loss_fn.Annealing.getWeight(self.global_step) if masked else 0.0,
+                terms={n: _TAIL_TERMS[n].entry(self, given[_TAIL_TERMS[n].arg], rays_o.device) for n in tail_terms} or None,
+                packed=packed)
+            if tail_terms and not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes,
+                                                 extra['_fused_loss']):
+                # (rgb_act or differentiable_normals changed after construction, ...): never a step without the targets
+                raise RuntimeError(f"{asked}: the model no longer fits the fused tail (rendering._fused_tail_ok); the targets "
+                                   "would be left out of the loss")
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
@@ -660,31 +612,21 @@ class NGPTrainer:
         # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the
         # start; the depth_mono term only changes d_sigmas, which the density head's backward notes: the bound holds)
         self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
-                                and not self.semantic and not self.normal_mono
-                                and "semantic" not in multi and "normal_mono" not in multi)
+                                and not any(_TAIL_TERMS[n].exact_norm for n in tail_terms))
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
-        if self.semantic and '_loss_terms' not in results:
+        fused = extra.get('_fused_loss')
+        if tail_terms and (fused is None or '_loss_terms' not in results
+                           or results['_loss_terms'].numel() != TAIL_LAYOUT[fused.entry].n_terms):
             # (rgb_act / differentiable_normals changed after construction, a model without _field, ...)
-            raise RuntimeError("semantic=True: render() did not take the fused semantic tail (rendering._fused_tail_ok); the "
-                               "labels would be left out of the loss")
-        if self.normal_mono and ('_loss_terms' not in results or results['_loss_terms'].numel() != 5):
-            raise RuntimeError("normal_mono=True: render() did not take the fused normal tail (rendering._fused_tail_ok); the "
-                               "normals would be left out of the loss")
-        if self.depth_mono and ('_loss_terms' not in results or results['_loss_terms'].numel() != 5):
-            raise RuntimeError("depth_mono=True: render() did not take the fused depth tail (rendering._fused_tail_ok); the "
-                               "depths would be left out of the loss")
-        if multi and ('_loss_terms' not in results or results['_loss_terms'].numel() != 8):
-            raise RuntimeError(f"multi_terms={multi}: render() did not take the fused tail (rendering._fused_tail_ok); the "
-                               "targets would be left out of the loss")
+            raise RuntimeError(f"{asked}: render() did not take the fused tail (rendering._fused_tail_ok); the targets would "
+                               "be left out of the loss")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]
-            if multi:
-                results['loss_terms'] = terms.detach()   # the 8 terms of ngp_render_loss_fused_multi: for a caller's log
-            if self.depth_mono:
-                results['loss_terms'] = terms.detach()   # [loss, rgb, opacity, distortion, depth_mono]: for a caller's log
+            if tail_terms:
+                results['loss_terms'] = terms.detach()   # the entry's terms (rendering._RenderLossFn): for a caller's log
             torch.autograd.backward([terms], [self._unit_seed(terms)])
         elif default_recipe and not masked:
             # same value and gradients as sum(term.mean()) over NeRFLoss's default terms; the

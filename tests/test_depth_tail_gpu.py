@@ -1,6 +1,6 @@
 """The depth_mono form of the fused render + loss tail on the GPU (depth_fit_kernel, then
 render_loss_fused_kernel<8, 32, false, false, false, true>, behind ngp_render_loss_fused_dep) against the float64
-restatement of tests/depth_tail_reference.py, and the routes built on it: rendering._RenderLossDepFn,
+restatement of tests/depth_tail_reference.py, and the routes built on it: rendering._RenderLossFn,
 NGPTrainer(depth_mono=True), tools/train_dataset.py --depth_mono.
 
 Bars.  The outputs this entry shares with ngp_render_loss_fused keep tests/test_fused_tail_gpu.py's bars: opacity, depth,
@@ -71,7 +71,7 @@ def run_dep(ngp, x, depths, T_thr=1e-4, classes=7, lam_o=DR.R.LAMBDA_O, lam_d=DR
     t = {k: T(x[k]) for k in ("sig", "rgbs", "dsig", "nrm", "sem", "dirs", "deltas", "ts", "rays_a", "gt", "bg", "scale3")}
     E = lambda *s: torch.full(s, float("nan"), device=DEV)
     total = torch.full((NR_,), -7, dtype=torch.int64, device=DEV)
-    if adjacent:                # rendering._RenderLossDepFn's layout: one buffer, one memset
+    if adjacent:                # rendering.TAIL_LAYOUT['dep']: one buffer, one memset
         acc = E(8 + WS_INTS)
         terms, vr, ws_ = acc[:5], acc[6:8].view(torch.int64), acc[8:].view(torch.int32)
     else:
@@ -241,7 +241,7 @@ def test_block_edges(ngp, rows):
 
 # ------------------------------------------------------------------------------------------- d. layouts, the workspace
 def test_memset_branches_and_garbage_in_the_workspace(ngp):
-    """terms, vr_samples and the workspace adjacent as rendering._RenderLossDepFn lays them out (one fill) and in separate
+    """terms, vr_samples and the workspace adjacent as rendering._RenderLossFn lays them out (one fill) and in separate
     allocations (three fills), the workspace starting as -5, as all bits set and as a large positive pattern: the entry
     clears it, so the four launches agree bit for bit and with the restatement"""
     x, depths = batch("crafted"), depths_of("crafted")
@@ -356,18 +356,18 @@ def _mono_depths(scene, o, d):
 
 
 def test_wrapper_hands_back_the_direct_call(ngp):
-    """rendering._RenderLossDepFn on the crafted batch: the outputs are those of the direct call, and back-propagating
+    """rendering._RenderLossFn with the packed depth_mono term on the crafted batch: the outputs are those of the direct call, and back-propagating
     terms[0] with a unit seed hands back the launch's d_sigmas and d_rgbs bit for bit"""
-    from ngp_amd.rendering import _RenderLossDepFn
+    from ngp_amd.rendering import FusedTail, _RenderLossFn
     x, depths = batch("crafted"), depths_of("crafted")
     direct = run_dep(ngp, x, depths, use_scale=True, scene_scale=0.5)
     t = {k: T(x[k]) for k in ("sig", "rgbs", "dsig", "nrm", "sem", "dirs", "deltas", "ts", "rays_a", "gt", "bg", "scale3")}
     sig, rgbs = t["sig"].requires_grad_(True), t["rgbs"].requires_grad_(True)
-    args = (t["dsig"], t["nrm"], t["sem"], t["dirs"], t["deltas"], t["ts"], t["rays_a"], t["gt"])
-    outs = _RenderLossDepFn.apply(sig, rgbs, *args, T(depths), t["scale3"], 1e-4, 7, DR.R.LAMBDA_O, DR.R.LAMBDA_D,
-                                  DR.LAMBDA_DM, 0.5, t["bg"])
+    args = (sig, rgbs, t["sem"], t["nrm"], None, t["dsig"], t["dirs"], t["deltas"], t["ts"], t["rays_a"])
+    tail = FusedTail(t["gt"], DR.R.LAMBDA_O, DR.R.LAMBDA_D, terms={"depth_mono": (T(depths), DR.LAMBDA_DM, 0.5)}, packed=True)
+    outs = _RenderLossFn.apply(*args, tail, t["scale3"], 1e-4, 7, t["bg"])
     terms = outs[0]
-    assert terms.shape == (5,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:])
+    assert terms.shape == (5,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:] if o is not None)
     seed = torch.zeros_like(terms)
     seed[0] = 1.0
     torch.autograd.backward([terms], [seed])
@@ -385,16 +385,17 @@ def test_wrapper_hands_back_the_direct_call(ngp):
     assert np.array_equal(N(rgbs.grad)[own], direct["d_rgb"][own])
     for bad in (T(depths)[:5], T(depths).double(), T(depths).reshape(-1, 1)):
         with pytest.raises(ValueError):
-            _RenderLossDepFn.apply(sig, rgbs, *args, bad, t["scale3"], 1e-4, 7, 0.0, 0.0, 0.0, 1.0, None)
+            _RenderLossFn.apply(*args, FusedTail(t["gt"], 0.0, 0.0, terms={"depth_mono": (bad, 0.0, 1.0)}, packed=True),
+                                t["scale3"], 1e-4, 7, None)
 
 
 def test_fused_depth_tail_matches_the_launch_per_operation_route(ngp):
     """scale 8, exponential stepping, random background, 1500 rays of the proxy scene, same marcher noise and background
     draw on both routes.  A: render + NeRFLoss(depth_mono=True, scale=8) + sum of means + autograd; B: render with
-    _fused_loss=(gt, lambda_o, lambda_d, 'dep', depths, lambda_dm, 8) through rendering._RenderLossDepFn.  The bars of the
+    _fused_loss=FusedTail(..., terms={'depth_mono': ...}, packed=True) through rendering._RenderLossFn.  The bars of the
     semantic and normal counterparts: terms rtol 1e-4, parameter gradients within 3e-4 of the largest entry."""
     from ngp_amd.losses import NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     torch.manual_seed(33)
     model = _grid_buffers(ngp.networks.NGP(scale=8.0).to(DEV))
@@ -417,7 +418,8 @@ def test_fused_depth_tail_matches_the_launch_per_operation_route(ngp):
         torch.manual_seed(35)
         kw = dict(exp_step_factor=1 / 256, random_bg=True)
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, lam[0], lam[1], "dep", depths, lam[2], 8.0), **kw)
+            tail = FusedTail(gt, lam[0], lam[1], terms={"depth_mono": (depths, lam[2], 8.0)}, packed=True)
+            res = render(model, o, d, _fused_loss=tail, **kw)
             assert "_loss_terms" in res
             terms = res.pop("_loss_terms")
             assert terms.shape == (5,) and terms.requires_grad

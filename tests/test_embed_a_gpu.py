@@ -174,7 +174,7 @@ def test_field_route_against_the_tensor_route(ngp, fused):
     every gradient within 3e-4 of the tensor route's largest entry (that test's own bar); codes.grad is not zero"""
     from ngp_amd.appearance import RayCodes
     from ngp_amd.losses import nerf_loss_and_grads, NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     model = _playground_model(ngp, 33)
     with torch.no_grad():
@@ -196,7 +196,7 @@ def test_field_route_against_the_tensor_route(ngp, fused):
         emb = codes[img] if route == "tensor" else RayCodes(codes, img)
         kw = dict(exp_step_factor=1 / 256, num_classes=7, random_bg=True, embedding_a=emb)
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, lam_o, lam_d), **kw)
+            res = render(model, o, d, _fused_loss=FusedTail(gt, lam_o, lam_d), **kw)
             terms = res.pop("_loss_terms")
             torch.autograd.backward([terms], [torch.tensor([1.0, 0, 0, 0], device=DEV)])
         else:

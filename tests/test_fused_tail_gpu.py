@@ -275,8 +275,8 @@ def test_block_edges(ngp, rows):
 # ------------------------------------------------------------------------------------------- e. memset branches
 @pytest.mark.parametrize("masked", [False, True])
 def test_memset_branches(ngp, masked):
-    """terms and vr_samples adjacent as rendering._RenderLossFn / _RenderLossMaskedFn lay them out (one fill) and in
-    separate allocations (two fills), both pre-filled with NaN / a large negative count"""
+    """terms and vr_samples adjacent as rendering._RenderLossFn lays them out (one fill) and in separate allocations
+    (two fills), both pre-filled with NaN / a large negative count"""
     x = batch("crafted")
     cfg = dict(classes=7, masked=masked, size_delta=6e-2)
     a = run_tail(ngp, x, adjacent=True, **cfg)
@@ -329,22 +329,21 @@ def test_random_batch(ngp, name):
 # ------------------------------------------------------------------------------------------- h. the autograd wrappers
 @pytest.mark.parametrize("masked", [False, True])
 def test_wrapper_hands_back_the_direct_call(ngp, masked):
-    """rendering._RenderLossFn / _RenderLossMaskedFn on the crafted batch: the outputs are those of the direct call, and
-    back-propagating terms[0] with a unit seed hands back the launch's d_sigmas, d_rgbs (and d_mask) bit for bit"""
-    from ngp_amd.rendering import _RenderLossFn, _RenderLossMaskedFn
+    """rendering._RenderLossFn (with and without a mask in its FusedTail) on the crafted batch: the outputs are those of the
+    direct call, and back-propagating terms[0] with a unit seed hands back the launch's d_sigmas, d_rgbs (and d_mask) bit
+    for bit"""
+    from ngp_amd.rendering import FusedTail, _RenderLossFn
     x = batch("crafted")
     cfg = dict(classes=7, use_scale=True, masked=masked, size_delta=6e-2)
     direct = run_tail(ngp, x, **cfg)
     t = {k: T(x[k]) for k in ("sig", "rgbs", "dsig", "nrm", "sem", "dirs", "deltas", "ts", "rays_a", "gt", "bg", "scale3", "mask")}
     sig, rgbs, mask = t["sig"].requires_grad_(True), t["rgbs"].requires_grad_(True), t["mask"][:, None].requires_grad_(True)
-    common = (t["dsig"], t["nrm"], t["sem"], t["dirs"], t["deltas"], t["ts"], t["rays_a"], t["gt"], t["scale3"], 1e-4, 7,
-              R.LAMBDA_O, R.LAMBDA_D)
-    if masked:
-        outs = _RenderLossMaskedFn.apply(sig, rgbs, mask, *common, 6e-2, t["bg"])
-    else:
-        outs = _RenderLossFn.apply(sig, rgbs, *common, t["bg"])
+    tail = FusedTail(t["gt"], R.LAMBDA_O, R.LAMBDA_D, mask=mask, size_delta=6e-2) if masked else FusedTail(t["gt"], R.LAMBDA_O, R.LAMBDA_D)
+    outs = _RenderLossFn.apply(sig, rgbs, t["sem"], t["nrm"], tail.mask, t["dsig"], t["dirs"], t["deltas"], t["ts"], t["rays_a"],
+                               tail, t["scale3"], 1e-4, 7, t["bg"])
     terms = outs[0]
-    assert terms.shape == (5 if masked else 4,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:])
+    assert outs[11] is None          # neither entry has a workspace
+    assert terms.shape == (5 if masked else 4,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:] if o is not None)
     seed = torch.zeros_like(terms)
     seed[0] = 1.0
     torch.autograd.backward([terms], [seed])

@@ -169,3 +169,34 @@ def test_options_of_the_restatement():
     noise = R.fp32_error(x, ref=bg)
     print("float32 noise of the crafted batch:", {k: np.array2string(np.asarray(v), precision=3) for k, v in noise.items()})
     assert 0 < noise["opacity"] < 2e-6 and 0 < noise["d_sig"] * 27 < 2e-5 and noise["terms"].shape == (4,)
+
+
+def test_layout_table_and_fused_tail(ngp):
+    """rendering.TAIL_LAYOUT keeps every entry on its one-fill branch: vr_samples (an int64) 8-byte aligned behind the
+    terms, the workspace right behind it and as large as the header says, the accumulator exactly that long (the semantic
+    entry's workspace is an allocation of its own); and what FusedTail selects and refuses"""
+    import os
+    import re
+    from ngp_amd.rendering import MULTI_TERMS, TAIL_LAYOUT, FusedTail
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "ngp_hip.h")).read()
+    ints = {k.lower(): int(v) for k, v in re.findall(r"#define NGP_(SEM|NRM|DEP|MULTI)_WS_INTS (\d+)", header)}
+    assert sorted(ints) == ["dep", "multi", "nrm", "sem"]
+    assert list(TAIL_LAYOUT) == ["default", "masked", "sem", "nrm", "dep", "multi"]
+    for key, lay in TAIL_LAYOUT.items():
+        assert lay.vr_at % 2 == 0 and lay.vr_at >= lay.n_terms, key
+        assert lay.ws_ints == ints.get(key, 0), key
+        if lay.ws_at is not None:
+            assert lay.ws_ints > 0 and lay.ws_at == lay.vr_at + 2 and lay.acc == lay.ws_at + lay.ws_ints, key
+        else:
+            assert lay.acc == lay.vr_at + 2 and (lay.ws_ints == 0 or key == "sem"), key
+    assert [TAIL_LAYOUT[k].n_terms for k in TAIL_LAYOUT] == [4, 5, 6, 5, 5, 8]
+    gt, one = object(), {"depth_mono": (None, 1.0, 1.0)}
+    two = dict(one, normal_mono=(None, 1.0))
+    assert FusedTail(gt, 1.0, 2.0).entry == "default" and FusedTail(gt, 1.0, 2.0, mask=gt, size_delta=0.5).entry == "masked"
+    assert [FusedTail(gt, 0, 0, terms={t: ()}, packed=True).entry for t in MULTI_TERMS] == ["sem", "nrm", "dep"]
+    assert FusedTail(gt, 0, 0, terms=one).entry == "multi" and FusedTail(gt, 0, 0, terms=two).entry == "multi"
+    assert FusedTail(gt, 0, 0).terms == {} and FusedTail(gt, 0, 0, terms=two).terms == two
+    for bad in (dict(mask=gt, terms=one), dict(packed=True), dict(terms={}, packed=True), dict(terms=two, packed=True),
+                dict(terms={}), dict(terms={"sky": ()}), dict(terms=dict(one, sky=()))):
+        with pytest.raises(ValueError):
+            FusedTail(gt, 0, 0, **bad)

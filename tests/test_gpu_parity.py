@@ -1158,7 +1158,7 @@ def test_fused_tail_with_random_background_and_codes(ngp):
     codes, random background colour): every result, the loss terms and every gradient (field parameters, appearance
     codes) against the launch-per-operation route on the same samples and the same background draw."""
     from ngp_amd.losses import nerf_loss_and_grads, NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     torch.manual_seed(33)
     model = ngp.networks.NGP(scale=8.0, embed_a=True, embed_a_len=8).to(DEV)
@@ -1184,7 +1184,7 @@ def test_fused_tail_with_random_background_and_codes(ngp):
         torch.manual_seed(35)                      # same marcher noise, same background colour
         kw = dict(exp_step_factor=1 / 256, num_classes=7, random_bg=True, embedding_a=codes[img])
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, lam_o, lam_d), **kw)
+            res = render(model, o, d, _fused_loss=FusedTail(gt, lam_o, lam_d), **kw)
             assert "_loss_terms" in res
             terms = res.pop("_loss_terms")
             torch.autograd.backward([terms], [torch.tensor([1.0, 0, 0, 0], device=DEV)])
@@ -1746,7 +1746,7 @@ def test_training_step_matches_reference_golden(ngp, golden, monkeypatch, route)
     vren = C oracle).  Here: render() -> fused loss kernels -> backward -> NGPTrainer.optimizer_step()."""
     from helpers import table_rule
     from ngp_amd.losses import nerf_loss_and_grads
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.trainer import NGPTrainer
     g = golden("g8_train_step.npz")
     small = ("xyz_net.0.weight", "xyz_net.0.bias", "xyz_net.2.weight", "xyz_net.2.bias", "rgb_net.params",
@@ -1770,7 +1770,7 @@ def test_training_step_matches_reference_golden(ngp, golden, monkeypatch, route)
         with torch.no_grad():
             ref_res = render(model, o, d, exp_step_factor=0.0, num_classes=7)
         res = render(model, o, d, exp_step_factor=0.0, num_classes=7,
-                     _fused_loss=(gt, tr.loss_fn.lambda_opa, tr.loss_fn.lambda_distortion))
+                     _fused_loss=FusedTail(gt, tr.loss_fn.lambda_opa, tr.loss_fn.lambda_distortion))
     else:
         res = render(model, o, d, exp_step_factor=0.0, num_classes=7)
     monkeypatch.undo()

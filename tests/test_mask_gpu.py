@@ -148,9 +148,10 @@ def _scene_model(ngp, seed):
 def test_masked_fused_tail_matches_the_launch_per_operation_route(ngp, k):
     """scale 8, exponential stepping, random background, 1500 rays, same marcher noise and background draw on both
     routes.  A: render + NeRFLoss(embed_msk=True, mask=msk(uvi), step=k) + sum of means + autograd; B: render with
-    _fused_loss=(gt, lambda_o, lambda_d, msk(uvi), size_delta).  test_fused_tail_with_random_background_and_codes' bars."""
+    _fused_loss=FusedTail(gt, lambda_o, lambda_d, mask=msk(uvi), size_delta=size_delta).
+    test_fused_tail_with_random_background_and_codes' bars."""
     from ngp_amd.losses import NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     model = _scene_model(ngp, 33)
     msk = make_module(ngp, R.make_params())
@@ -172,7 +173,7 @@ def test_masked_fused_tail_matches_the_launch_per_operation_route(ngp, k):
         torch.manual_seed(35)
         kw = dict(exp_step_factor=1 / 256, num_classes=7, random_bg=True)
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, lam_o, lam_d, msk(uvi), size_delta), **kw)
+            res = render(model, o, d, _fused_loss=FusedTail(gt, lam_o, lam_d, mask=msk(uvi), size_delta=size_delta), **kw)
             assert "_loss_terms" in res
             terms = res.pop("_loss_terms")
             assert terms.shape == (5,)

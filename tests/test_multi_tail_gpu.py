@@ -1,7 +1,7 @@
 """The fused render + loss tail with several optional terms at once on the GPU (ngp_render_loss_fused_multi: the label
 count, the depth fit and render_loss_fused_kernel<CMAX, 32, false, SEM, NRM, DEP>) against the parent's single entries bit
 for bit, against ngp_render_loss_fused bit for bit, against the float64 restatement of tests/multi_tail_reference.py, and
-the routes built on it: rendering._RenderLossMultiFn, NGPTrainer(multi_terms=...), tools/train_dataset.py --multi_terms.
+the routes built on it: rendering._RenderLossFn, NGPTrainer(multi_terms=...), tools/train_dataset.py --multi_terms.
 
 Bars.  The outputs shared with ngp_render_loss_fused are that entry's bit for bit; against the restatement they keep
 tests/test_fused_tail_gpu.py's bars (opacity, depth, rgb, normal_pred, semantic, ws rtol 2e-5, atol 2e-6; d_rgbs rtol 2e-4,
@@ -93,7 +93,7 @@ def run_multi(ngp, x, mask, tg, T_thr=1e-4, classes=7, lam_o=R.LAMBDA_O, lam_d=R
     t = {k: T(x[k]) for k in ("sig", "rgbs", "dsig", "nrm", "sem", "dirs", "deltas", "ts", "rays_a", "gt", "bg", "scale3")}
     E = lambda *s: torch.full(s, float("nan"), device=DEV)
     total = torch.full((NR_,), -7, dtype=torch.int64, device=DEV)
-    if adjacent:                # rendering._RenderLossMultiFn's layout: one buffer, one memset
+    if adjacent:                # rendering.TAIL_LAYOUT['multi']: one buffer, one memset
         acc = E(10 + WS_INTS)
         terms, vr, ws_ = acc[:8], acc[8:10].view(torch.int64), acc[10:].view(torch.int32)
     else:
@@ -380,7 +380,7 @@ def test_block_edges(ngp, rows, mask):
 
 
 def test_memset_branches_garbage_and_a_second_call(ngp):
-    """terms, vr_samples and the workspace adjacent as rendering._RenderLossMultiFn lays them out (one fill) and in separate
+    """terms, vr_samples and the workspace adjacent as rendering._RenderLossFn lays them out (one fill) and in separate
     allocations (three fills), the workspace starting as -5, as all bits set and as a large positive pattern: the entry
     clears it, so the launches agree with one another and with the restatement, and a second call on the same buffers
     leaves the same per-ray and per-sample outputs bit for bit"""
@@ -438,10 +438,10 @@ _close, _grid_buffers = DG._close, DG._grid_buffers
 
 
 def test_wrapper_hands_back_the_direct_call(ngp):
-    """rendering._RenderLossMultiFn on the crafted batch: the outputs are those of the direct call, and back-propagating
+    """rendering._RenderLossFn with several terms on the crafted batch: the outputs are those of the direct call, and back-propagating
     terms[0] with a unit seed hands back the launch's d_sigmas, d_rgbs, d_sem and d_np bit for bit (padded with zeros to the
     inputs' widths); a term that is not named gives its input no gradient"""
-    from ngp_amd.rendering import _RenderLossMultiFn
+    from ngp_amd.rendering import FusedTail, _RenderLossFn
     x = batch("crafted")
     tg = targets("crafted", 10)
     for mask in (7, 6, 5):
@@ -456,10 +456,11 @@ def test_wrapper_hands_back_the_direct_call(ngp):
             named["normal_mono"] = (T(tg["normals"]), NR.LAMBDA_NM)
         if mask & DEP:
             named["depth_mono"] = (T(tg["depths"]), DR.LAMBDA_DM, 0.5)
-        rest = (t["dsig"], t["dirs"], t["deltas"], t["ts"], t["rays_a"], t["gt"])
-        outs = _RenderLossMultiFn.apply(*leaves, *rest, named, t["scale3"], 1e-4, classes, R.LAMBDA_O, R.LAMBDA_D, t["bg"])
+        rest = (None, t["dsig"], t["dirs"], t["deltas"], t["ts"], t["rays_a"])
+        outs = _RenderLossFn.apply(*leaves, *rest, FusedTail(t["gt"], R.LAMBDA_O, R.LAMBDA_D, terms=named), t["scale3"], 1e-4,
+                                   classes, t["bg"])
         terms = outs[0]
-        assert terms.shape == (8,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:])
+        assert terms.shape == (8,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:] if o is not None)
         seed = torch.zeros_like(terms)
         seed[0] = 1.0
         torch.autograd.backward([terms], [seed])
@@ -491,7 +492,7 @@ def test_wrapper_hands_back_the_direct_call(ngp):
     for bad in (dict(), dict(sky=(1,)), dict(semantic=(T(tg["labels"])[:5], 1.0, 1.0)), dict(normal_mono=(T(tg["normals"]).double(), 1.0)),
                 dict(depth_mono=(T(tg["depths"]).reshape(-1, 1), 1.0, 1.0)), dict(depth_mono=(T(tg["depths"]), 1.0, 0.0))):
         with pytest.raises((ValueError, RuntimeError)):
-            _RenderLossMultiFn.apply(*leaves, *rest, bad, t["scale3"], 1e-4, 7, 0.0, 0.0, None)
+            _RenderLossFn.apply(*leaves, *rest, FusedTail(t["gt"], 0.0, 0.0, terms=bad), t["scale3"], 1e-4, 7, None)
 
 
 def _scene_targets(scene, o, d, classes, gen):
@@ -503,10 +504,10 @@ def test_fused_multi_tail_matches_the_launch_per_operation_route(ngp, classes):
     """scale 8, exponential stepping, random background, 1500 rays of the proxy scene, same marcher noise and background
     draw on both routes, labels valid or 256, every normal non-zero, depths without NaN (where the module states the same
     loss).  A: render + NeRFLoss(semantic, normal_mono, depth_mono, scale=8) + sum of means + autograd; B: render with
-    _fused_loss=(gt, lambda_o, lambda_d, 'multi', {...}) through rendering._RenderLossMultiFn.  The bars of the three sibling
+    _fused_loss=FusedTail(gt, lambda_o, lambda_d, terms={...}) through rendering._RenderLossFn.  The bars of the three sibling
     comparisons: terms rtol 1e-4, parameter gradients within 3e-4 of the largest entry."""
     from ngp_amd.losses import NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     torch.manual_seed(33)
     model = _grid_buffers(ngp.networks.NGP(scale=8.0, classes=classes).to(DEV))
@@ -531,7 +532,7 @@ def test_fused_multi_tail_matches_the_launch_per_operation_route(ngp, classes):
         torch.manual_seed(35)
         kw = dict(exp_step_factor=1 / 256, num_classes=classes, random_bg=True)
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, f.lambda_opa, f.lambda_distortion, "multi", multi), **kw)
+            res = render(model, o, d, _fused_loss=FusedTail(gt, f.lambda_opa, f.lambda_distortion, terms=multi), **kw)
             assert "_loss_terms" in res
             terms = res.pop("_loss_terms")
             assert terms.shape == (8,) and terms.requires_grad

@@ -1,6 +1,6 @@
 """The normal_mono form of the fused render + loss tail on the GPU (render_loss_fused_kernel<8, 32, false, false, true>
 behind ngp_render_loss_fused_nrm) against the float64 restatement of tests/normal_tail_reference.py, and the routes
-built on it: rendering._RenderLossNrmFn, NGPTrainer(normal_mono=True), tools/train_dataset.py --normal_mono.
+built on it: rendering._RenderLossFn, NGPTrainer(normal_mono=True), tools/train_dataset.py --normal_mono.
 
 Bars.  The outputs this entry shares with ngp_render_loss_fused keep tests/test_fused_tail_gpu.py's bars: opacity, depth,
 rgb, normal_pred, semantic, ws rtol 2e-5, atol 2e-6; d_sigmas, d_rgbs rtol 2e-4, atol 2e-5 / n_rays; Ro, Rp and
@@ -78,7 +78,7 @@ def run_nrm(ngp, x, normals, T_thr=1e-4, classes=7, lam_o=NR.R.LAMBDA_O, lam_d=N
         nrm, sem = wide[0], wide[1]
     E = lambda *s: torch.full(s, float("nan"), device=DEV)
     total = torch.full((NR_,), -7, dtype=torch.int64, device=DEV)
-    if adjacent:                # rendering._RenderLossNrmFn's layout: one buffer, one memset
+    if adjacent:                # rendering.TAIL_LAYOUT['nrm']: one buffer, one memset
         acc = E(12)
         terms, vr, ws_ = acc[:5], acc[6:8].view(torch.int64), acc[8:12].view(torch.int32)
     else:
@@ -244,7 +244,7 @@ def test_wide_normal_rows(ngp):
 
 
 def test_memset_branches(ngp):
-    """terms, vr_samples and the workspace adjacent as rendering._RenderLossNrmFn lays them out (one fill) and in separate
+    """terms, vr_samples and the workspace adjacent as rendering._RenderLossFn lays them out (one fill) and in separate
     allocations (three fills), all pre-filled with NaN / negative numbers"""
     x, normals = batch("crafted"), normals_of("crafted")
     a = run_nrm(ngp, x, normals, adjacent=True)
@@ -350,10 +350,10 @@ def _nonzero_normals(scene, o, d, gen):
 def test_fused_normal_tail_matches_the_launch_per_operation_route(ngp):
     """scale 8, exponential stepping, random background, 1500 rays of the proxy scene, same marcher noise and background
     draw on both routes, every target non-zero.  A: render + NeRFLoss(normal_mono=True) + sum of means + autograd; B:
-    render with _fused_loss=(gt, lambda_o, lambda_d, 'nrm', normals, lambda_nm) through rendering._RenderLossNrmFn.  The
+    render with _fused_loss=FusedTail(..., terms={'normal_mono': ...}, packed=True) through rendering._RenderLossFn.  The
     bars of the semantic counterpart: terms rtol 1e-4, parameter gradients within 3e-4 of the largest entry."""
     from ngp_amd.losses import NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     torch.manual_seed(33)
     model = _grid_buffers(ngp.networks.NGP(scale=8.0).to(DEV))
@@ -376,7 +376,8 @@ def test_fused_normal_tail_matches_the_launch_per_operation_route(ngp):
         torch.manual_seed(35)
         kw = dict(exp_step_factor=1 / 256, random_bg=True)
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, lam[0], lam[1], "nrm", normals, lam[2]), **kw)
+            tail = FusedTail(gt, lam[0], lam[1], terms={"normal_mono": (normals, lam[2])}, packed=True)
+            res = render(model, o, d, _fused_loss=tail, **kw)
             assert "_loss_terms" in res
             terms = res.pop("_loss_terms")
             assert terms.shape == (5,) and terms.requires_grad
@@ -411,18 +412,18 @@ def test_fused_normal_tail_matches_the_launch_per_operation_route(ngp):
 
 
 def test_wrapper_hands_back_the_direct_call(ngp):
-    """rendering._RenderLossNrmFn on the crafted batch: the outputs are those of the direct call, and back-propagating
+    """rendering._RenderLossFn with the packed normal_mono term on the crafted batch: the outputs are those of the direct call, and back-propagating
     terms[0] with a unit seed hands back the launch's d_sigmas, d_rgbs and d_normal_head bit for bit"""
-    from ngp_amd.rendering import _RenderLossNrmFn
+    from ngp_amd.rendering import FusedTail, _RenderLossFn
     x, normals = batch("crafted"), normals_of("crafted")
     direct = run_nrm(ngp, x, normals, use_scale=True)
     t = {k: T(x[k]) for k in ("sig", "rgbs", "dsig", "nrm", "sem", "dirs", "deltas", "ts", "rays_a", "gt", "bg", "scale3")}
     sig, rgbs, head = t["sig"].requires_grad_(True), t["rgbs"].requires_grad_(True), t["nrm"].requires_grad_(True)
-    args = (t["dsig"], t["sem"], t["dirs"], t["deltas"], t["ts"], t["rays_a"], t["gt"])
-    outs = _RenderLossNrmFn.apply(sig, rgbs, head, *args, T(normals), t["scale3"], 1e-4, 7, NR.R.LAMBDA_O, NR.R.LAMBDA_D,
-                                  NR.LAMBDA_NM, t["bg"])
+    args = (sig, rgbs, t["sem"], head, None, t["dsig"], t["dirs"], t["deltas"], t["ts"], t["rays_a"])
+    tail = FusedTail(t["gt"], NR.R.LAMBDA_O, NR.R.LAMBDA_D, terms={"normal_mono": (T(normals), NR.LAMBDA_NM)}, packed=True)
+    outs = _RenderLossFn.apply(*args, tail, t["scale3"], 1e-4, 7, t["bg"])
     terms = outs[0]
-    assert terms.shape == (5,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:])
+    assert terms.shape == (5,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:] if o is not None)
     seed = torch.zeros_like(terms)
     seed[0] = 1.0
     torch.autograd.backward([terms], [seed])
@@ -437,7 +438,8 @@ def test_wrapper_hands_back_the_direct_call(ngp):
     assert head.grad.shape == (x["n"], 3) and np.array_equal(N(head.grad)[own], direct["d_np"][own])
     for bad in (T(normals)[:5], T(normals).double(), T(normals)[:, :2]):
         with pytest.raises(ValueError):
-            _RenderLossNrmFn.apply(sig, rgbs, head, *args, bad, t["scale3"], 1e-4, 7, 0.0, 0.0, 0.0, None)
+            _RenderLossFn.apply(*args, FusedTail(t["gt"], 0.0, 0.0, terms={"normal_mono": (bad, 0.0)}, packed=True),
+                                t["scale3"], 1e-4, 7, None)
 
 
 # ------------------------------------------------------------------------------------------- h. the trainer

@@ -1,6 +1,6 @@
 """The semantic form of the fused render + loss tail on the GPU (render_loss_fused_kernel<8 | 16, 32, false, true> behind
 ngp_render_loss_fused_sem) against the float64 restatement of tests/semantic_tail_reference.py, and the routes built on
-it: rendering._RenderLossSemFn, NGPTrainer(semantic=True), tools/train_dataset.py --render_semantic.
+it: rendering._RenderLossFn, NGPTrainer(semantic=True), tools/train_dataset.py --render_semantic.
 
 Bars.  The outputs this entry shares with ngp_render_loss_fused keep tests/test_fused_tail_gpu.py's bars: opacity, depth,
 rgb, normal_pred, semantic, ws rtol 2e-5, atol 2e-6; d_rgbs rtol 2e-4, atol 2e-5 / n_rays; Ro, Rp and terms[0:4] 8 times
@@ -77,7 +77,7 @@ def run_sem(ngp, x, labels, T_thr=1e-4, classes=7, lam_o=S.R.LAMBDA_O, lam_d=S.R
         nrm, sem = wide[0], wide[1]
     E = lambda *s: torch.full(s, float("nan"), device=DEV)
     total = torch.full((NR,), -7, dtype=torch.int64, device=DEV)
-    if adjacent:                # rendering._RenderLossSemFn's layout: one buffer, one memset
+    if adjacent:                # rendering.TAIL_LAYOUT['sem']: one buffer, one memset
         acc = E(8)
         terms, vr = acc[:6], acc[6:8].view(torch.int64)
     else:
@@ -242,7 +242,7 @@ def test_wide_logit_rows(ngp, classes):
 
 
 def test_memset_branches(ngp):
-    """terms and vr_samples adjacent as rendering._RenderLossSemFn lays them out (one fill) and in separate allocations
+    """terms and vr_samples adjacent as rendering._RenderLossFn lays them out (one fill) and in separate allocations
     (two fills), both pre-filled with NaN / a large negative count"""
     x = batch("crafted")
     labels = S.labels_for(x, 10)
@@ -328,10 +328,10 @@ def _scene_labels(scene, o, d, classes, gen):
 def test_fused_semantic_tail_matches_the_launch_per_operation_route(ngp, classes):
     """scale 8, exponential stepping, random background, 1500 rays of the proxy scene, same marcher noise and background
     draw on both routes.  A: render + NeRFLoss(semantic=True) + sum of means + autograd; B: render with
-    _fused_loss=(gt, lambda_o, lambda_d, 'sem', labels, lambda_sem, lambda_sky) through rendering._RenderLossSemFn.
+    _fused_loss=FusedTail(gt, lambda_o, lambda_d, terms={'semantic': ...}, packed=True) through rendering._RenderLossFn.
     tests/test_mask_gpu.py's tolerances for its masked-tail-against-layered comparison."""
     from ngp_amd.losses import NeRFLoss
-    from ngp_amd.rendering import render
+    from ngp_amd.rendering import FusedTail, render
     from ngp_amd.synthetic import LegoProxy
     torch.manual_seed(33)
     model = _grid_buffers(ngp.networks.NGP(scale=8.0, classes=classes).to(DEV))
@@ -355,7 +355,8 @@ def test_fused_semantic_tail_matches_the_launch_per_operation_route(ngp, classes
         torch.manual_seed(35)
         kw = dict(exp_step_factor=1 / 256, num_classes=classes, random_bg=True)
         if fused:
-            res = render(model, o, d, _fused_loss=(gt, lam[0], lam[1], "sem", labels, lam[2], lam[3]), **kw)
+            tail = FusedTail(gt, lam[0], lam[1], terms={"semantic": (labels, lam[2], lam[3])}, packed=True)
+            res = render(model, o, d, _fused_loss=tail, **kw)
             assert "_loss_terms" in res
             terms = res.pop("_loss_terms")
             assert terms.shape == (6,) and terms.requires_grad
@@ -390,9 +391,9 @@ def test_fused_semantic_tail_matches_the_launch_per_operation_route(ngp, classes
 
 
 def test_wrapper_hands_back_the_direct_call(ngp):
-    """rendering._RenderLossSemFn on the crafted batch: the outputs are those of the direct call, and back-propagating
+    """rendering._RenderLossFn with the packed semantic term on the crafted batch: the outputs are those of the direct call, and back-propagating
     terms[0] with a unit seed hands back the launch's d_sigmas, d_rgbs and d_sem_logits bit for bit"""
-    from ngp_amd.rendering import _RenderLossSemFn
+    from ngp_amd.rendering import FusedTail, _RenderLossFn
     x = batch("crafted")
     classes = 10
     labels = S.labels_for(x, classes)
@@ -400,11 +401,11 @@ def test_wrapper_hands_back_the_direct_call(ngp):
     t = {k: T(x[k]) for k in ("sig", "rgbs", "dsig", "nrm", "sem", "dirs", "deltas", "ts", "rays_a", "gt", "bg", "scale3")}
     sig, rgbs = t["sig"].requires_grad_(True), t["rgbs"].requires_grad_(True)
     logits = t["sem"][:, :classes].contiguous().requires_grad_(True)
-    outs = _RenderLossSemFn.apply(sig, rgbs, logits, t["dsig"], t["nrm"], t["dirs"], t["deltas"], t["ts"], t["rays_a"], t["gt"],
-                                  T(labels), t["scale3"], 1e-4, classes, S.R.LAMBDA_O, S.R.LAMBDA_D, S.LAMBDA_SEM, S.LAMBDA_SKY,
-                                  t["bg"])
+    args = (sig, rgbs, logits, t["nrm"], None, t["dsig"], t["dirs"], t["deltas"], t["ts"], t["rays_a"])
+    tail = FusedTail(t["gt"], S.R.LAMBDA_O, S.R.LAMBDA_D, terms={"semantic": (T(labels), S.LAMBDA_SEM, S.LAMBDA_SKY)}, packed=True)
+    outs = _RenderLossFn.apply(*args, tail, t["scale3"], 1e-4, classes, t["bg"])
     terms = outs[0]
-    assert terms.shape == (6,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:])
+    assert terms.shape == (6,) and terms.requires_grad and not any(o.requires_grad for o in outs[1:] if o is not None)
     seed = torch.zeros_like(terms)
     seed[0] = 1.0
     torch.autograd.backward([terms], [seed])
@@ -417,8 +418,8 @@ def test_wrapper_hands_back_the_direct_call(ngp):
     assert np.array_equal(N(rgbs.grad)[own], direct["d_rgb"][own])
     assert logits.grad.shape == (x["n"], classes) and np.array_equal(N(logits.grad)[own], direct["d_sem"][own])
     with pytest.raises(ValueError):
-        _RenderLossSemFn.apply(sig, rgbs, logits, t["dsig"], t["nrm"], t["dirs"], t["deltas"], t["ts"], t["rays_a"], t["gt"],
-                               T(labels)[:5], t["scale3"], 1e-4, classes, 0.0, 0.0, 0.0, 0.0, None)
+        _RenderLossFn.apply(*args, FusedTail(t["gt"], 0.0, 0.0, terms={"semantic": (T(labels)[:5], 0.0, 0.0)}, packed=True),
+                            t["scale3"], 1e-4, classes, None)
 
 
 # ------------------------------------------------------------------------------------------- h. the trainer
