@@ -695,7 +695,13 @@ class NGP(nn.Module):
         with torch.enable_grad():
             h = self.xyz_net(self.xyz_encoder(xn))
             sigmas = self.sigma_act(h[:, 0])
-            grads = torch.autograd.grad(sigmas, x, torch.ones_like(sigmas), create_graph=True)[0]
+            # this walk wants d(sigma)/dx only: without the flag the encoder's backward would also scatter d(sum sigma)/dtable,
+            # into a table-sized scratch array or, under a trainer, into the flat gradient itself
+            self.xyz_encoder.input_grad_only = True
+            try:
+                grads = torch.autograd.grad(sigmas, x, torch.ones_like(sigmas), create_graph=True)[0]
+            finally:
+                self.xyz_encoder.input_grad_only = False
         feat_rgb = self.rgb_encoder(xn.detach())
         dn = F.normalize(d, p=2, dim=-1, eps=1e-6)
         cols = [self.dir_encoder((dn + 1) / 2), feat_rgb]

@@ -45,7 +45,9 @@ class _GridFwd(Function):
         dx = dparams = None
         if ctx.needs_input_grad[0]:
             dx = _GridBwdInput.apply(dy, x, params, enc)
-        if ctx.needs_input_grad[1]:
+        # needs_input_grad is fixed at forward time: a graph walk that asks for dL/dx alone (autograd.grad(y, x)) still
+        # arrives here with [1] set, and the scatter below would add to the trainer's buffer behind autograd's back
+        if ctx.needs_input_grad[1] and not enc.input_grad_only:
             buf = enc.grad_buffer
             if buf is not None:
                 # trainer-owned flat gradient: scatter-add straight into it (autograd sees None)
@@ -113,6 +115,7 @@ class Encoding(nn.Module):
         # view of the table's gradient (the scatter adds into it, autograd gets None); on_grad_ready(): called behind the
         # scatter, and whether it issues a collective; _bound_valid: no scatter outside its norm bound added to grad_buffer
         self.grad_buffer = self.on_grad_ready = None
+        self.input_grad_only = False   # True while a caller walks the graph for dL/dx alone: no table scatter (_GridFwd)
         self.grad_ready_is_collective = False
         self._bound_valid = True
         if ot in ("Grid", "HashGrid", "DenseGrid"):
