@@ -499,6 +499,33 @@ int ngp_embed_a_bwd(const float* dL_dcols, int64_t ld, int E, const int64_t* img
                     int64_t n_rays, int64_t n_imgs, float* d_weight, void* stream);
 
 /* ------------------------------------------------------------------------
+ * T1  HDR-NeRF tone-mappers (use_exposure: models/networks_noCUDA.py:238-251, train.py:301-306): the three per-channel
+ * tcnn networks 1 -> 64 (ReLU) -> 1 (Sigmoid) of NGP(rgb_act='None'), all channels in one launch each way.
+ * params0..2: one channel's 2048 floats each in the tinycudann.Network layout, W1 (64,16) row-major, then W2 (16,64),
+ * 16-byte aligned.  tcnn pads the one input to 16 columns with ones, so per channel c and sample s
+ *     u = log_radiance[s][c] + ln(exposure),  z_j = W1[j][0] u + sum_{k=1..15} W1[j][k],  rgb[s][c] = sigmoid(sum_j W2[0][j] relu(z_j)).
+ * log_radiance, rgb, dL_drgb, d_log_radiance (n,3).  exposure: NULL (unit exposure, ln = 0), or seconds with
+ * exposure_stride 0 (one value for every sample) or 1 (one value per sample); the logarithm is taken here.
+ * bwd: recomputes the hidden layer (nothing is saved but the inputs), writes d_log_radiance (NULL: not wanted) and
+ *   ACCUMULATES (+=, the caller zeroes) the parameter gradients into dparams0..2 (the layout of params): rows 1..15 of W2
+ *   are not touched, the 15 padding columns of a row of W1 all receive the same sum; the ReLU derivative is z_j > 0.
+ *   There is no gradient for exposure.  A persistent grid keeps every workgroup's 576 sums in registers across its
+ *   tiles and stores them as doubles to `workspace` (ngp_tonemap_bwd_workspace(n) floats, host-only query, at most
+ *   2 * 576 * NGP_TONEMAP_BWD_MAX_BLOCKS, 8-byte aligned; scratch: its contents need not be cleared or kept, but two
+ *   calls that may overlap need one each); a second launch adds them over the workgroups in a fixed order: no atomics,
+ *   the same bits on every run.  Between its float32 inputs and outputs the backward works in double.
+ * n == 0 returns NGP_OK before any pointer is looked at (nothing is launched, the sinks are left alone); n < 0 or a
+ * stride other than 0 or 1 is NGP_EINVAL.
+ * ---------------------------------------------------------------------- */
+#define NGP_TONEMAP_BWD_MAX_BLOCKS 512
+int ngp_tonemap_fwd(const float* params0, const float* params1, const float* params2, const float* log_radiance,
+                    const float* exposure, int exposure_stride, int64_t n, float* rgb, void* stream);
+int64_t ngp_tonemap_bwd_workspace(int64_t n);
+int ngp_tonemap_bwd(const float* params0, const float* params1, const float* params2, const float* log_radiance,
+                    const float* exposure, int exposure_stride, const float* dL_drgb, int64_t n, float* d_log_radiance,
+                    float* dparams0, float* dparams1, float* dparams2, float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------
  * P1  camera pose refinement (optimize_ext: train.py:143-149, 225-230; datasets/ray_utils.py:50-104): the rays of a
  * batch from per-image corrections, and the adjoint of that map reduced per image.  One launch each way.
  * poses (n_imgs, 3, 4) camera-to-world [Rp | t]; dR (n_imgs, 3) axis-angle, dT (n_imgs, 3); directions (n_pix, 3) camera

@@ -26,6 +26,7 @@ SOURCES = [
     ("mlp_kernels.hip", []),
     ("mask_kernels.hip", []),
     ("embed_kernels.hip", []),
+    ("tonemap_kernels.hip", []),
     ("pose_kernels.hip", ["-ffp-contract=off"]),    # at dR = dT = 0 the rays are bit-identical to get_rays' products
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),

@@ -125,7 +125,7 @@ class ColmapDataset(BaseDataset):
             img = torch.from_numpy(read_image(img_path, self.img_wh))
             if hdr:
                 scene = [p for p in self.root_dir.split('/') if p][-1]
-                digit = int(img_path.split('.')[0][-1])
+                digit = int(os.path.splitext(os.path.basename(img_path))[0][-1])   # (a directory name may hold a dot)
                 img = torch.cat([img, _HDR_EXPOSURES[scene][digit] * torch.ones_like(img[:, :1])], 1)
             self.rays.append(img)
         self.rays = torch.stack(self.rays).to(self.device)  # (N_images, hw, 3|4)

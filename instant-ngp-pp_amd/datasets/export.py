@@ -101,12 +101,10 @@ def export_nerfpp(root, images, c2w, K, splits):
     return root
 
 
-def export_colmap(root, images, c2w, K, names=None, points=None, model="PINHOLE", labels=None, shuffle_seed=None):
-    """COLMAP layout: sparse/0/*.bin with ONE camera (id 1) and world-to-camera poses, images/<name>.
-    `shuffle_seed` stores the image records in a permuted order (COLMAP registers images in
-    reconstruction order, not name order — the loader has to sort)."""
-    n, h, w = images.shape[0], images.shape[1], images.shape[2]
-    names = names or [f"frame_{i:04d}.png" for i in range(n)]
+def _write_colmap_sparse(root, hw, c2w, K, names, points=None, model="PINHOLE", order=None):
+    """sparse/0/{cameras,images,points3D}.bin: ONE camera (id 1) of size hw = (h, w), world-to-camera poses, records
+    stored in `order`"""
+    h, w = hw
     os.makedirs(os.path.join(root, "sparse", "0"), exist_ok=True)
     if model == "PINHOLE":
         params = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
@@ -118,22 +116,72 @@ def export_colmap(root, images, c2w, K, names=None, points=None, model="PINHOLE"
         params = [0.0] * cu.CAMERA_MODELS[cu.CAMERA_MODEL_IDS[model]][1]
     cu.write_cameras_binary({1: cu.Camera(1, model, w, h, np.array(params, dtype=np.float64))},
                             os.path.join(root, "sparse/0/cameras.bin"))
-    order = list(range(n))
-    if shuffle_seed is not None:
-        order = list(np.random.default_rng(shuffle_seed).permutation(n))
     records = {}
-    for i in order:
+    for i in (range(len(names)) if order is None else order):
         w2c = np.linalg.inv(_homog(c2w[i]))
         records[i + 1] = cu.Image(i + 1, cu.rotmat2qvec(w2c[:3, :3]), w2c[:3, 3], 1, names[i],
                                   np.zeros((0, 2)), np.zeros(0, dtype=np.int64))
-        _save_png(images[i], os.path.join(root, "images", names[i]))
-        if labels is not None:
-            _save_png(_label_u8(labels[i]), os.path.join(root, "semantic", os.path.splitext(names[i])[0] + ".pgm"))
     cu.write_images_binary(records, os.path.join(root, "sparse/0/images.bin"))
     points = np.zeros((1, 3)) if points is None else np.asarray(points, dtype=np.float64)
     cloud = {j + 1: cu.Point3D(j + 1, p, np.array([128, 128, 128], dtype=np.uint8), 0.5,
                                np.array([1], dtype=np.int32), np.array([0], dtype=np.int32)) for j, p in enumerate(points)}
     cu.write_points3d_binary(cloud, os.path.join(root, "sparse/0/points3D.bin"))
+
+
+def export_colmap(root, images, c2w, K, names=None, points=None, model="PINHOLE", labels=None, shuffle_seed=None):
+    """COLMAP layout: sparse/0/*.bin with ONE camera (id 1) and world-to-camera poses, images/<name>.
+    `shuffle_seed` stores the image records in a permuted order (COLMAP registers images in
+    reconstruction order, not name order — the loader has to sort)."""
+    n, h, w = images.shape[0], images.shape[1], images.shape[2]
+    names = names or [f"frame_{i:04d}.png" for i in range(n)]
+    order = list(range(n))
+    if shuffle_seed is not None:
+        order = list(np.random.default_rng(shuffle_seed).permutation(n))
+    _write_colmap_sparse(root, (h, w), c2w, K, names, points, model, order)
+    for i in order:
+        _save_png(images[i], os.path.join(root, "images", names[i]))
+        if labels is not None:
+            _save_png(_label_u8(labels[i]), os.path.join(root, "semantic", os.path.splitext(names[i])[0] + ".pgm"))
+    return root
+
+
+HDR_UNIT_EXPOSURE_RGB = 0.73   # what ColmapDataset sets for the synthetic HDR-NeRF scenes
+
+
+def hdr_response(radiance, seconds, unit_rgb=HDR_UNIT_EXPOSURE_RGB):
+    """the camera response of export_hdr_nerf_syn: sigmoid(ln(radiance * seconds) + logit(unit_rgb)), 0 at zero
+    radiance.  Unit radiance at unit exposure maps to unit_rgb, and a tone-mapper (a sigmoid of a function of
+    ln radiance + ln seconds) can represent it."""
+    x = np.asarray(radiance, dtype=np.float64) * float(seconds)
+    return x / (x + (1.0 - unit_rgb) / unit_rgb)
+
+
+def export_hdr_nerf_syn(root, radiance_images, c2w, K, scene='chair'):
+    """The HDR-NeRF synthetic layout ColmapDataset._hdr_split reads (`root` must end in HDR-NeRF/syndata/<scene>: the
+    loader takes the layout, the split rule and the exposure table from the path): sparse/0/*.bin with the 35
+    registered frames in name order, train/NNN_e.png = the last 18 poses at exposures e in {0, 2, 4}, test/NNN_e.png =
+    the first 17 poses at e in {1, 3}: exposures never seen in training, HDR-NeRF's protocol.  Nothing else is written
+    into either directory (the loader globs *[024].png and *[13].png).
+    radiance_images (35, h, w, 3): linear radiance, float, or uint8 (taken as value / 255); the 8-bit image at exposure e
+    is hdr_response(radiance, colmap._HDR_EXPOSURES[scene][e])."""
+    from .colmap import _HDR_EXPOSURES
+    radiance = np.asarray(radiance_images)
+    if radiance.ndim != 4 or radiance.shape[0] != 35 or radiance.shape[3] != 3:
+        raise ValueError(f"the synthetic HDR-NeRF split is fixed at 35 poses of (h, w, 3): got {radiance.shape}")
+    if scene not in _HDR_EXPOSURES:
+        raise ValueError(f"no exposure table for scene {scene!r}: known {sorted(_HDR_EXPOSURES)}")
+    parts = [p for p in os.path.normpath(str(root)).split(os.sep) if p]
+    if parts[-1] != scene or 'syndata' not in parts or 'HDR-NeRF' not in parts:
+        raise ValueError(f"root must end in HDR-NeRF/syndata/{scene} (the loader reads the layout from the path): got {root}")
+    if radiance.dtype == np.uint8:
+        radiance = radiance.astype(np.float64) / 255.0
+    times = _HDR_EXPOSURES[scene]
+    _write_colmap_sparse(root, radiance.shape[1:3], c2w, K, [f"{i:03d}.png" for i in range(35)])
+    for split, poses, digits in (("test", range(17), (1, 3)), ("train", range(17, 35), (0, 2, 4))):
+        for i in poses:
+            for e in digits:
+                img = (hdr_response(radiance[i], times[e]) * 255.0 + 0.5).astype(np.uint8)
+                _save_png(img, os.path.join(root, split, f"{i:03d}_{e}.png"))
     return root
 
 

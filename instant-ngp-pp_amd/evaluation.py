@@ -251,14 +251,21 @@ def evaluate_split(model, test_set, chunk=131072, on_image=None, **render_kwargs
     `normals` (test items carry no 'normal', the reference's rule in datasets/base.py: test_set.normals[i] is read) the
     dictionary also holds 'normal_deg', normal_degrees of results['normal_pred'] per image (NaN: no pixel has a normal).
     When the split has `depths_2d` (read as test_set.depths_2d[i], like the normals) it also holds 'depth_absrel',
-    depth_absrel of results['depth'] per image (NaN: no pixel has a depth)."""
+    depth_absrel of results['depth'] per image (NaN: no pixel has a depth).  When a test item carries 'exposure' (HDR-NeRF
+    data) and the model is tone-mapped (rgb_act='None'), that image is rendered at its exposure time, unless render_kwargs
+    names an exposure itself."""
     psnrs, ssims, accs, mious, valids, degs, rels = [], [], [], [], [], [], []
     classes = render_kwargs.get("num_classes", 7)
     for i in range(len(test_set)):
         s = test_set[i]
         if "rgb" not in s:
             raise ValueError("the split has no ground-truth images to evaluate against")
-        results = render_image(model, test_set.directions, s["pose"], chunk, **render_kwargs)
+        kw = render_kwargs
+        if "exposure" in s and getattr(model, "rgb_act", "Sigmoid") == "None" and "exposure" not in render_kwargs:
+            # HDR-NeRF data: one exposure time per test image, every sample's (a (1, 1) tensor is not expanded per ray)
+            kw = dict(render_kwargs, exposure=torch.as_tensor(s["exposure"], dtype=torch.float32)
+                      .to(s["pose"].device).reshape(1, 1))
+        results = render_image(model, test_set.directions, s["pose"], chunk, **kw)
         p, q, rgb = image_metrics(results["rgb"], s["rgb"], test_set.img_wh)
         psnrs.append(p)
         ssims.append(q)

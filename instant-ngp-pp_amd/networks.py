@@ -522,6 +522,55 @@ class _FieldFn(Function):
         return (None, g_x, g_d, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None)
 
 
+_TONE_WS = {}
+
+
+def _tone_workspace(dev):
+    """ngp_tonemap_bwd's scratch (the workgroups' partial sums: at most 512 x 576 doubles), one per device AND stream: two
+    backwards on one stream run one behind the other (a step's render and its unit-exposure term do), backwards on two
+    streams may overlap and must not share their partial sums"""
+    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
+    if key not in _TONE_WS:
+        _TONE_WS[key] = torch.empty(call_host("tonemap_bwd_workspace", 1 << 40), dtype=_f32, device=dev)
+    return _TONE_WS[key]
+
+
+class _ToneMapFn(Function):
+    """rgb (n,3) = the three tone-mappers of log_radiance (n,3) + ln(exposure), one launch each way (ngp_tonemap_fwd /
+    ngp_tonemap_bwd).  exposure: None, one value (every sample's) or (n) values; it takes no gradient.  Parameter
+    gradients: into the owner's `link.grad_sinks` (tone_0..2: a trainer's flat gradient views, autograd gets None, as
+    _FieldFn does) or, without sinks, handed to autograd."""
+
+    @staticmethod
+    def forward(ctx, log_radiance, exposure, p0, p1, p2, owner):
+        n = log_radiance.shape[0]
+        rgb = torch.empty(n, 3, dtype=_f32, device=log_radiance.device)
+        stride = 0 if exposure is None or exposure.numel() == 1 else 1
+        call("tonemap_fwd", p0, p1, p2, log_radiance, exposure, stride, n, rgb)
+        ctx.save_for_backward(log_radiance, exposure, p0, p1, p2)
+        ctx.owner, ctx.stride = owner, stride
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g):
+        log_radiance, exposure, p0, p1, p2 = ctx.saved_tensors
+        need_x, need_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[2:5])
+        if not (need_x or need_p):
+            return (None,) * 6
+        sinks = ctx.owner.link.grad_sinks
+        to_sinks = need_p and "tone_0" in sinks
+        if to_sinks:
+            out = [sinks[f"tone_{i}"] for i in range(3)]
+        else:
+            out = [torch.zeros_like(p) for p in (p0, p1, p2)]
+        dx = torch.empty_like(log_radiance) if need_x else None
+        call("tonemap_bwd", p0, p1, p2, log_radiance, exposure, ctx.stride, g.contiguous(), log_radiance.shape[0], dx,
+             *out, _tone_workspace(g.device))
+        if to_sinks or not need_p:
+            return (dx,) + (None,) * 5
+        return (dx, None) + tuple(t if need else None for t, need in zip(out, ctx.needs_input_grad[2:5])) + (None,)
+
+
 class NGP(nn.Module):
     def __init__(self, scale, rgb_act='Sigmoid', use_skybox=False, embed_a=False, embed_a_len=12, classes=7):
         super().__init__()
@@ -745,14 +794,41 @@ class NGP(nn.Module):
 
     def log_radiance_to_rgb(self, log_radiances, **kwargs):
         """HDR -> LDR with the per-channel tonemappers (models/networks_noCUDA.py:238-251; the
-        reference's CUDA model calls this without defining it, networks.py:238)."""
-        out = []
-        for i in range(3):
-            inp = log_radiances[:, i:i + 1]
-            if 'exposure' in kwargs:
-                inp = inp + torch.log(kwargs['exposure'])
-            out.append(getattr(self, f'tonemapper_net_{i}')(inp))
-        return torch.cat(out, 1)
+        reference's CUDA model calls this without defining it, networks.py:238).  With the constructor's tone-mappers
+        the three channels run as one launch each way (_ToneMapFn); `exposure` is absent, one value ((1,1) or 0-dim:
+        every sample's) or (n,1): one per sample, and takes no gradient."""
+        nets = self._stock_tonemappers()
+        if nets is None:   # tone-mappers put there from outside: composed module by module
+            out = []
+            for i in range(3):
+                inp = log_radiances[:, i:i + 1]
+                if 'exposure' in kwargs:
+                    inp = inp + torch.log(kwargs['exposure'])
+                out.append(getattr(self, f'tonemapper_net_{i}')(inp))
+            return torch.cat(out, 1)
+        if not log_radiances.is_cuda:
+            raise RuntimeError("log_radiances must be a CUDA tensor")
+        n = log_radiances.shape[0]
+        exposure = kwargs.get('exposure')
+        if exposure is not None:
+            if not exposure.is_cuda:
+                raise RuntimeError("exposure must be a CUDA tensor")
+            if exposure.requires_grad:
+                raise ValueError("exposure takes no gradient: the tone-mapper kernels have none for it")
+            if exposure.numel() not in (1, n):
+                raise ValueError(f"exposure holds one value or one per sample ({n}), got {tuple(exposure.shape)}")
+            exposure = exposure.detach().to(_f32).reshape(-1).contiguous()
+        return _ToneMapFn.apply(log_radiances.to(_f32).contiguous(), exposure, *[t.params for t in nets], self)
+
+    def _stock_tonemappers(self):
+        """the three networks as the constructor builds them (what ngp_tonemap_fwd / _bwd are written for), or None"""
+        nets = [getattr(self, f'tonemapper_net_{i}', None) for i in range(3)]
+        for t in nets:
+            if not (isinstance(t, tcnn.Network) and t.layer_shapes == [(64, 16), (16, 64)] and t.n_input_dims == 1
+                    and t.n_output_dims == 1 and t.activation == _RELU and t.output_activation == 2
+                    and t.params.is_contiguous()):
+                return None
+        return nets
 
     # ------------------------------------------------------------------ occupancy grid
     @torch.no_grad()

@@ -202,8 +202,18 @@ class NGPTrainer:
     def __init__(self, model, lr=1e-2, num_epochs=20, steps_per_epoch=1000, clip_norm=50.0,
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
-                 semantic=False, normal_mono=False, depth_mono=False, multi_terms=()):
-        """multi_terms: a non-empty subset of ('semantic', 'normal_mono', 'depth_mono'): those of NeRFLoss's optional terms
+                 semantic=False, normal_mono=False, depth_mono=False, multi_terms=(), use_exposure=False,
+                 unit_exposure_rgb=0.5):
+        """use_exposure: the reference's HDR-NeRF recipe (--use_exposure, train.py:99, 169-170, 301-306) for a model built with
+        rgb_act='None': step() then needs exposure= (the exposure time of every ray), which reaches the three tone-mappers
+        through render(), and the loss gains unit_exposure = 0.5 (tone(0, exposure=1) - unit_exposure_rgb)^2, its mean over
+        the three channels (unit_exposure_rgb: the dataset's, 0.73 synthetic / 0.5 real); results['loss_terms'] holds
+        [loss, rgb, opacity, distortion, unit_exposure] (on the NeRFLoss module's route, taken with an optional term in
+        loss_kwargs or a per-step target=, that term's means sit between distortion and unit_exposure).  The tone-mappers run on ngp_tonemap_fwd / ngp_tonemap_bwd, whose
+        backward adds straight into the flat gradient; the term touches only the tone-mapper parameters, whose squares are
+        always summed exactly, so the step's clip route is that of any tone-mapped model.  Combines with embedding_a and
+        random_bg; not with msk_model, pose_refiner or a skybox (and the fused-tail options refuse a tone-mapped model).
+        multi_terms: a non-empty subset of ('semantic', 'normal_mono', 'depth_mono'): those of NeRFLoss's optional terms
         TOGETHER on the fused render + loss tail (ngp_render_loss_fused_multi), as the reference's street-scene recipes use
         them.  Each term is the one its own flag below trains; step() then needs exactly the named terms' targets (labels=,
         normals=, depths=), and results['loss_terms'] holds the 8 terms [loss, rgb, opacity, distortion, CELoss, sky_depth,
@@ -289,6 +299,16 @@ class NGPTrainer:
             # gradient for dirs), a skybox (a function of rays_d) and second-order normals would leave it silently incomplete
             raise ValueError("pose refinement runs on the fused render + loss tail: a trainer with a pose_refiner takes no "
                              "optional loss term, no skybox and no differentiable normals")
+        self.use_exposure, self.unit_exposure_rgb = bool(use_exposure), float(unit_exposure_rgb)
+        if self.use_exposure:
+            if getattr(model, "rgb_act", "Sigmoid") != "None":
+                raise ValueError("use_exposure=True needs a model built with rgb_act='None' (log-radiance and the three "
+                                 f"tone-mappers): this one has rgb_act={getattr(model, 'rgb_act', 'Sigmoid')!r}")
+            why = [w for w, bad in (
+                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False))) if bad]
+            if why:
+                raise ValueError("use_exposure=True does not combine with " + ", ".join(why))
         self.semantic, self.normal_mono, self.depth_mono = bool(semantic), bool(normal_mono), bool(depth_mono)
         if isinstance(multi_terms, str):
             multi_terms = (multi_terms,)
@@ -414,6 +434,9 @@ class NGPTrainer:
                  "nrm_p": m.norm_pred_header.params, "sem_p": m.semantic_header.params}
         if self.embedding_a is not None:
             sinks["embedding_a"] = self.embedding_a.weight
+        tone = m._stock_tonemappers()
+        if tone:   # ngp_tonemap_bwd's sinks (networks._ToneMapFn); other tone-mappers keep autograd's route
+            sinks.update({f"tone_{i}": t.params for i, t in enumerate(tone)})
         link.grad_sinks = {name: p.grad for name, p in sinks.items()}
         if self.msk_model is not None:
             k, (l1, l2) = self.msk_model, (self.msk_model.mask_net[0], self.msk_model.mask_net[2])
@@ -474,6 +497,22 @@ class NGPTrainer:
             s = self._seed4 = torch.tensor([1.0] + [0.0] * (terms.numel() - 1), device=terms.device)
         return s
 
+    def _unit_exposure_rgb(self):
+        """the tone-mappers at zero log-radiance and unit exposure, (1, 3) with a graph to their parameters"""
+        z = getattr(self, '_unit_inputs', None)
+        if z is None or z[0].device != self.flat_param.device:
+            dev = self.flat_param.device
+            z = self._unit_inputs = (torch.zeros(1, 3, device=dev), torch.ones(1, 1, device=dev))
+        return self.model.log_radiance_to_rgb(z[0], exposure=z[1])
+
+    def _unit_exposure_term(self):
+        """-> (unit (1,3), the gradient of the term w.r.t. it, the term): mean over the channels of
+        0.5 (unit - unit_exposure_rgb)^2 (train.py:301-306), seeded directly as the default terms are"""
+        unit = self._unit_exposure_rgb()
+        with torch.no_grad():
+            diff = unit - self.unit_exposure_rgb
+            return unit, diff / 3.0, 0.5 * (diff * diff).mean()
+
     def _early_norm_share(self):
         if self._norm_share_armed and not self._bound_step:
             self._norm_share_fired += 1
@@ -491,8 +530,11 @@ class NGPTrainer:
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
     def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None, labels=None,
-             normals=None, depths=None, **loss_kwargs):
+             normals=None, depths=None, exposure=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
+
+        exposure: (n_rays) or (n_rays, 1) float exposure time of every ray in seconds, required by a trainer built with
+        use_exposure=True and refused by any other.
 
         A trainer built with multi_terms= needs exactly the named terms' targets among labels=, normals=, depths= (as
         described below), and takes no target= and no per-step loss term.
@@ -526,6 +568,18 @@ class NGPTrainer:
             raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
         if self.embedding_a is not None and img_idxs is None:
             raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
+        if getattr(self, "use_exposure", False):   # (getattr: as in _tail_terms, the host tests' stand-ins carry only some flags)
+            if exposure is None:
+                raise ValueError("this trainer was built with use_exposure=True: step() needs exposure= (the exposure time "
+                                 "of every ray)")
+            if not (torch.is_tensor(exposure) and exposure.is_floating_point() and exposure.numel() == rgb_gt.shape[0]
+                    and exposure.dim() in (1, 2)):
+                raise ValueError(f"exposure= must be ({rgb_gt.shape[0]},) or ({rgb_gt.shape[0]}, 1) float: got "
+                                 f"{tuple(exposure.shape) if torch.is_tensor(exposure) else type(exposure).__name__}")
+            if not exposure.is_cuda:
+                raise RuntimeError("exposure must be a CUDA tensor")
+        elif exposure is not None:
+            raise ValueError("exposure= is for a trainer built with use_exposure=True")
         tail_terms, packed, asked = _tail_terms(self)
         given = {"labels": labels, "normals": normals, "depths": depths}
         for name in MULTI_TERMS:
@@ -602,6 +656,8 @@ class NGPTrainer:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
             extra['_pose'] = (ref, img_idxs, pix_idxs)
+        if exposure is not None:
+            extra['exposure'] = exposure.detach().to(_f32).reshape(-1, 1)
         results = render(model, rays_o, rays_d, exp_step_factor=self.exp_step_factor,
                          num_classes=self.num_classes, marched=marched, **self.render_kwargs, **extra)
         if launch_next_late:
@@ -634,11 +690,19 @@ class NGPTrainer:
             terms, (d_rgb, d_op, d_ws) = nerf_loss_and_grads(
                 results["rgb"], results["opacity"], results["ws"], results["deltas"], results["ts"],
                 results["rays_a"], rgb_gt, self.loss_fn.lambda_opa, self.loss_fn.lambda_distortion)
-            loss = terms[0]
             outs, seeds = [results["rgb"], results["opacity"]], [d_rgb, d_op]
             if d_ws is not None:
                 outs.append(results["ws"])
                 seeds.append(d_ws)
+            if exposure is not None:
+                # train.py:301-306; seeded in the same backward call (one backward per step: _norm_share_armed)
+                unit, d_unit, term = self._unit_exposure_term()
+                terms = torch.cat([terms, term.reshape(1)])
+                terms[0] += term
+                results['loss_terms'] = terms
+                outs.append(unit)
+                seeds.append(d_unit)
+            loss = terms[0]
             torch.autograd.backward(outs, seeds)
         else:
             batch = {"rgb": rgb_gt}
@@ -648,7 +712,13 @@ class NGPTrainer:
             if masked:
                 kw.update(embed_msk=True, mask=mask, step=self.global_step)
             loss_d = self.loss_fn(results, batch, **kw)
+            if exposure is not None:
+                unit = self._unit_exposure_rgb()
+                loss_d['unit_exposure'] = 0.5 * (unit - self.unit_exposure_rgb) ** 2
             loss = sum(lo.mean() for lo in loss_d.values())
+            if exposure is not None:
+                # [loss, rgb, opacity, distortion, (the optional terms of loss_kwargs, in NeRFLoss's order,) unit_exposure]
+                results['loss_terms'] = torch.stack([loss.detach()] + [lo.detach().mean() for lo in loss_d.values()])
             loss.backward()
         self.optimizer_step()
         return loss.detach(), results

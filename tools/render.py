@@ -58,6 +58,11 @@ def parse_args(argv=None):
     ap.add_argument("--embed_a_mode", choices=("mean", "nearest", "index"), default="mean",
                     help="code of a frame: mean of the two training cameras nearest to the frame's pose, the nearest "
                          "one, or training image <frame number>; needs the train split's poses")
+    ap.add_argument("--use_exposure", action="store_true",
+                    help="the checkpoint was trained with --use_exposure (log-radiance and three tone-mappers): every frame "
+                         "is rendered at its test item's exposure time, or at --exposure")
+    ap.add_argument("--exposure", type=float, default=None, metavar="T",
+                    help="with --use_exposure: render every frame at T seconds instead of the items' own exposures")
     ap.add_argument("--aa_host_check", action="store_true",
                     help="with --anti_aliasing_factor and --render_rgb: also copy the fine 8-bit rgb frame to the host, "
                          "resize it with Pillow, require equality with the device result and report host_route_s")
@@ -69,6 +74,10 @@ def parse_args(argv=None):
                  "or --render_traj (the camera path's rays come from the loader at one ray per pixel)")
     if args.aa_host_check and not (args.anti_aliasing_factor > 1.0 and args.render_rgb):
         ap.error("--aa_host_check needs --anti_aliasing_factor above 1 and --render_rgb")
+    if args.exposure is not None and not args.use_exposure:
+        ap.error("--exposure needs --use_exposure")
+    if args.exposure is not None and not args.exposure > 0:
+        ap.error("--exposure must be positive (seconds)")
     if args.chunk_size <= 0:
         ap.error("--chunk_size must be positive")
     if not (args.render_rgb or args.render_depth or args.render_normal or args.render_semantic or args.render_points):
@@ -92,8 +101,10 @@ def main(argv=None):
     if args.dataset_name not in dataset_dict:
         raise SystemExit(f"unknown --dataset_name {args.dataset_name}; known: {sorted(dataset_dict)}")
     dev = torch.device("cuda", 0)
-    model = (NGP(scale=args.scale, classes=args.num_classes, embed_a=True, embed_a_len=args.embed_a_len) if args.embed_a
-             else NGP(scale=args.scale, classes=args.num_classes)).to(dev)
+    more = dict(embed_a=True, embed_a_len=args.embed_a_len) if args.embed_a else {}
+    if args.use_exposure:
+        more["rgb_act"] = "None"
+    model = NGP(scale=args.scale, classes=args.num_classes, **more).to(dev)
     ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model', 'density_grid', 'grid_coords'])
     test_set = dataset_dict[args.dataset_name](args.root_dir, "test", args.downsample, device=dev,
                                                render_traj=args.render_traj, num_classes=args.num_classes)
@@ -131,7 +142,15 @@ def main(argv=None):
         return time.perf_counter()
 
     for i in range(len(poses)):
-        gt = test_set[i]["rgb"].to(dev) if have_gt else None      # a split kept on the host is copied outside the stages
+        item = test_set[i] if have_gt else {}
+        gt = item["rgb"].to(dev) if have_gt else None      # a split kept on the host is copied outside the stages
+        if args.use_exposure:   # one exposure time per frame, every sample's
+            seconds = args.exposure
+            if seconds is None:
+                if "exposure" not in item:
+                    raise SystemExit(f"--use_exposure: frame {i} carries no exposure time; give --exposure T")
+                seconds = float(item["exposure"])
+            render_kwargs["exposure"] = torch.full((1, 1), float(seconds), device=dev)
         if frame_embed is not None:
             with torch.no_grad():
                 key = i % len(frame_embed.poses) if args.embed_a_mode == "index" else poses[i]

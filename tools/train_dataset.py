@@ -21,6 +21,8 @@ reference: train.py:82-392).  GPU only.
       --depth_mono --ckpt_path out/dep.ckpt   # depth_mono term on the proxy's depth maps (right up to scale and shift): held-out abs-rel
   python tools/train_dataset.py --make_proxy /tmp/proxy_all --dataset_name tnt --downsample 0.125 --num_epochs 2 \
       --multi_terms semantic normal_mono depth_mono --num_classes 5   # the three terms together on one fused tail
+  python tools/train_dataset.py --make_proxy /tmp/proxy_hdr --dataset_name colmap --downsample 0.1 --num_epochs 3 \
+      --steps_per_epoch 200 --use_exposure   # HDR-NeRF recipe on the multi-exposure proxy: held-out PSNR at unseen exposures
 """
 import argparse
 import json
@@ -45,8 +47,10 @@ from ngp_amd.rendering import MULTI_TERMS
 from ngp_amd.trainer import NGPTrainer
 
 
-def build_model(scale, device, embed_a=False, embed_a_len=4, num_classes=7):
+def build_model(scale, device, embed_a=False, embed_a_len=4, num_classes=7, use_exposure=False):
     more = dict(embed_a=True, embed_a_len=embed_a_len) if embed_a else {}
+    if use_exposure:   # log-radiance and the three tone-mappers (train.py:99)
+        more["rgb_act"] = "None"
     model = NGP(scale=scale, classes=num_classes, **more).to(device)
     G = model.grid_size
     model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=device))
@@ -81,7 +85,7 @@ def cameras_outside(train_set, scale):
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
           render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
           num_classes=7, normal_mono=False, lambda_normal_mono=None, depth_mono=False, lambda_depth_mono=None,
-          multi_terms=()):
+          multi_terms=(), use_exposure=False):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
@@ -92,7 +96,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     term's weight instead of NeRFLoss's 1); the trainer then carries `terms_log`, the loss terms of every step as device
     tensors (read after the run: nothing is read while it trains); multi_terms: the terms of --multi_terms, together on one
     tail (NGPTrainer(multi_terms=...)): the sampler feeds each named term as its own flag would, and `terms_log` holds the
-    8 terms of every step"""
+    8 terms of every step; use_exposure: the HDR-NeRF recipe of --use_exposure, fed with the sampler's exposure times and the
+    dataset's unit_exposure_rgb (`terms_log` then holds the 5 terms of every step)"""
     train_set.batch_size = batch_size
     multi_terms = tuple(multi_terms or ())
     if multi_terms and (semantic or normal_mono or depth_mono):
@@ -124,6 +129,11 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         more.update(pose_refiner=pose_refiner, pose_lr=pose_lr)
     if semantic or num_classes != 7:
         more.update(num_classes=num_classes)
+    if use_exposure:
+        if train_set.rays.shape[-1] != 4:
+            raise ValueError("--use_exposure needs an exposure time per ray: the dataset has none (the colmap loader reads "
+                             "them for the HDR-NeRF layouts)")
+        more.update(use_exposure=True, unit_exposure_rgb=train_set.unit_exposure_rgb)
     if multi_terms:
         more.update(multi_terms=multi_terms)
     else:
@@ -150,7 +160,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             uvi = None
             if msk_model is not None:
                 uvi = implicit_mask.uvi(s["uv"], s["img_idxs"], train_set.img_wh, n_imgs).to(idx.device)
-            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None, None, None
+            return None, None, s["rgb"].contiguous(), uvi, idx, s["pix_idxs"].to(torch.int64).contiguous(), None, None, None, None
         o, d = train_set.batch_rays(s)
         uvi = None
         if msk_model is not None:
@@ -161,7 +171,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         lab = s["label"].to(o.device, torch.int64).contiguous() if semantic else None
         nrm = s["normal"].to(o.device, torch.float32).contiguous() if normal_mono else None
         dep = s["depth"].to(o.device, torch.float32).reshape(-1).contiguous() if depth_mono else None
-        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab, nrm, dep
+        exp = s["exposure"].to(o.device, torch.float32).contiguous() if use_exposure else None
+        return o.contiguous(), d.contiguous(), s["rgb"].contiguous(), uvi, idx, None, lab, nrm, dep, exp
 
     import gc
     gc.collect()
@@ -180,9 +191,11 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             more["normals"] = cur[7]
         if cur[8] is not None:
             more["depths"] = cur[8]
+        if cur[9] is not None:
+            more["exposure"] = cur[9]
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
-        if depth_mono or multi_terms:
+        if depth_mono or multi_terms or use_exposure:
             trainer.terms_log.append(res["loss_terms"])
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
@@ -281,6 +294,12 @@ def parse_args(argv=None):
                          "(the reference's street-scene recipes set --render_semantic and --normal_mono together and add "
                          "depth_mono): each named term loads its maps and reports its metrics as its own flag does; the "
                          "JSON line gains loss_terms (8) and every optional term's mean over the first and last ten steps")
+    ap.add_argument("--use_exposure", action="store_true",
+                    help="the reference's HDR-NeRF recipe (--use_exposure): a model with rgb_act='None' and three tone-mappers, "
+                         "fed with the exposure time of every ray (the colmap loader reads them for the HDR-NeRF layouts) and "
+                         "regularised at unit exposure; the test split is rendered at each image's own exposure.  The JSON line "
+                         "gains unit_exposure_rgb_pred and the term's mean over the first and last ten steps.  With "
+                         "--make_proxy DIR --dataset_name colmap the multi-exposure proxy goes to DIR/HDR-NeRF/syndata/chair")
     ap.add_argument("--proxy_views", type=int, default=108, help="views of the scene --make_proxy writes")
     args = ap.parse_args(argv)
     args.multi_terms = tuple(t for t in MULTI_TERMS if t in args.multi_terms)
@@ -305,6 +324,13 @@ def parse_args(argv=None):
                  "--render_semantic")
     if not 1 <= args.num_classes <= 16:
         ap.error("--num_classes must lie in [1, 16]")
+    if args.use_exposure and (args.embed_msk or args.optimize_ext or args.multi_terms or args.render_semantic
+                              or args.normal_mono or args.depth_mono):
+        ap.error("--use_exposure combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext or a term on "
+                 "the fused tail (--render_semantic, --normal_mono, --depth_mono, --multi_terms)")
+    if args.make_proxy and args.use_exposure and args.dataset_name != "colmap":
+        ap.error("--make_proxy with --use_exposure writes the HDR-NeRF synthetic layout: --dataset_name colmap (the loader "
+                 "that reads it)")
     if args.make_proxy and args.render_semantic and args.dataset_name not in ("tnt", "colmap"):
         ap.error("--make_proxy with --render_semantic writes a labelled scene: --dataset_name tnt or colmap (the layouts "
                  "that carry semantic/*.pgm)")
@@ -376,6 +402,19 @@ def make_proxy_with_all_maps(root, scene, n_quad=256):
                              normals=normals, depths=depths)
 
 
+def make_hdr_proxy(root, scene, n_quad=256):
+    """the analytic proxy as an HDR-NeRF synthetic scene under <root>/HDR-NeRF/syndata/chair (the loader reads layout, split
+    and exposure table from the path): the scene's 35 views, taken as linear radiance, at three training and two held-out
+    exposures (export.export_hdr_nerf_syn) -> that directory"""
+    from ngp_amd.datasets import export
+    if scene.poses.shape[0] != 35:
+        raise ValueError(f"the synthetic HDR-NeRF split is fixed at 35 poses: the scene has {scene.poses.shape[0]}")
+    radiance = export.render_scene_views(scene, range(35), rgba=False, n_quad=n_quad)
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    return export.export_hdr_nerf_syn(os.path.join(root, "HDR-NeRF", "syndata", "chair"), radiance, c2w, K, scene="chair")
+
+
 def multi_terms_summary(terms_log, k=10):
     """{term: (mean over the first k steps, over the last k steps)} for terms[4:8] of train()'s terms_log"""
     t = torch.stack([v.detach() for v in terms_log]).cpu()
@@ -399,8 +438,12 @@ def main():
     if args.make_proxy:
         from ngp_amd.synthetic import LegoProxy
         wh = int(800 * args.downsample)
-        scene = LegoProxy(n_images=args.proxy_views, img_wh=(wh, wh), device=dev)
-        if args.multi_terms:
+        hdr = args.dataset_name == "colmap" and args.use_exposure
+        scene = LegoProxy(n_images=35 if hdr else args.proxy_views, img_wh=(wh, wh), device=dev)
+        if hdr:
+            root = make_hdr_proxy(args.make_proxy, scene)
+            args.downsample = 1.0
+        elif args.multi_terms:
             root = make_proxy_with_all_maps(args.make_proxy, scene)
             args.downsample = 1.0   # (these layouts are written at the size they are read at)
         elif args.render_semantic:
@@ -432,6 +475,10 @@ def main():
         raise SystemExit(f"{flag or '--normal_mono'}: {root} holds no normal maps (normal/*.npy) for the {args.dataset_name} loader")
     if with_dep and not hasattr(train_set, "depths_2d"):
         raise SystemExit(f"{flag or '--depth_mono'}: {root} holds no depth maps (depth/*.npy) for the {args.dataset_name} loader")
+    if args.use_exposure and train_set.rays.shape[-1] != 4:
+        print(f"--use_exposure: the {args.dataset_name} loader found no exposure times in {root} (the colmap loader reads "
+              "them for the HDR-NeRF layouts)", file=sys.stderr)
+        raise SystemExit(2)
     if with_sem:
         labels_of_split(train_set)
         if hasattr(test_set, "labels"):
@@ -442,7 +489,11 @@ def main():
                   f"{args.scale}): the sky term rewards depth on rays labelled 4 and puts density at the far end of the volume, "
                   "between the scene and the cameras opposite; held-out PSNR suffers.  Choose --scale so that the volume "
                   "encloses the cameras.", file=sys.stderr)
-    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len, args.num_classes)
+    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len, args.num_classes, args.use_exposure)
+    unit_pred0 = None
+    if args.use_exposure:
+        with torch.no_grad():
+            unit_pred0 = model.log_radiance_to_rgb(torch.zeros(1, 3, device=dev), exposure=torch.ones(1, 1, device=dev))
     msk_model = implicit_mask().to(dev) if args.embed_msk else None
     embedding_a = FrameEmbedding(args.embed_a_len, train_set.poses).to(dev) if args.embed_a else None
     pose_refiner = true_poses = None
@@ -455,7 +506,8 @@ def main():
           exp_step_factor=args.exp_step_factor, render_kwargs={"random_bg": True} if args.random_bg else None,
           msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
           semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono,
-                    depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono, multi_terms=args.multi_terms)
+                    depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono, multi_terms=args.multi_terms,
+                    use_exposure=args.use_exposure)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
@@ -485,6 +537,13 @@ def main():
         n_terms, first, last = terms_summary(trainer.terms_log)
         out.update(loss_terms=n_terms, depth_mono_term_first=first, depth_mono_term_last=last,
                    lambda_depth_mono=trainer.loss_fn.lambda_depth_mono)
+    if args.use_exposure:   # the test images were rendered at their own exposures (evaluate_split), never seen in training
+        with torch.no_grad():
+            unit = model.log_radiance_to_rgb(torch.zeros(1, 3, device=dev), exposure=torch.ones(1, 1, device=dev))
+        n_terms, first, last = terms_summary(trainer.terms_log)
+        out.update(use_exposure=True, loss_terms=n_terms, unit_exposure_rgb=train_set.unit_exposure_rgb,
+                   unit_exposure_rgb_init=unit_pred0[0].tolist(), unit_exposure_rgb_pred=unit[0].tolist(),
+                   unit_exposure_term_first=first, unit_exposure_term_last=last)
     if args.multi_terms:
         out.update(loss_terms=int(trainer.terms_log[0].numel()), multi_terms=list(args.multi_terms),
                    lambda_depth_mono=trainer.loss_fn.lambda_depth_mono)
