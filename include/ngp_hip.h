@@ -265,6 +265,20 @@ int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* d
                           float lambda_distortion, int64_t* total_samples, int64_t* vr_samples, float* opacity,
                           float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                           float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, void* stream);
+/* The same launch over a per-ray background (use_skybox, rendering.py:236-241 with rgb_bg = forward_skybox(rays_d)):
+ * rgb_bg is (n_rays_total, 3), indexed by the ray index of the row like target_rgb, and must not be NULL.  One more output,
+ * dL_drgb_bg (same shape): g_rgb (1 - opacity) with the ray's seed g_rgb = 2 (rgb - gt) / (3 R), written for every row of
+ * rays_a, a ray without samples included (opacity 0, rgb = bg, dL_drgb_bg = g_rgb); rows of rays that rays_a does not
+ * name are not touched.  Every other output is ngp_render_loss_fused's arithmetic: with every row of rgb_bg equal to one
+ * colour the per-ray and per-sample outputs are that entry's bit for bit.  terms (4), classes <= 8. */
+int ngp_render_loss_fused_sky(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, float T_threshold, int classes, int n_rays,
+                              float lambda_opacity, float lambda_distortion, int64_t* total_samples, int64_t* vr_samples,
+                              float* opacity, float* depth, float* rgb, float* normal_pred, float* sem, float* ws,
+                              float* loss_o, float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs,
+                              float* dL_drgb_bg, void* stream);
 /* The same launch for NeRFLoss(embed_msk=True) (losses.py:85-93, 142-151): mask (n_rays) is the transient mask m of
  * every ray.  Colour term mean((1 - m) e^2), its seed 2 (1 - m) e / (3 R) (the background's share of d_opacity uses it),
  * terms (5) = [loss, rgb, opacity, distortion, r_ms] with r_ms = size_delta mean(m^2) (the digit term has weight 0 in the
@@ -524,6 +538,32 @@ int64_t ngp_tonemap_bwd_workspace(int64_t n);
 int ngp_tonemap_bwd(const float* params0, const float* params1, const float* params2, const float* log_radiance,
                     const float* exposure, int exposure_stride, const float* dL_drgb, int64_t n, float* d_log_radiance,
                     float* dparams0, float* dparams1, float* dparams2, float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------
+ * S1  skybox (use_skybox: models/networks.py:128-148, 284-291; train.py:160): the background colour of a ray from its
+ * direction, SH degree 3 -> tcnn network 9 -> 32 (ReLU) -> 3 (Sigmoid), one launch each way.  Only the Sigmoid output
+ * activation is supported.  params: the network's 1024 floats in the tinycudann.Network layout, W1 (32,16) row-major,
+ * then W2 (16,32).  rays_d, rgb_bg, dL_drgb_bg (n_rays,3).  Per ray
+ *     u = d / |d| (forward_skybox's normalisation, no epsilon),  x = (u + 1) / 2,
+ *     y_0..8 = the degree-3 real SH basis of 2 x - 1 (ngp_sh_fwd's polynomial forms),
+ *     z_j = sum_{k<9} W1[j][k] y_k + sum_{k=9..15} W1[j][k]   (tcnn pads the 9 inputs to 16 columns with ones),
+ *     rgb_bg[c] = sigmoid(sum_j W2[c][j] relu(z_j)), c < 3     (rows 3..15 of W2 are unused).
+ * bwd: recomputes the hidden layer (nothing is saved but the inputs) and ACCUMULATES (+=, the caller zeroes) the
+ *   parameter gradients into dparams (the layout of params): columns 9..15 of a row of W1 all receive the same sum, rows
+ *   3..15 of W2 are not touched; the ReLU derivative is z_j > 0.  There is no gradient for rays_d.  A persistent grid keeps
+ *   every workgroup's 416 sums in registers across its tiles and stores them as doubles to `workspace`
+ *   (ngp_skybox_bwd_workspace(n) floats, host-only query, at most 2 * 416 * NGP_SKYBOX_BWD_MAX_BLOCKS, 8-byte aligned;
+ *   scratch: its contents need not be cleared or kept, but two calls that may overlap need one each); a second launch
+ *   adds them over the workgroups in a fixed order: no atomics, the same bits on every run.  Between their float32
+ *   inputs and outputs both directions work in double.
+ * n_rays == 0 returns NGP_OK before any pointer is looked at (nothing is launched, dparams is left alone); n_rays < 0
+ * is NGP_EINVAL.
+ * ---------------------------------------------------------------------- */
+#define NGP_SKYBOX_BWD_MAX_BLOCKS 256
+int ngp_skybox_fwd(const float* params, const float* rays_d, int64_t n_rays, float* rgb_bg, void* stream);
+int64_t ngp_skybox_bwd_workspace(int64_t n);
+int ngp_skybox_bwd(const float* params, const float* rays_d, const float* dL_drgb_bg, int64_t n_rays, float* dparams,
+                   float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
  * P1  camera pose refinement (optimize_ext: train.py:143-149, 225-230; datasets/ray_utils.py:50-104): the rays of a

@@ -27,6 +27,7 @@ SOURCES = [
     ("mask_kernels.hip", []),
     ("embed_kernels.hip", []),
     ("tonemap_kernels.hip", []),
+    ("sky_kernels.hip", []),
     ("pose_kernels.hip", ["-ffp-contract=off"]),    # at dR = dT = 0 the rays are bit-identical to get_rays' products
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),

@@ -600,6 +600,8 @@ struct RenderLossArgs {
     const float* dep_gt;
     int* dep_ws;
     float g_dm, dm_scale;
+    // SKY only (use_skybox): bg is (n_rays_total, 3), one background colour per ray, and the loss's gradient w.r.t. it
+    float* d_bg;
     // where the last workgroup puts the rounded normal_mono and depth_mono terms: terms[4] for the single entries,
     // terms[6] and terms[7] for ngp_render_loss_fused_multi (CELoss and sky_depth are terms[4], terms[5] in both)
     int slot_nm, slot_dm;
@@ -748,10 +750,14 @@ __global__ void __launch_bounds__(256) depth_fit_kernel(const float* __restrict_
     }
 }
 
-template <int CMAX, int W, bool MASKED, bool SEM, bool NRM, bool DEP>
+// SKY: the background is a colour per ray, bg[3 r + c] (the skybox's, rendering.py:236-241), and the launch also writes the
+// loss's gradient w.r.t. it, d_bg[r] = g_rgb (1 - opacity), for every row (a ray without samples: opacity 0, d_bg = g_rgb).
+// Everything else is the default form's arithmetic on bg0..2.
+template <int CMAX, int W, bool MASKED, bool SEM, bool NRM, bool DEP, bool SKY = false>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
     static_assert(!(MASKED && (SEM || NRM || DEP)), "MASKED x SEM, MASKED x NRM and MASKED x DEP are not built");
+    static_assert(!(SKY && (MASKED || SEM || NRM || DEP)), "SKY is built with the default terms only");
     constexpr int RPB = 256 / W;          // rays per block
     // one row of partials per active term behind the three of the default recipe: [ms] or [ce, sky][nm][dm]
     constexpr int ROW_SEM = 3, ROW_NRM = 3 + (SEM ? 2 : 0), ROW_DEP = ROW_NRM + (NRM ? 1 : 0);
@@ -859,8 +865,11 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
         // ---------------- loss terms and gradient seeds of the ray
         // the image colour: composited colour over the background (black when bg == NULL)
         float fR = aR, fG = aG, fB = aB, bg0 = 0.0f, bg1 = 0.0f, bg2 = 0.0f;
-        if (p.bg) {
-            bg0 = p.bg[0]; bg1 = p.bg[1]; bg2 = p.bg[2];
+        // (SKY: the ray's own colour; the entry has checked rgb_bg, and the test of the pointer stays so that this form's
+        // arithmetic is laid out, and contracted, exactly as the constant background's)
+        const float* bg = SKY ? p.bg + 3 * r : p.bg;
+        if (bg) {
+            bg0 = bg[0]; bg1 = bg[1]; bg2 = bg[2];
             const float rest = 1.0f - aO;
             fR = aR + bg0 * rest; fG = aG + bg1 * rest; fB = aB + bg2 * rest;
         }
@@ -949,6 +958,10 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 p.d_mask[r] = 2.0f * p.g_ms * mk - p.g_rgb * s_rgb;
                 s_rgb *= keep;
                 s_ms = mk * mk;
+            }
+            if (SKY) {
+                const float rest = 1.0f - aO;
+                p.d_bg[3 * r] = gR * rest; p.d_bg[3 * r + 1] = gG * rest; p.d_bg[3 * r + 2] = gB * rest;
             }
             if (SEM) { s_ce = ce; s_sky = sky; }
             if (NRM) s_nm = nm;
@@ -1405,6 +1418,7 @@ static RenderLossArgs tail_args(const float* sigmas, const float* rgbs, const fl
     a.labels = nullptr; a.sem_ws = nullptr; a.lam_sem = a.g_sky = 0.0f; a.d_sem = nullptr;
     a.nrm_gt = nullptr; a.nrm_ws = nullptr; a.g_nm = 0.0f; a.d_np = nullptr;
     a.dep_gt = nullptr; a.dep_ws = nullptr; a.g_dm = 0.0f; a.dm_scale = 1.0f;
+    a.d_bg = nullptr;
     a.slot_nm = a.slot_dm = 4;
     return a;
 }
@@ -1446,11 +1460,15 @@ static int tail_clear(float* terms, size_t n_terms, size_t vr_at, int64_t* vr_sa
     return NGP_OK;
 }
 
-// the 13 instantiations of the tail: the default and the masked one, and every non-empty set of the three optional terms,
-// those with the semantic term at 8 and at 16 classes
+// the 14 instantiations of the tail: the default, the masked and the per-ray-background (a.d_bg set) one, and every
+// non-empty set of the three optional terms, those with the semantic term at 8 and at 16 classes
 static int tail_launch(bool masked, int term_mask, int classes, int n_rays, hipStream_t st, const RenderLossArgs& a)
 {
     const dim3 grid = seg_grid(n_rays), block(256);
+    if (a.d_bg) {
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, false, true>), grid, block, 0, st, a);
+        return ngp_check_launch();
+    }
     // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
     // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
 #define NGP_TAIL(CM, M, S, N, D) hipLaunchKernelGGL((render_loss_fused_kernel<CM, 32, M, S, N, D>), grid, block, 0, st, a)
@@ -1497,6 +1515,27 @@ int ngp_render_loss_fused(const float* sigmas, const float* rgbs, const float* d
                   target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
                   vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
         nullptr, 0.0f, nullptr, stream);
+}
+
+int ngp_render_loss_fused_sky(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
+                              const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
+                              const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
+                              const float* target_rgb, const float* rgb_bg, float T_threshold, int classes, int n_rays,
+                              float lambda_opacity, float lambda_distortion, int64_t* total_samples, int64_t* vr_samples,
+                              float* opacity, float* depth, float* rgb, float* normal_pred, float* sem, float* ws,
+                              float* loss_o, float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs,
+                              float* dL_drgb_bg, void* stream)
+{
+    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
+                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
+                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
+                                 dL_dsigmas, dL_drgbs);
+    const int rc = tail_check(a, 0, 8, true, rgb_bg && dL_drgb_bg);
+    if (rc != TAIL_GO) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (tail_clear(a.terms, 4, 4, a.vr_samples, nullptr, 0, 0, st) != NGP_OK) return NGP_ELAUNCH;
+    a.d_bg = dL_drgb_bg;
+    return tail_launch(false, 0, a.classes, a.n_rays, st, a);
 }
 
 int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,

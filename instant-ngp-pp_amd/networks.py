@@ -571,6 +571,43 @@ class _ToneMapFn(Function):
         return (dx, None) + tuple(t if need else None for t, need in zip(out, ctx.needs_input_grad[2:5])) + (None,)
 
 
+_SKY_WS = {}
+
+
+def _sky_workspace(dev):
+    """ngp_skybox_bwd's scratch (the workgroups' partial sums: at most 256 x 416 doubles), one per device AND stream, as
+    _tone_workspace is and for its reason"""
+    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
+    if key not in _SKY_WS:
+        _SKY_WS[key] = torch.empty(call_host("skybox_bwd_workspace", 1 << 40), dtype=_f32, device=dev)
+    return _SKY_WS[key]
+
+
+class _SkyFn(Function):
+    """rgb_bg (n,3) = the skybox's colour of rays_d (n,3), one launch each way (ngp_skybox_fwd / ngp_skybox_bwd); rays_d
+    takes no gradient.  Parameter gradient: into the owner's `link.grad_sinks['sky']` (a trainer's flat gradient view,
+    autograd gets None, as _ToneMapFn does) or, without a sink, handed to autograd."""
+
+    @staticmethod
+    def forward(ctx, rays_d, params, owner):
+        n = rays_d.shape[0]
+        rgb_bg = torch.empty(n, 3, dtype=_f32, device=rays_d.device)
+        call("skybox_fwd", params, rays_d, n, rgb_bg)
+        ctx.save_for_backward(rays_d, params)
+        ctx.owner = owner
+        return rgb_bg
+
+    @staticmethod
+    def backward(ctx, g):
+        rays_d, params = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        sink = ctx.owner.link.grad_sinks.get("sky")
+        out = sink if sink is not None else torch.zeros_like(params)
+        call("skybox_bwd", params, rays_d, g.contiguous(), rays_d.shape[0], out, _sky_workspace(g.device))
+        return None, (None if sink is not None else out), None
+
+
 class NGP(nn.Module):
     def __init__(self, scale, rgb_act='Sigmoid', use_skybox=False, embed_a=False, embed_a_len=12, classes=7):
         super().__init__()
@@ -791,6 +828,27 @@ class NGP(nn.Module):
         d = d / torch.norm(d, dim=1, keepdim=True)
         d = self.skybox_dir_encoder((d + 1) / 2)
         return self.skybox_rgb_net(d)
+
+    def skybox_rgb(self, rays_d):
+        """forward_skybox(rays_d) as one launch each way (_SkyFn: ngp_skybox_fwd / ngp_skybox_bwd), what the fused training
+        tail composites over; rays_d takes no gradient.  forward_skybox stays the module-by-module route (the test-time
+        renderer's, and render(use_skybox=True)'s without a fused tail)."""
+        if not self._stock_skybox():
+            raise RuntimeError("skybox_rgb needs the skybox as the constructor builds it with rgb_act='Sigmoid' (SH degree 3 "
+                               "-> 32 -> 3, Sigmoid): the sky kernels are written for nothing else")
+        if not rays_d.is_cuda:
+            raise RuntimeError("rays_d must be a CUDA tensor")
+        # the sky parameters sit in the Adam sweep's first piece, as every MLP's do
+        self.link.join_params(rgb_table=False)
+        return _SkyFn.apply(rays_d.detach().to(_f32).contiguous(), self.skybox_rgb_net.params, self)
+
+    def _stock_skybox(self):
+        """the skybox as the constructor builds it for sigmoid colours (what ngp_skybox_fwd / _bwd are written for)"""
+        enc, net = getattr(self, 'skybox_dir_encoder', None), getattr(self, 'skybox_rgb_net', None)
+        return bool(self.use_skybox and isinstance(enc, tcnn.Encoding) and enc.otype == "SphericalHarmonics" and enc.n_output_dims == 9
+                    and isinstance(net, tcnn.Network) and net.layer_shapes == [(32, 16), (16, 32)] and net.n_input_dims == 9
+                    and net.n_output_dims == 3 and net.activation == _RELU and net.output_activation == 2
+                    and net.params.is_contiguous())
 
     def log_radiance_to_rgb(self, log_radiances, **kwargs):
         """HDR -> LDR with the per-channel tonemappers (models/networks_noCUDA.py:238-251; the

@@ -325,7 +325,7 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
             kwargs[k] = v.for_batch(rays_a)
     fused = kwargs.pop('_fused_loss', None)
     if fused is not None and _fused_tail_ok(model, kwargs, exp_step_factor, classes, fused):
-        return _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs)
+        return _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs, rays_d)
     sigmas, rgbs, normals_raw, normals_pred, sems = model(xyzs, dirs, **kwargs)
     results['sigma'] = sigmas
     results['xyzs'] = xyzs
@@ -356,10 +356,13 @@ def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
 
 def _fused_tail_ok(model, kwargs, exp_step_factor, classes, fused=None):
     """the one-launch render + loss tail covers the default recipe: sigmoid colours (no tone mapper), black or random
-    constant background (no skybox network), detached analytic normals, at most 8 classes (1 to 16 when `fused`, a
-    FusedTail, names the semantic term)"""
+    constant background (a skybox network only when `fused`, a FusedTail, says `sky`: ngp_render_loss_fused_sky), detached
+    analytic normals, at most 8 classes (1 to 16 when `fused` names the semantic term)"""
     sem = fused is not None and 'semantic' in fused.terms
-    return (getattr(model, 'rgb_act', 'Sigmoid') == 'Sigmoid' and not kwargs.get('use_skybox', False)
+    sky = bool(kwargs.get('use_skybox', False))
+    if sky and not (fused is not None and fused.sky and getattr(model, 'use_skybox', False)):
+        return False
+    return (getattr(model, 'rgb_act', 'Sigmoid') == 'Sigmoid'
             and not getattr(model, 'differentiable_normals', False) and (1 <= classes <= 16 if sem else classes <= 8)
             and hasattr(model, '_field'))
 
@@ -398,10 +401,15 @@ class FusedTail:
         lambda_nm), 'depth_mono': (depth_gt (n_rays) float32, lambda_dm, scene_scale)}, a non-empty subset.  packed=True
         takes exactly one term and selects that term's own entry with its packed terms (ngp_render_loss_fused_sem / _nrm /
         _dep); packed=False selects ngp_render_loss_fused_multi and its 8 terms.
+    sky=True (with neither): the background is a colour per ray, the skybox's (ngp_render_loss_fused_sky).  That entry has
+        the default entry's accumulator, so `entry` stays 'default'; `symbol` names what is called.
     `entry` is the key of TAIL_LAYOUT the combination selects."""
-    __slots__ = ('rgb_gt', 'lambda_opa', 'lambda_dist', 'mask', 'size_delta', 'terms', 'packed', 'entry')
+    __slots__ = ('rgb_gt', 'lambda_opa', 'lambda_dist', 'mask', 'size_delta', 'terms', 'packed', 'entry', 'sky')
 
-    def __init__(self, rgb_gt, lambda_opa, lambda_dist, mask=None, size_delta=0.0, terms=None, packed=False):
+    def __init__(self, rgb_gt, lambda_opa, lambda_dist, mask=None, size_delta=0.0, terms=None, packed=False, sky=False):
+        if sky and (mask is not None or terms is not None):
+            raise ValueError("the fused tail composites over a skybox with the default terms only: no mask, no optional terms")
+        self.sky = bool(sky)
         if terms is not None and (not terms or any(k not in MULTI_TERMS for k in terms)):
             raise ValueError(f"the multi tail takes a non-empty subset of {MULTI_TERMS}: got {tuple(terms)}")
         if mask is not None and terms is not None:
@@ -414,6 +422,13 @@ class FusedTail:
             self.entry = 'default' if mask is None else 'masked'
         else:
             self.entry = _PACKED_ENTRY[next(iter(terms))] if packed else 'multi'
+
+    @property
+    def symbol(self):
+        """the C entry behind ngp_: the TAIL_LAYOUT key's, or the per-ray-background twin of the default entry"""
+        if self.sky:
+            return "render_loss_fused_sky"
+        return "render_loss_fused" + ("" if self.entry == 'default' else "_" + self.entry)
 
 
 class _RenderLossFn(torch.autograd.Function):
@@ -437,7 +452,9 @@ class _RenderLossFn(torch.autograd.Function):
     forward returns (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, workspace): the workspace as int32
     (the labels' n_valid at int 0; the fit's scale, shift and n_valid at int 12, 13, 14 of the depth entry's and at int
     24, 25, 26 of the multi entry's), None where the entry has none.  Only terms is differentiable, and only through
-    terms[0] with a unit seed (NGPTrainer's use): backward hands the gradients computed in forward to the field."""
+    terms[0] with a unit seed (NGPTrainer's use): backward hands the gradients computed in forward to the field.
+    rgb_bg: None, one colour (3), or with tail.sky one colour per ray (n_rays_total, 3), indexed by rays_a's ray index: the
+        skybox's.  Only then does it get a gradient, g_rgb (1 - opacity) of its ray, from the same launch."""
 
     @staticmethod
     def forward(ctx, sig, rgb_o, sem_logits, np_raw, mask, dsig_dx, dirs, deltas, ts, rays_a, tail, scale3, T_thr, classes,
@@ -478,6 +495,14 @@ class _RenderLossFn(torch.autograd.Function):
         d_sem = E(n, classes) if labels is not None else None
         d_np = E(n, 3) if normals_gt is not None else None
         d_mask = E(nr) if mask is not None else None
+        d_bg = None
+        if tail.sky:
+            if rgb_bg is None or rgb_bg.dim() != 2 or rgb_bg.shape[1] != 3 or rgb_bg.shape[0] < nr or rgb_bg.dtype != f32:
+                raise ValueError(f"the sky tail takes a float32 background of at least ({nr}, 3), one row per ray: got "
+                                 f"{None if rgb_bg is None else tuple(rgb_bg.shape)}")
+            rgb_bg = rgb_bg.contiguous()
+            # the launch writes the row of every ray rays_a names; only a batch that leaves rays out needs the fill
+            d_bg = E(nr, 3) if rgb_bg.shape[0] == nr else torch.zeros_like(rgb_bg)
         lay = TAIL_LAYOUT[tail.entry]
         acc = E(lay.acc)
         terms, vr = acc[:lay.n_terms], acc[lay.vr_at:lay.vr_at + 2].view(torch.int64)
@@ -497,11 +522,13 @@ class _RenderLossFn(torch.autograd.Function):
             'dep': (dep_a, (wsp,)),
             'multi': ((bits,) + sem_a + nrm_a + dep_a, (wsp, d_sem, d_np)),
         }[tail.entry]
-        call("render_loss_fused" + ("" if tail.entry == 'default' else "_" + tail.entry), sig, rgb_o, dsig_dx, scale3, np_raw,
+        if tail.sky:
+            own_out = (d_bg,)
+        call(tail.symbol, sig, rgb_o, dsig_dx, scale3, np_raw,
              np_raw.stride(0), sem_logits, sem_logits.stride(0), dirs, deltas, ts, rays_a, tail.rgb_gt.contiguous(), rgb_bg,
              *own_in, float(T_thr), int(classes), nr, float(tail.lambda_opa), float(tail.lambda_dist), total, vr, opacity,
              depth, rgb, normal, sem, ws, Ro, Rp, terms, d_sig, d_rgb, *own_out)
-        ctx.save_for_backward(d_sig, d_rgb, d_sem, d_np, d_mask)
+        ctx.save_for_backward(d_sig, d_rgb, d_sem, d_np, d_mask, d_bg)
         ctx.pad_sem, ctx.pad_np = sem_logits.shape[1] - classes, np_raw.shape[1] - 3
         ctx.mask_shape = mask.shape if mask is not None else None
         ctx.set_materialize_grads(False)             # no zero-filled gradient tensors for the other outputs
@@ -510,21 +537,25 @@ class _RenderLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_terms, *_unused):
-        d_sig, d_rgb, d_sem, d_np, d_mask = ctx.saved_tensors
+        d_sig, d_rgb, d_sem, d_np, d_mask, d_bg = ctx.saved_tensors
         if d_sem is not None and ctx.pad_sem:
             d_sem = F.pad(d_sem, (0, ctx.pad_sem))
         if d_np is not None and ctx.pad_np:
             d_np = F.pad(d_np, (0, ctx.pad_np))
         if d_mask is not None:
             d_mask = d_mask.view(ctx.mask_shape)
-        return (d_sig, d_rgb, d_sem, d_np, d_mask) + (None,) * 10
+        return (d_sig, d_rgb, d_sem, d_np, d_mask) + (None,) * 9 + (d_bg,)
 
 
-def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs):
+def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs, rays_d=None):
     """fused: the FusedTail of render(..., _fused_loss=)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
     rgb_bg = None
-    if kwargs.get('exp_step_factor', 0.) != 0 and kwargs.get('random_bg', False):
+    if fused.sky:   # as in the reference, the skybox takes precedence over random_bg
+        if not kwargs.get('use_skybox', False):
+            raise ValueError("FusedTail(sky=True) goes with render(..., use_skybox=True)")
+        rgb_bg = model.skybox_rgb(rays_d)
+    elif kwargs.get('exp_step_factor', 0.) != 0 and kwargs.get('random_bg', False):
         rgb_bg = torch.rand(3, device=xyzs.device)      # rendering.py:239 (drawn at the same place in the RNG stream)
     (terms, total, vr, opacity, depth, rgb, normal, sem, ws, Ro, Rp, _) = _RenderLossFn.apply(
         sig, rgb_o, sem_logits, np_raw, fused.mask, dsig_dx, dirs.contiguous(), results['deltas'], results['ts'], rays_a, fused,

@@ -69,6 +69,21 @@ def analytic_rgb(x):
     return 0.5 + 0.5 * torch.sin(8 * math.pi * x)
 
 
+SKY_HORIZON, SKY_ZENITH, SKY_LOBE = (0.55, 0.50, 0.40), (0.10, 0.30, 0.70), (0.40, 0.25, 0.05)
+SKY_LOBE_DIR = (0.6, -0.48, 0.64)
+
+
+def analytic_sky(d):
+    """the colour of the background in direction d (N,3) (any length): a horizon-to-zenith gradient in the height of the
+    normalised direction plus a broad warm lobe around SKY_LOBE_DIR; inside [0.1, 0.95], the clamp never acts.  Smooth and of
+    low order in the direction (quadratic), so the skybox network (SH degree 3 -> 32 -> 3) can fit it."""
+    u = d / d.norm(dim=-1, keepdim=True).clamp(min=1e-12)
+    c = lambda v: torch.tensor(v, device=d.device, dtype=d.dtype)
+    up = 0.5 + 0.5 * u[..., 2:3]
+    lobe = (0.5 + 0.5 * (u * c(SKY_LOBE_DIR)).sum(-1, keepdim=True)) ** 2
+    return (c(SKY_HORIZON) + (c(SKY_ZENITH) - c(SKY_HORIZON)) * up + c(SKY_LOBE) * lobe).clamp(0.0, 1.0)
+
+
 class LegoProxy:
     def __init__(self, n_images=100, img_wh=(800, 800), device="cuda", seed=20220806, radius=1.5):
         self.device = torch.device(device)
@@ -110,8 +125,9 @@ class LegoProxy:
         return img, pix
 
     @torch.no_grad()
-    def ground_truth(self, rays_o, rays_d, n_quad=1024, white_bg=False):
-        """dense quadrature of the analytic field inside the unit box -> rgb (N,3), opacity (N)"""
+    def ground_truth(self, rays_o, rays_d, n_quad=1024, white_bg=False, sky=False):
+        """dense quadrature of the analytic field inside the unit box -> rgb (N,3), opacity (N); sky: composited over
+        analytic_sky(rays_d), a background that depends on the view direction (it takes precedence over white_bg)"""
         inv = 1.0 / rays_d
         a, b = (-0.5 - rays_o) * inv, (0.5 - rays_o) * inv
         t1 = torch.minimum(a, b).amax(-1).clamp(min=0)
@@ -134,7 +150,9 @@ class LegoProxy:
             w = alpha * T
             out_rgb[sl] = (w[..., None] * analytic_rgb(x)).sum(1)
             out_op[sl] = w.sum(1)
-        if white_bg:
+        if sky:
+            out_rgb = out_rgb + analytic_sky(rays_d) * (1 - out_op)[:, None]
+        elif white_bg:
             out_rgb = out_rgb + (1 - out_op)[:, None]
         return out_rgb, out_op
 

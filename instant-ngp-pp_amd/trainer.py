@@ -203,8 +203,18 @@ class NGPTrainer:
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
                  semantic=False, normal_mono=False, depth_mono=False, multi_terms=(), use_exposure=False,
-                 unit_exposure_rgb=0.5):
-        """use_exposure: the reference's HDR-NeRF recipe (--use_exposure, train.py:99, 169-170, 301-306) for a model built with
+                 unit_exposure_rgb=0.5, use_skybox=False):
+        """use_skybox: the reference's skybox recipe (--use_skybox, train.py:160) for a model built with use_skybox=True
+        and sigmoid colours, on fused kernels: from global_step >= warmup_steps on (the reference's schedule) the step
+        passes use_skybox to render(), the skybox's colours come from ngp_skybox_fwd (networks._SkyFn), the tail composites
+        over them per ray (ngp_render_loss_fused_sky) and hands the background's gradient to ngp_skybox_bwd, which adds
+        straight into the flat gradient.  Before that the step is the default recipe (with random_bg if set) and the sky
+        parameters get a zero gradient.  As in the reference the skybox takes precedence over random_bg.  step() then takes
+        no target= and no per-step loss term.  Combines with embedding_a and random_bg; not with msk_model, pose_refiner,
+        semantic / normal_mono / depth_mono / multi_terms, use_exposure or a tone-mapped model, differentiable normals or an
+        optional term in loss_kwargs.  render_kwargs={'use_skybox': True} (without this flag) remains the
+        launch-per-operation route, from step 0.
+        use_exposure: the reference's HDR-NeRF recipe (--use_exposure, train.py:99, 169-170, 301-306) for a model built with
         rgb_act='None': step() then needs exposure= (the exposure time of every ray), which reaches the three tone-mappers
         through render(), and the loss gains unit_exposure = 0.5 (tone(0, exposure=1) - unit_exposure_rgb)^2, its mean over
         the three channels (unit_exposure_rgb: the dataset's, 0.73 synthetic / 0.5 real); results['loss_terms'] holds
@@ -337,6 +347,21 @@ class NGPTrainer:
                  "semantic" in named and head != int(num_classes))) if bad]
             if why:
                 raise ValueError(f"{asked[-1]} runs on the fused render + loss tail, which does not take " + ", ".join(why))
+        self.use_skybox = bool(use_skybox)
+        if self.use_skybox:
+            if not getattr(model, "use_skybox", False):
+                raise ValueError("use_skybox=True needs a model built with use_skybox=True (skybox_dir_encoder and "
+                                 "skybox_rgb_net)")
+            why = asked + [w for w, bad in (
+                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                ("use_exposure=True", self.use_exposure),
+                ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                ("an optional term in loss_kwargs", optional),
+                ("differentiable normals", getattr(model, "differentiable_normals", False)),
+                ("render_kwargs['use_skybox'] (the launch-per-operation route: name one of the two)",
+                 "use_skybox" in self.render_kwargs)) if bad]
+            if why:
+                raise ValueError("use_skybox=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -437,6 +462,8 @@ class NGPTrainer:
         tone = m._stock_tonemappers()
         if tone:   # ngp_tonemap_bwd's sinks (networks._ToneMapFn); other tone-mappers keep autograd's route
             sinks.update({f"tone_{i}": t.params for i, t in enumerate(tone)})
+        if getattr(m, "_stock_skybox", None) and m._stock_skybox():   # ngp_skybox_bwd's sink (networks._SkyFn)
+            sinks["sky"] = m.skybox_rgb_net.params
         link.grad_sinks = {name: p.grad for name, p in sinks.items()}
         if self.msk_model is not None:
             k, (l1, l2) = self.msk_model, (self.msk_model.mask_net[0], self.msk_model.mask_net[2])
@@ -529,9 +556,17 @@ class NGPTrainer:
     def lr(self):
         return self.lr_at(min(self.global_step // self.steps_per_epoch, self.num_epochs))
 
+    def sky_active(self):
+        """whether the step about to be taken composites over the skybox: a trainer built with use_skybox=True, from
+        global_step >= warmup_steps on (train.py:160)"""
+        return bool(getattr(self, "use_skybox", False) and self.global_step >= self.warmup_steps)
+
     def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None, labels=None,
              normals=None, depths=None, exposure=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
+
+        A trainer built with use_skybox=True takes no target= and no per-step loss term; the skybox joins the step from
+        global_step >= warmup_steps on.
 
         exposure: (n_rays) or (n_rays, 1) float exposure time of every ray in seconds, required by a trainer built with
         use_exposure=True and refused by any other.
@@ -599,6 +634,14 @@ class NGPTrainer:
                                  "takes no target= and no per-step loss term")
             if not rays_o.is_cuda:
                 raise RuntimeError(f"{asked} needs CUDA tensors: the fused tail has no other route")
+        sky = getattr(self, "use_skybox", False)   # (getattr: the host tests' stand-ins carry only some flags)
+        if sky:
+            if target or loss_kwargs:
+                raise ValueError("this trainer was built with use_skybox=True: the step stays on the fused render + loss tail "
+                                 "and takes no target= and no per-step loss term")
+            if not rays_o.is_cuda:
+                raise RuntimeError("use_skybox=True needs CUDA tensors: the fused tail has no other route")
+        sky_on = NGPTrainer.sky_active(self)
         ref = self.pose_refiner
         if ref is not None:
             if rays_o is not None or rays_d is not None or next_rays is not None:
@@ -646,7 +689,7 @@ class NGPTrainer:
                 # size_delta of the step being taken (losses.py:60-69, 85)
                 size_delta=self.loss_fn.Annealing.getWeight(self.global_step) if masked else 0.0,
                 terms={n: _TAIL_TERMS[n].entry(self, given[_TAIL_TERMS[n].arg], rays_o.device) for n in tail_terms} or None,
-                packed=packed)
+                packed=packed, sky=sky_on)
             if tail_terms and not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes,
                                                  extra['_fused_loss']):
                 # (rgb_act or differentiable_normals changed after construction, ...): never a step without the targets
@@ -658,6 +701,8 @@ class NGPTrainer:
             extra['_pose'] = (ref, img_idxs, pix_idxs)
         if exposure is not None:
             extra['exposure'] = exposure.detach().to(_f32).reshape(-1, 1)
+        if sky_on:
+            extra['use_skybox'] = True
         results = render(model, rays_o, rays_d, exp_step_factor=self.exp_step_factor,
                          num_classes=self.num_classes, marched=marched, **self.render_kwargs, **extra)
         if launch_next_late:
@@ -666,7 +711,9 @@ class NGPTrainer:
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
         # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
         # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the
-        # start; the depth_mono term only changes d_sigmas, which the density head's backward notes: the bound holds)
+        # start; the depth_mono term only changes d_sigmas, which the density head's backward notes: the bound holds; the
+        # skybox adds nothing to a table gradient and its own parameters lie behind _mlp_lo, where squares are always
+        # summed exactly: the bound holds)
         self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
                                 and not any(_TAIL_TERMS[n].exact_norm for n in tail_terms))
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
@@ -678,6 +725,9 @@ class NGPTrainer:
             # (rgb_act / differentiable_normals changed after construction, a model without _field, ...)
             raise RuntimeError(f"{asked}: render() did not take the fused tail (rendering._fused_tail_ok); the targets would "
                                "be left out of the loss")
+        if sky_on and '_loss_terms' not in results:
+            raise RuntimeError("use_skybox=True: render() did not take the fused tail (rendering._fused_tail_ok); the step "
+                               "would run without its skybox kernels")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]

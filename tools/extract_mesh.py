@@ -48,6 +48,9 @@ def main(argv=None):
     ap.add_argument("--embed_a", action="store_true",
                     help="the checkpoint was trained with appearance codes (--embed_a): --colors renders with the code of training image 0")
     ap.add_argument("--embed_a_len", type=int, default=4, help="length of an appearance code")
+    ap.add_argument("--use_skybox", action="store_true",
+                    help="the checkpoint was trained with --use_skybox: the model is built with the skybox so that it loads "
+                         "(the mesh and its colours do not look at the background)")
     ap.add_argument("--chunk", type=int, default=128 ** 3)
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
@@ -55,7 +58,7 @@ def main(argv=None):
     res = args.resolution[0] if len(args.resolution) == 1 else tuple(args.resolution)
 
     dev = torch.device("cuda", 0)
-    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len)
+    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len, use_skybox=args.use_skybox)
     ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model'])
     more = {}
     if args.embed_a:

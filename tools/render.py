@@ -63,6 +63,9 @@ def parse_args(argv=None):
                          "is rendered at its test item's exposure time, or at --exposure")
     ap.add_argument("--exposure", type=float, default=None, metavar="T",
                     help="with --use_exposure: render every frame at T seconds instead of the items' own exposures")
+    ap.add_argument("--use_skybox", action="store_true",
+                    help="the checkpoint was trained with --use_skybox (skybox_dir_encoder and skybox_rgb_net): every frame is "
+                         "rendered over the skybox's colour of its rays")
     ap.add_argument("--aa_host_check", action="store_true",
                     help="with --anti_aliasing_factor and --render_rgb: also copy the fine 8-bit rgb frame to the host, "
                          "resize it with Pillow, require equality with the device result and report host_route_s")
@@ -76,6 +79,8 @@ def parse_args(argv=None):
         ap.error("--aa_host_check needs --anti_aliasing_factor above 1 and --render_rgb")
     if args.exposure is not None and not args.use_exposure:
         ap.error("--exposure needs --use_exposure")
+    if args.use_skybox and args.use_exposure:
+        ap.error("--use_skybox does not go with --use_exposure (no recipe trains both)")
     if args.exposure is not None and not args.exposure > 0:
         ap.error("--exposure must be positive (seconds)")
     if args.chunk_size <= 0:
@@ -104,6 +109,8 @@ def main(argv=None):
     more = dict(embed_a=True, embed_a_len=args.embed_a_len) if args.embed_a else {}
     if args.use_exposure:
         more["rgb_act"] = "None"
+    if args.use_skybox:
+        more["use_skybox"] = True
     model = NGP(scale=args.scale, classes=args.num_classes, **more).to(dev)
     ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model', 'density_grid', 'grid_coords'])
     test_set = dataset_dict[args.dataset_name](args.root_dir, "test", args.downsample, device=dev,
@@ -136,6 +143,8 @@ def main(argv=None):
     host_route_s = 0.0
     psnrs, ssims, points = [], [], []
     render_kwargs = {"exp_step_factor": args.exp_step_factor, "num_classes": args.num_classes}
+    if args.use_skybox:
+        render_kwargs["use_skybox"] = True
 
     def tick():
         torch.cuda.synchronize()

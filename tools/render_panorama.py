@@ -46,6 +46,9 @@ def parse_args(argv=None):
     ap.add_argument("--embed_a", action="store_true",
                     help="the checkpoint was trained with appearance codes (--embed_a): the panorama is rendered with the code of training image 0")
     ap.add_argument("--embed_a_len", type=int, default=4, help="length of an appearance code")
+    ap.add_argument("--use_skybox", action="store_true",
+                    help="the checkpoint was trained with --use_skybox: the panorama is rendered over the skybox's colour of "
+                         "its rays (mask.png still marks the pixels without opacity)")
     ap.add_argument("--render_depth", action="store_true", help="also write depth.png (Turbo of depth / (2 * scale))")
     ap.epilog = ("mask.png is 255 where the opacity BYTE is 0 and 0 elsewhere: the reference compares the uint8 opacity "
                  "image with 0.5 (render_panorama.py:126-133), so only fully transparent pixels are marked.")
@@ -70,8 +73,10 @@ def main(argv=None):
     from ngp_amd.networks import NGP
 
     dev = torch.device("cuda", 0)
-    model = (NGP(scale=args.scale, classes=args.num_classes, embed_a=True, embed_a_len=args.embed_a_len) if args.embed_a
-             else NGP(scale=args.scale, classes=args.num_classes)).to(dev)
+    build = dict(embed_a=True, embed_a_len=args.embed_a_len) if args.embed_a else {}
+    if args.use_skybox:
+        build["use_skybox"] = True
+    model = NGP(scale=args.scale, classes=args.num_classes, **build).to(dev)
     ckpt.load_ckpt(model, args.ckpt, prefixes_to_ignore=['embedding_a', 'msk_model', 'density_grid', 'grid_coords'])
     more = {}
     if args.embed_a:   # render_panorama.py:80-85 of the reference: the code of training image 0
@@ -79,6 +84,8 @@ def main(argv=None):
         if table.dim() != 2 or table.shape[1] != args.embed_a_len:
             raise SystemExit(f"--embed_a_len {args.embed_a_len}: the checkpoint's table is {tuple(table.shape)}")
         more["embedding_a"] = table[0:1].to(dev).float().contiguous()
+    if args.use_skybox:
+        more["use_skybox"] = True
     H, W = args.pano_hw
     aa = args.anti_aliasing_factor
     fine_h, fine_w = supersampled_size(H, W, aa) if aa > 1.0 else (H, W)

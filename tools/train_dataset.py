@@ -23,6 +23,9 @@ reference: train.py:82-392).  GPU only.
       --multi_terms semantic normal_mono depth_mono --num_classes 5   # the three terms together on one fused tail
   python tools/train_dataset.py --make_proxy /tmp/proxy_hdr --dataset_name colmap --downsample 0.1 --num_epochs 3 \
       --steps_per_epoch 200 --use_exposure   # HDR-NeRF recipe on the multi-exposure proxy: held-out PSNR at unseen exposures
+  python tools/train_dataset.py --make_proxy /tmp/proxy_sky --dataset_name tnt --downsample 0.125 --num_epochs 3 \
+      --steps_per_epoch 200 --use_skybox --ckpt_path out/sky.ckpt   # skybox recipe on the proxy over the analytic sky: held-out
+      # PSNR, and test_sky_psnr over the held-out pixels that see only sky
 """
 import argparse
 import json
@@ -47,8 +50,10 @@ from ngp_amd.rendering import MULTI_TERMS
 from ngp_amd.trainer import NGPTrainer
 
 
-def build_model(scale, device, embed_a=False, embed_a_len=4, num_classes=7, use_exposure=False):
+def build_model(scale, device, embed_a=False, embed_a_len=4, num_classes=7, use_exposure=False, use_skybox=False):
     more = dict(embed_a=True, embed_a_len=embed_a_len) if embed_a else {}
+    if use_skybox:   # skybox_dir_encoder and skybox_rgb_net (train.py:97)
+        more["use_skybox"] = True
     if use_exposure:   # log-radiance and the three tone-mappers (train.py:99)
         more["rgb_act"] = "None"
     model = NGP(scale=scale, classes=num_classes, **more).to(device)
@@ -85,7 +90,7 @@ def cameras_outside(train_set, scale):
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
           render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
           num_classes=7, normal_mono=False, lambda_normal_mono=None, depth_mono=False, lambda_depth_mono=None,
-          multi_terms=(), use_exposure=False):
+          multi_terms=(), use_exposure=False, use_skybox=False):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
@@ -97,7 +102,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     tensors (read after the run: nothing is read while it trains); multi_terms: the terms of --multi_terms, together on one
     tail (NGPTrainer(multi_terms=...)): the sampler feeds each named term as its own flag would, and `terms_log` holds the
     8 terms of every step; use_exposure: the HDR-NeRF recipe of --use_exposure, fed with the sampler's exposure times and the
-    dataset's unit_exposure_rgb (`terms_log` then holds the 5 terms of every step)"""
+    dataset's unit_exposure_rgb (`terms_log` then holds the 5 terms of every step); use_skybox: the skybox recipe of
+    --use_skybox (NGPTrainer(use_skybox=True): the skybox joins from the end of the warm-up on)"""
     train_set.batch_size = batch_size
     multi_terms = tuple(multi_terms or ())
     if multi_terms and (semantic or normal_mono or depth_mono):
@@ -134,6 +140,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             raise ValueError("--use_exposure needs an exposure time per ray: the dataset has none (the colmap loader reads "
                              "them for the HDR-NeRF layouts)")
         more.update(use_exposure=True, unit_exposure_rgb=train_set.unit_exposure_rgb)
+    if use_skybox:
+        more.update(use_skybox=True)
     if multi_terms:
         more.update(multi_terms=multi_terms)
     else:
@@ -300,6 +308,12 @@ def parse_args(argv=None):
                          "regularised at unit exposure; the test split is rendered at each image's own exposure.  The JSON line "
                          "gains unit_exposure_rgb_pred and the term's mean over the first and last ten steps.  With "
                          "--make_proxy DIR --dataset_name colmap the multi-exposure proxy goes to DIR/HDR-NeRF/syndata/chair")
+    ap.add_argument("--use_skybox", action="store_true",
+                    help="the reference's skybox recipe (--use_skybox): a model with the skybox network, which colours the "
+                         "background by view direction from the end of the warm-up on; the test split is rendered with it.  With "
+                         "--make_proxy DIR --dataset_name tnt the proxy is written over the analytic sky, with the opacity of "
+                         "every pixel in opacity/*.npy.  Whenever the scene directory has those, the JSON line gains "
+                         "test_sky_psnr, the PSNR over the held-out pixels whose opacity is below 0.01")
     ap.add_argument("--proxy_views", type=int, default=108, help="views of the scene --make_proxy writes")
     args = ap.parse_args(argv)
     args.multi_terms = tuple(t for t in MULTI_TERMS if t in args.multi_terms)
@@ -328,6 +342,13 @@ def parse_args(argv=None):
                               or args.normal_mono or args.depth_mono):
         ap.error("--use_exposure combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext or a term on "
                  "the fused tail (--render_semantic, --normal_mono, --depth_mono, --multi_terms)")
+    if args.use_skybox and (args.embed_msk or args.optimize_ext or args.multi_terms or args.render_semantic
+                            or args.normal_mono or args.depth_mono or args.use_exposure):
+        ap.error("--use_skybox combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext, --use_exposure or "
+                 "a term on the fused tail (--render_semantic, --normal_mono, --depth_mono, --multi_terms)")
+    if args.make_proxy and args.use_skybox and args.dataset_name != "tnt":
+        ap.error("--make_proxy with --use_skybox writes the scene over the analytic sky: --dataset_name tnt (the layout "
+                 "whose images carry their background)")
     if args.make_proxy and args.use_exposure and args.dataset_name != "colmap":
         ap.error("--make_proxy with --use_exposure writes the HDR-NeRF synthetic layout: --dataset_name colmap (the loader "
                  "that reads it)")
@@ -415,6 +436,63 @@ def make_hdr_proxy(root, scene, n_quad=256):
     return export.export_hdr_nerf_syn(os.path.join(root, "HDR-NeRF", "syndata", "chair"), radiance, c2w, K, scene="chair")
 
 
+def make_sky_proxy(root, scene, n_quad=256):
+    """the analytic proxy composited over synthetic.analytic_sky (a background that depends on the view direction) in
+    the tnt layout, every 8th view held out, with the scene's opacity of every pixel in opacity/<stem>.npy (float32, h x w)"""
+    from ngp_amd.datasets import export
+    n = scene.poses.shape[0]
+    w, h = scene.img_wh
+    pix = torch.arange(w * h, device=scene.device)
+    images, opacities = [], []
+    for i in range(n):
+        o, d = scene.rays(torch.full((w * h,), i, dtype=torch.long, device=scene.device), pix)
+        rgb, opacity = scene.ground_truth(o, d, n_quad=n_quad, sky=True)
+        images.append((rgb.clamp(0, 1).reshape(h, w, 3).cpu().numpy() * 255.0 + 0.5).astype(np.uint8))
+        opacities.append(opacity.reshape(h, w).cpu().numpy().astype(np.float32))
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    split_of = [1 if i % 8 == 0 else 0 for i in range(n)]
+    export.export_tnt(root, np.stack(images), c2w, K, split_of)
+    os.makedirs(os.path.join(root, "opacity"), exist_ok=True)
+    for i in range(n):
+        np.save(os.path.join(root, "opacity", f"{split_of[i]}_{i:08d}.npy"), opacities[i])
+    return root
+
+
+def opacity_maps(test_set, root):
+    """the opacity map of every image of the split from <root>/opacity/<image stem>.npy (make_sky_proxy writes them), as
+    (n_images, h*w) float32 on the split's device, or None when the scene has none or they do not fit the images"""
+    paths = [os.path.join(root, "opacity", os.path.splitext(os.path.basename(p))[0] + ".npy") for p in getattr(test_set, "imgs", [])]
+    if not paths or not all(os.path.exists(p) for p in paths):
+        return None
+    maps = np.stack([np.load(p).reshape(-1) for p in paths]).astype(np.float32)
+    w, h = test_set.img_wh
+    return torch.from_numpy(maps).to(test_set.rays.device) if maps.shape[1] == w * h else None
+
+
+class SkyPsnr:
+    """on_image callback of evaluate_split: the squared error over the pixels whose ground-truth opacity is below
+    `below`, pooled over the split (on the device: one read-back, in value())"""
+
+    def __init__(self, test_set, opacity, below=0.01, then=None):
+        self.gt, self.sky, self.then = test_set.rays, opacity < below, then
+        self.sq = torch.zeros((), dtype=torch.float64, device=opacity.device)
+        self.n = torch.zeros((), dtype=torch.float64, device=opacity.device)
+
+    def __call__(self, i, rgb, results):
+        m = self.sky[i].to(rgb.device)
+        err = (rgb - self.gt[i][..., :3].to(rgb.device)) ** 2
+        self.sq += err[m].sum().double().to(self.sq.device)
+        self.n += 3.0 * m.sum().double().to(self.n.device)
+        if self.then is not None:
+            self.then(i, rgb, results)
+
+    def value(self):
+        """(PSNR in dB, number of pixels); (None, 0) without a sky pixel"""
+        n = float(self.n)
+        return (float(-10.0 * torch.log10(self.sq / self.n)), int(n / 3)) if n else (None, 0)
+
+
 def multi_terms_summary(terms_log, k=10):
     """{term: (mean over the first k steps, over the last k steps)} for terms[4:8] of train()'s terms_log"""
     t = torch.stack([v.detach() for v in terms_log]).cpu()
@@ -455,6 +533,9 @@ def main():
         elif args.depth_mono:
             root = make_proxy_with_depths(args.make_proxy, scene)
             args.downsample = 1.0
+        elif args.use_skybox:
+            root = make_sky_proxy(args.make_proxy, scene)
+            args.downsample = 1.0
         else:
             root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
     loader = dataset_dict[args.dataset_name]
@@ -489,7 +570,7 @@ def main():
                   f"{args.scale}): the sky term rewards depth on rays labelled 4 and puts density at the far end of the volume, "
                   "between the scene and the cameras opposite; held-out PSNR suffers.  Choose --scale so that the volume "
                   "encloses the cameras.", file=sys.stderr)
-    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len, args.num_classes, args.use_exposure)
+    model = build_model(args.scale, dev, args.embed_a, args.embed_a_len, args.num_classes, args.use_exposure, args.use_skybox)
     unit_pred0 = None
     if args.use_exposure:
         with torch.no_grad():
@@ -507,7 +588,7 @@ def main():
           msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
           semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono,
                     depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono, multi_terms=args.multi_terms,
-                    use_exposure=args.use_exposure)
+                    use_exposure=args.use_exposure, use_skybox=args.use_skybox)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
@@ -515,8 +596,14 @@ def main():
         more["embedding_a"] = embedding_a(0).detach()
     if with_sem or args.num_classes != 7:
         more["num_classes"] = args.num_classes
-    res = evaluate_split(model, test_set, on_image=_save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None,
-                         exp_step_factor=args.exp_step_factor, **more)
+    if args.use_skybox:   # the held-out images are rendered over the skybox (render(test_time=True, use_skybox=True))
+        more["use_skybox"] = True
+    on_image = _save_rgb(args.save_dir, test_set.img_wh) if args.save_dir else None
+    opacity = opacity_maps(test_set, root)
+    sky_psnr = None
+    if opacity is not None:
+        on_image = sky_psnr = SkyPsnr(test_set, opacity, then=on_image)
+    res = evaluate_split(model, test_set, on_image=on_image, exp_step_factor=args.exp_step_factor, **more)
     psnrs, ssims = res["psnr"], res["ssim"]
     if args.ckpt_path:
         ckpt.save_ckpt(model, args.ckpt_path, msk_model=msk_model, pose_refiner=pose_refiner,
@@ -524,6 +611,10 @@ def main():
     out = {"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
            "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
            "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}
+    if args.use_skybox:
+        out["use_skybox"] = True
+    if sky_psnr is not None:   # over the held-out pixels that see only background
+        out["test_sky_psnr"], out["test_sky_pixels"] = sky_psnr.value()
     if "sem_acc" in res:
         acc, miou = semantic_summary(res)   # accuracy over all valid pixels; images without a valid label take no part
         out.update(test_sem_acc_mean=acc, test_sem_acc=res["sem_acc"], test_sem_miou_mean=miou,
