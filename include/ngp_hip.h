@@ -407,6 +407,23 @@ int ngp_neg_normalize(const float* x, int64_t ldx, const float* scale3 /* device
                       float* y, void* stream);
 int ngp_neg_normalize_bwd(const float* x, int64_t ldx, const float* dL_dy, int64_t n, float* dL_dx,
                           void* stream);
+/* NeRFLoss(normal_ref=True)'s two terms behind ANY ngp_render_loss_fused* entry, which has left ws (0 behind a ray's
+ * early stop), loss_o (Ro) and loss_p (Rp).  RefLoss composites with detached sigmas, so ws is a constant here and
+ *     L = lambda_rp mean(Rp) + lambda_ro mean(Ro),   the means over 3 R and R values, R = n_rays (the rows of rays_a),
+ * has per-sample gradients.  With n_raw = -normalize(dsigma_dx * scale3), n_pred = -normalize(normal_head) (eps 1e-6),
+ * d = normalize(dirs), e = n_raw - n_pred, dot = max(<n_raw, d>, 0), G_p = lambda_rp ws / (3 R), G_o = lambda_ro ws / R:
+ *     dL/dn_raw = 2 e G_p + 2 dot d G_o,   dL/dn_pred = -2 e G_p,
+ * each taken through the backward of -normalize exactly as ngp_neg_normalize_bwd does it (a row of norm <= eps: -g 1e6);
+ * scale3 (device (3) or NULL) is applied on the dsigma_dx side, so dL_dgrads (N,3) is w.r.t. dsigma_dx itself.
+ * dL_dnormal_head (N,3) is written, or added to when add_to_normal_head != 0 (the tail's normal_mono gradient is there).
+ * ref_terms (2) = [lambda_rp mean(Rp), lambda_ro mean(Ro)], the per-ray values summed in a fixed order (doubles).
+ * 32 lanes per rays_a row; samples and rays that rays_a does not name are not touched.  Runs on the tail's stream,
+ * behind the tail.  n_rays == 0 returns NGP_OK before any pointer is looked at; n_rays < 0, ld_normal_head < 3 or a NULL
+ * pointer other than scale3 is NGP_EINVAL. */
+int ngp_normal_ref_tail(const float* dsigma_dx, const float* scale3, const float* normal_head, int64_t ld_normal_head,
+                        const float* dirs, const float* ws, const int64_t* rays_a, int n_rays, const float* loss_o,
+                        const float* loss_p, float lambda_rp, float lambda_ro, int add_to_normal_head, float* dL_dgrads,
+                        float* dL_dnormal_head, float* ref_terms, void* stream);
 
 /* ------------------------------------------------------------------------
  * R4  torch_scatter.segment_csr(src, indptr) with sum reduction
@@ -474,6 +491,31 @@ int ngp_density_field_fwd(const ngp_grid_desc* desc, const float* table, const f
 int ngp_grid_bwd_bwd_input(const ngp_grid_desc* desc, const float* table, const float* x,
                            const float* dL_dy, int64_t lddy, const float* dL_ddLdx, int64_t n,
                            float* dtable, float* dL_ddLdy, void* stream);
+
+/* D2  second-order backward of the density head 128 -> 128 softplus -> 1 softplus: the element-wise pass of the route
+ * loss(normals_raw) -> d(sigma)/dx -> density table and xyz_net (normal_ref), between products that other entries form.
+ * With s1 = sigmoid(z1) = 1 - exp(-a1), s2 = sigmoid(z2) = 1 - exp(-sig), w2 = W2[0] and g = d_sig (NULL = 0), the
+ * first order is  dfeat = m W1,  m = s2 (w2 * s1)  (what ngp_density_field_fwd leaves).  A gradient v on
+ * grads = d(sigma)/dx becomes u = dL/d(dfeat) in ngp_grid_bwd_bwd_input, and r = u W1^T (n,128) in ngp_linear_fwd.
+ * Per row this entry forms
+ *     q = sum_h r_h w2_h s1_h,   e2 = q s2 (1 - s2) + g s2            (= dL/dz2, the first-order share included)
+ *     m_h  = s2 w2_h s1_h                                              (dW1 += m^T u)
+ *     e1_h = s1_h w2_h (e2 + r_h s2 (1 - s1_h))                        (= dL/dz1: dW1 += e1^T feat, db1 += sum e1,
+ *                                                                        dL/dfeat = e1 W1)
+ * writes m (n,128) and e1 (n,128) (e1 may be r itself) and ACCUMULATES (+=) dW2 (128) += sum_rows (e2 a1 + s2 r * s1),
+ * db2 (1) += sum_rows e2.  1 - exp(-y) is evaluated as -expm1(-y) and 1 - s as exp(-y): both keep their digits at y = 1e-6
+ * and at y = 30.  A persistent grid of at most NGP_DENSITY_BWD2_MAX_BLOCKS workgroups takes tiles of NGP_DENSITY_BWD2_ROWS
+ * rows; a workgroup keeps its 129 sums in registers (doubles) across its tiles and stores them to `workspace`
+ * (ngp_density_head_bwd2_workspace(n) floats, host-only query, 8-byte aligned; scratch: its contents need not be
+ * cleared or kept, but two calls that may overlap need one each); a second launch adds them over the workgroups in a
+ * fixed order: no atomics, the same bits on every run.
+ * a1, r, m, e1 are contiguous and 16-byte aligned.  n == 0 returns NGP_OK before any pointer is looked at; n < 0, a NULL
+ * pointer other than d_sig or a misaligned one is NGP_EINVAL, without a launch. */
+#define NGP_DENSITY_BWD2_ROWS 8
+#define NGP_DENSITY_BWD2_MAX_BLOCKS 1024
+int64_t ngp_density_head_bwd2_workspace(int64_t n);
+int ngp_density_head_bwd2(const float* a1, const float* sig, const float* r, const float* W2, const float* d_sig, int64_t n,
+                          float* m, float* e1, float* dW2, float* db2, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
  * M1  transient mask field (models/implicit_mask.py): tcnn Grid/Hash encoding L = 8, F = 2 (desc must say so) of

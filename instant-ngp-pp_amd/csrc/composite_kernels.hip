@@ -1238,6 +1238,85 @@ __global__ void neg_normalize_bwd_kernel(const float* __restrict__ x, int64_t ld
     }
 }
 
+// backward of y = -x / max(|x|, eps) for one row, neg_normalize_bwd_kernel's arithmetic (the <= eps branch included)
+__device__ __forceinline__ void neg_normalize_bwd_row(float a, float b, float c, float ga, float gb, float gc, float& da,
+                                                      float& db, float& dc)
+{
+    const float nrm = sqrtf(a * a + b * b + c * c);
+    if (nrm > 1e-6f) {
+        const float inv = 1.0f / nrm;
+        const float ua = a * inv, ub = b * inv, uc = c * inv;
+        const float dot = ua * ga + ub * gb + uc * gc;
+        da = -(ga - ua * dot) * inv; db = -(gb - ub * dot) * inv; dc = -(gc - uc * dot) * inv;
+    } else {
+        da = -ga * 1e6f; db = -gb * 1e6f; dc = -gc * 1e6f;
+    }
+}
+
+// The Ro / Rp terms of NeRFLoss(normal_ref=True) behind a fused tail: the tail has left ws (RefLoss composites with
+// detached sigmas: its weights are constants here), so the gradients of lambda_rp mean(Rp) + lambda_ro mean(Ro) w.r.t.
+// d(sigma)/dx and the normal head's raw output are per-sample expressions.  32 lanes per rays_a row.
+__global__ void normal_ref_tail_kernel(const float* __restrict__ dsig_dx, const float* __restrict__ scale3,
+                                       const float* __restrict__ np_raw, int64_t ld_np, const float* __restrict__ dirs,
+                                       const float* __restrict__ ws, const int64_t* __restrict__ rays_a, int n_rays,
+                                       float g_rp, float g_ro, int add_head, float* __restrict__ d_grads,
+                                       float* __restrict__ d_np)
+{
+    Seg sg; int lane;
+    if (!seg_load(rays_a, n_rays, sg, lane)) return;
+    const float sc0 = scale3 ? scale3[0] : 1.0f, sc1 = scale3 ? scale3[1] : 1.0f, sc2 = scale3 ? scale3[2] : 1.0f;
+    for (int k = lane; k < sg.n; k += 32) {
+        const int64_t s = sg.start + k;
+        const float w = ws[s];
+        const float Gp = g_rp * w, Go = g_ro * w;
+        // normals_raw = -normalize(d sigma/dx * scale3), normals_pred = -normalize(head), eps 1e-6: the tail's own forms
+        const float xx = dsig_dx[3 * s] * sc0, xy = dsig_dx[3 * s + 1] * sc1, xz = dsig_dx[3 * s + 2] * sc2;
+        float inv = -1.0f / fmaxf(sqrtf(xx * xx + xy * xy + xz * xz), 1e-6f);
+        const float gx = xx * inv, gy = xy * inv, gz = xz * inv;
+        const float px = np_raw[s * ld_np], py = np_raw[s * ld_np + 1], pz = np_raw[s * ld_np + 2];
+        inv = -1.0f / fmaxf(sqrtf(px * px + py * py + pz * pz), 1e-6f);
+        const float hx = px * inv, hy = py * inv, hz = pz * inv;
+        const float ex = gx - hx, ey = gy - hy, ez = gz - hz;
+        float dx = dirs[3 * s], dy = dirs[3 * s + 1], dz = dirs[3 * s + 2];
+        const float dinv = 1.0f / fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-6f);
+        dx *= dinv; dy *= dinv; dz *= dinv;
+        const float dot = fmaxf(gx * dx + gy * dy + gz * dz, 0.0f);
+        const float tp = 2.0f * Gp, to = 2.0f * dot * Go;
+        const float rx = ex * tp + dx * to, ry = ey * tp + dy * to, rz = ez * tp + dz * to;   // dL/d normals_raw
+        float ax, ay, az;
+        neg_normalize_bwd_row(xx, xy, xz, rx, ry, rz, ax, ay, az);
+        d_grads[3 * s] = ax * sc0; d_grads[3 * s + 1] = ay * sc1; d_grads[3 * s + 2] = az * sc2;
+        neg_normalize_bwd_row(px, py, pz, -ex * tp, -ey * tp, -ez * tp, ax, ay, az);         // dL/d normals_pred = -2 e G_p
+        if (add_head) { d_np[3 * s] += ax; d_np[3 * s + 1] += ay; d_np[3 * s + 2] += az; }
+        else { d_np[3 * s] = ax; d_np[3 * s + 1] = ay; d_np[3 * s + 2] = az; }
+    }
+}
+
+// ref_terms = [lambda_rp mean(Rp), lambda_ro mean(Ro)] over the rays rays_a names (3 n_rays and n_rays values): one
+// workgroup, a lane takes every 256th row in order, then a tree over the lanes: the same bits on every run
+__global__ void __launch_bounds__(256) normal_ref_terms_kernel(const int64_t* __restrict__ rays_a, int n_rays,
+                                                               const float* __restrict__ loss_o, const float* __restrict__ loss_p,
+                                                               float lambda_rp, float lambda_ro, float* __restrict__ ref_terms)
+{
+    __shared__ double sp[256], so[256];
+    double p = 0.0, o = 0.0;
+    for (int i = threadIdx.x; i < n_rays; i += 256) {
+        const size_t r = (size_t)rays_a[3 * (size_t)i];
+        p += ((double)loss_p[3 * r] + (double)loss_p[3 * r + 1]) + (double)loss_p[3 * r + 2];
+        o += (double)loss_o[r];
+    }
+    sp[threadIdx.x] = p; so[threadIdx.x] = o;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) { sp[threadIdx.x] += sp[threadIdx.x + h]; so[threadIdx.x] += so[threadIdx.x + h]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ref_terms[0] = (float)((double)lambda_rp * sp[0] / (3.0 * (double)n_rays));
+        ref_terms[1] = (float)((double)lambda_ro * so[0] / (double)n_rays);
+    }
+}
+
 inline dim3 seg_grid(int n_rays) { return dim3(ngp_blocks((int64_t)n_rays * 32, 256)); }
 
 } // namespace
@@ -1701,6 +1780,25 @@ int ngp_neg_normalize_bwd(const float* x, int64_t ldx, const float* dL_dy, int64
     if (!x || !dL_dy || !dL_dx) return NGP_EINVAL;
     hipLaunchKernelGGL(neg_normalize_bwd_kernel, dim3(ngp_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, x, ldx,
                        dL_dy, n, dL_dx);
+    return ngp_check_launch();
+}
+
+int ngp_normal_ref_tail(const float* dsigma_dx, const float* scale3, const float* normal_head, int64_t ld_normal_head,
+                        const float* dirs, const float* ws, const int64_t* rays_a, int n_rays, const float* loss_o,
+                        const float* loss_p, float lambda_rp, float lambda_ro, int add_to_normal_head, float* dL_dgrads,
+                        float* dL_dnormal_head, float* ref_terms, void* stream)
+{
+    if (n_rays < 0 || ld_normal_head < 3) return NGP_EINVAL;
+    if (n_rays == 0) return NGP_OK;
+    if (!dsigma_dx || !normal_head || !dirs || !ws || !rays_a || !loss_o || !loss_p || !dL_dgrads || !dL_dnormal_head ||
+        !ref_terms)
+        return NGP_EINVAL;
+    hipLaunchKernelGGL(normal_ref_tail_kernel, seg_grid(n_rays), dim3(256), 0, (hipStream_t)stream, dsigma_dx, scale3,
+                       normal_head, ld_normal_head, dirs, ws, rays_a, n_rays, lambda_rp / (3.0f * (float)n_rays),
+                       lambda_ro / (float)n_rays, add_to_normal_head, dL_dgrads, dL_dnormal_head);
+    if (ngp_check_launch() != NGP_OK) return NGP_ELAUNCH;
+    hipLaunchKernelGGL(normal_ref_terms_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rays_a, n_rays, loss_o, loss_p,
+                       lambda_rp, lambda_ro, ref_terms);
     return ngp_check_launch();
 }
 

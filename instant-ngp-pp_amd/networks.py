@@ -14,6 +14,9 @@ Differences, all deliberate:
     result is detached, i.e. normals_raw carries no gradient — which is what every recipe without
     --normal_ref needs.  Setting `model.differentiable_normals = True` switches forward() to the
     reference's own formulation, with the grid double backward (H4) on ngp_grid_bwd_bwd_input.
+    `model.second_order_normals = True` keeps the fused node instead and makes its d(sigma)/dx differentiable: the second
+    order then runs on ngp_grid_bwd_bwd_input, ngp_density_head_bwd2 and four existing products (what
+    NGPTrainer(normal_ref=True) trains through).
 """
 import numpy as np
 import torch
@@ -182,6 +185,8 @@ class _NegNormalize(Function):
         call("neg_normalize", x, 3, scale3, x.shape[0], y)
         if scale3 is None:
             ctx.save_for_backward(x)
+        elif ctx.needs_input_grad[0]:   # (second-order normals: d(sigma)/dx carries a graph)
+            ctx.save_for_backward(x, scale3)
         ctx.set_materialize_grads(False)
         return y
 
@@ -189,10 +194,12 @@ class _NegNormalize(Function):
     def backward(ctx, g):
         if g is None:
             return None, None
-        (x,) = ctx.saved_tensors
+        x, *scale3 = ctx.saved_tensors
+        if scale3:   # the chain rule around the scaling: the kernel differentiates -normalize at x * scale3
+            x = x * scale3[0]
         dx = torch.empty_like(x)
         call("neg_normalize_bwd", x, 3, g.contiguous(), x.shape[0], dx)
-        return dx, None
+        return (dx * scale3[0] if scale3 else dx), None
 
 
 def _density_fused_ok(enc, W1, b1, W2, b2):
@@ -220,7 +227,10 @@ class _FieldFn(Function):
     """
 
     @staticmethod
-    def forward(ctx, model, x, d, embed_a, xyz_table, W1, b1, W2, b2, rgb_table, rgb_p, nrm_p, sem_p, ray_codes=None):
+    def forward(ctx, model, x, d, embed_a, xyz_table, W1, b1, W2, b2, rgb_table, rgb_p, nrm_p, sem_p, ray_codes=None,
+                second_order=False):
+        # second_order: d(sigma)/dxn is a differentiable output (NGP.second_order_normals): a gradient on it reaches the
+        # density table and xyz_net through ngp_grid_bwd_bwd_input and ngp_density_head_bwd2 in backward
         # ray_codes = (img_idxs (n_rays) i64, rays_a (n_rays, 3) i64) of appearance.RayCodes: embed_a is then the
         # (n_imgs, E) embedding TABLE, broadcast per sample by ngp_embed_a_fwd and summed back by ngp_embed_a_bwd
         n = x.shape[0]
@@ -255,7 +265,16 @@ class _FieldFn(Function):
         def colour_branch():
             # [SH(16) | rgb grid features (128) | appearance code (E) | ones-padding] -> rgb_net, the two heads
             feat_rgb = rgb_in[:, 16:144]
-            call("sh_fwd_dirs", d, n, 4, rgb_in, Kp)
+            if second_order:
+                # The module route's own direction encoding, op for op (F.normalize, the [0,1] remap, ngp_sh_fwd), so that
+                # both normal_ref routes hand rgb_net the same bits.  ngp_sh_fwd_dirs multiplies by a rounded reciprocal
+                # and fuses the remap's add: 14 % of its basis values differ from these by up to 4e-7, which is enough to
+                # move a ReLU pre-activation that lies within 1e-8 of zero across it and with it one sample's whole term of
+                # dW1 (the reference's normal_ref step, G10, has such a sample: 5.5e-5 of rgb_net's gradient)
+                dn = F.normalize(d, p=2, dim=-1, eps=1e-6)
+                call("sh_fwd", ((dn + 1) / 2).contiguous(), n, 4, rgb_in, Kp)
+            else:
+                call("sh_fwd_dirs", d, n, 4, rgb_in, Kp)
             if ev_c is not None:
                 ev_c.wait()   # the colour table's piece (the stream this runs on waits for it)
             call("grid_fwd", re.desc, rgb_table, xn, n, rgb_in[:, 16:], Kp)
@@ -343,12 +362,14 @@ class _FieldFn(Function):
         ctx.save_for_backward(xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
                               xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dfeat,
                               *((d,) if ctx.needs_input_grad[2] else ()))
-        ctx.mark_non_differentiable(grads)
+        if not second_order:
+            ctx.mark_non_differentiable(grads)
         ctx.set_materialize_grads(False)
         return sig[:, 0], rgb_o, grads, np_o, sem_o
 
     @staticmethod
-    def backward(ctx, d_sig, d_rgb, _d_grads, d_np, d_sem):
+    def backward(ctx, d_sig, d_rgb, v, d_np, d_sem):
+        # v = dL/d(d sigma/dxn) (n,3): only a node built with second_order=True can receive one
         (xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
          xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dsig_dfeat) = ctx.saved_tensors[:19]
         model = ctx.model
@@ -398,8 +419,11 @@ class _FieldFn(Function):
             buf = torch.zeros_like(table)
             return buf, buf
 
+        if v is not None and need[1]:
+            raise RuntimeError("second-order normals with sample positions that require a gradient (pose refinement): the "
+                               "field's second order has no dL/dx")
         reuse = d_sig is not None and not need[1]
-        if reuse and need[4]:
+        if reuse and need[4] and v is None:
             d_sig_c = d_sig.contiguous()
             buf, g_xyz = table_buffer(xe, xyz_table)
 
@@ -490,7 +514,31 @@ class _FieldFn(Function):
             st.weight_products()
 
         # ---- density head
-        if d_sig is not None:
+        if v is not None:
+            # Both orders in one pass (include/ngp_hip.h, D2): v becomes u = dL/d(dfeat) and the table's second-order share
+            # in the grid's double backward, r = u W1^T, and ngp_density_head_bwd2 leaves m (dW1 += m^T u), e1 = dL/dz1 with
+            # the first-order share of d_sig inside it (dW1 += e1^T feat, db1, dL/dfeat = e1 W1) and dW2 / db2.  The
+            # d_sig-scaled scatter and the first-order weight products are not run: each share lands once.
+            link.bound_spoiled()    # the norm bound is not shown to hold for these contributions
+            (acc_W1, g_W1), (acc_W2, g_W2) = grad_buffer("W1", W1), grad_buffer("W2", W2)
+            (acc_b1, g_b1), (acc_b2, g_b2) = grad_buffer("b1", (128,)), grad_buffer("b2", (1,))
+            buf = None
+            if need[4]:
+                buf, g_xyz = table_buffer(xe, xyz_table)
+            u = torch.empty(n, 128, dtype=_f32, device=dev)
+            call("grid_bwd_bwd_input", xe.desc, xyz_table, xn, dsig_dfeat, 128, v.contiguous(), n, buf, u)
+            r = torch.empty(n, 128, dtype=_f32, device=dev)
+            call("linear_fwd", u, 128, W1, 128, None, n, 128, 128, _NONE, r, 128, None)
+            m = torch.empty(n, 128, dtype=_f32, device=dev)
+            call("density_head_bwd2", a1, sig, r, W2, None if d_sig is None else d_sig.contiguous(), n, m, r, acc_W2, acc_b2,
+                 _head2_workspace(dev))
+            call("linear_bwd_weight", m, 128, u, 128, n, 128, 128, acc_W1, 128, None)
+            call("linear_bwd_weight", r, 128, feat, 128, n, 128, 128, acc_W1, 128, acc_b1)      # (r holds e1 now)
+            if buf is not None:
+                call("linear_bwd_input", r, 128, W1, 128, n, 128, 128, m, 128, 0)               # (m is free: dL/dfeat)
+                call("grid_bwd_param", xe.desc, xn, m, 128, n, buf)
+                xe.grad_ready()
+        elif d_sig is not None:
             (acc_W1, g_W1), (acc_W2, g_W2) = grad_buffer("W1", W1), grad_buffer("W2", W2)
             (acc_b1, g_b1), (acc_b2, g_b2) = grad_buffer("b1", (128,)), grad_buffer("b2", (1,))
             nb_acc = link.norm_acc
@@ -519,7 +567,19 @@ class _FieldFn(Function):
             g_x = g_x / span
         if forked:
             main.wait_stream(side)
-        return (None, g_x, g_d, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None)
+        return (None, g_x, g_d, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None, None)
+
+
+_HEAD2_WS = {}
+
+
+def _head2_workspace(dev):
+    """ngp_density_head_bwd2's scratch (the workgroups' partial sums: at most 1024 x 129 doubles), one per device AND
+    stream, as _tone_workspace is and for its reason"""
+    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
+    if key not in _HEAD2_WS:
+        _HEAD2_WS[key] = torch.empty(call_host("density_head_bwd2_workspace", 1 << 40), dtype=_f32, device=dev)
+    return _HEAD2_WS[key]
 
 
 _TONE_WS = {}
@@ -618,6 +678,9 @@ class NGP(nn.Module):
         self.link = FieldLink()               # what a trainer and the field's autograd node agree on (link.py)
         self.grid_rng = None                  # set from outside: a shared-seed generator keeps DDP ranks' grids identical
         self.differentiable_normals = False   # True: forward() takes the reference's own formulation (module docstring)
+        # True: with grad enabled the fused field node hands out d(sigma)/dx WITH a graph (second order on ngp_grid_bwd_bwd_input
+        # and ngp_density_head_bwd2), so normals_raw reaches the density table and xyz_net; NGPTrainer(normal_ref=True) sets it
+        self.second_order_normals = False
         self.register_buffer('center', torch.zeros(1, 3))
         self.register_buffer('xyz_min', -torch.ones(1, 3) * scale)
         self.register_buffer('xyz_max', torch.ones(1, 3) * scale)
@@ -735,10 +798,20 @@ class NGP(nn.Module):
                     embed_a = torch.repeat_interleave(embed_a, int(x.size(0) / embed_a.size(0)), 0)
                 embed_a = embed_a.contiguous()
         lin1, lin2 = self.xyz_net[0], self.xyz_net[2]
+        second = bool(self.second_order_normals and torch.is_grad_enabled())
+        if second:
+            if not (x.is_cuda and _density_fused_ok(self.xyz_encoder, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
+                    and lin1.bias is not None and lin2.bias is not None):
+                raise RuntimeError("second_order_normals needs the density path ngp_density_field_fwd takes (a 16-level F = 8 "
+                                   "table and the 128 -> 128 -> 1 head with biases, contiguous, on the GPU): "
+                                   "differentiable_normals = True is the route for any other field")
+            if x.requires_grad:
+                raise RuntimeError("second_order_normals with sample positions that require a gradient (pose refinement): "
+                                   "the field's second order has no dL/dx")
         return _FieldFn.apply(self, x.contiguous(), d.contiguous(), embed_a,
                               self.xyz_encoder.params, lin1.weight, lin1.bias, lin2.weight, lin2.bias,
                               self.rgb_encoder.params, self.rgb_net.params, self.norm_pred_header.params,
-                              self.semantic_header.params, ray_codes)
+                              self.semantic_header.params, ray_codes, second)
 
     def grad(self, x):
         """-> sigmas (N), feat_rgb (N,128), d(sigma)/dx (N,3) (detached, see module docstring).

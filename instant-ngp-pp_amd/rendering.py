@@ -403,12 +403,19 @@ class FusedTail:
         _dep); packed=False selects ngp_render_loss_fused_multi and its 8 terms.
     sky=True (with neither): the background is a colour per ray, the skybox's (ngp_render_loss_fused_sky).  That entry has
         the default entry's accumulator, so `entry` stays 'default'; `symbol` names what is called.
+    normal_ref=(lambda_rp, lambda_ro): NeRFLoss's normal_ref terms behind the entry, whichever it is without a mask or a
+        skybox (_NormalRefFn: ngp_normal_ref_tail on the entry's ws, Ro and Rp); the model then hands out d(sigma)/dx with a
+        graph (NGP.second_order_normals).  The entry and its terms stay what they are; the two terms come beside them.
     `entry` is the key of TAIL_LAYOUT the combination selects."""
-    __slots__ = ('rgb_gt', 'lambda_opa', 'lambda_dist', 'mask', 'size_delta', 'terms', 'packed', 'entry', 'sky')
+    __slots__ = ('rgb_gt', 'lambda_opa', 'lambda_dist', 'mask', 'size_delta', 'terms', 'packed', 'entry', 'sky', 'normal_ref')
 
-    def __init__(self, rgb_gt, lambda_opa, lambda_dist, mask=None, size_delta=0.0, terms=None, packed=False, sky=False):
+    def __init__(self, rgb_gt, lambda_opa, lambda_dist, mask=None, size_delta=0.0, terms=None, packed=False, sky=False,
+                 normal_ref=None):
         if sky and (mask is not None or terms is not None):
             raise ValueError("the fused tail composites over a skybox with the default terms only: no mask, no optional terms")
+        if normal_ref is not None and (sky or mask is not None):
+            raise ValueError("normal_ref goes behind the default, the packed and the multi entries: no mask, no skybox")
+        self.normal_ref = None if normal_ref is None else (float(normal_ref[0]), float(normal_ref[1]))
         self.sky = bool(sky)
         if terms is not None and (not terms or any(k not in MULTI_TERMS for k in terms)):
             raise ValueError(f"the multi tail takes a non-empty subset of {MULTI_TERMS}: got {tuple(terms)}")
@@ -547,9 +554,49 @@ class _RenderLossFn(torch.autograd.Function):
         return (d_sig, d_rgb, d_sem, d_np, d_mask) + (None,) * 9 + (d_bg,)
 
 
+class _NormalRefFn(torch.autograd.Function):
+    """NeRFLoss(normal_ref=True)'s two terms behind a fused tail, one entry call (ngp_normal_ref_tail) on what the tail left:
+    ws (constants here: RefLoss composites with detached sigmas), Ro and Rp.
+    -> ref_terms (2) = [lambda_rp mean(Rp), lambda_ro mean(Ro)], the means NeRFLoss takes (over 3 n_rays and n_rays).
+    The gradients w.r.t. dsig_dx (d(sigma)/dx in normalised coordinates, scale3 applied inside) and the normal head's raw
+    output are computed in forward and handed over in backward, as _RenderLossFn does: ref_terms is differentiable only
+    with a unit seed on BOTH entries (NGPTrainer's use)."""
+
+    @staticmethod
+    def forward(ctx, dsig_dx, np_raw, dirs, ws, rays_a, Ro, Rp, scale3, lambda_rp, lambda_ro):
+        n, nr = dsig_dx.shape[0], rays_a.shape[0]
+        dev = dsig_dx.device
+        if np_raw.stride(1) != 1:
+            np_raw = np_raw.contiguous()
+        d_grads = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        d_np = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        if not getattr(rays_a, "_ngp_full_cover", False):   # samples outside every segment: no gradient
+            d_grads.zero_()
+            d_np.zero_()
+        ref_terms = torch.empty(2, dtype=torch.float32, device=dev)
+        call("normal_ref_tail", dsig_dx.contiguous(), scale3, np_raw, np_raw.stride(0), dirs.contiguous(), ws, rays_a, nr, Ro, Rp,
+             float(lambda_rp), float(lambda_ro), 0, d_grads, d_np, ref_terms)
+        ctx.save_for_backward(d_grads, d_np)
+        ctx.pad_np = np_raw.shape[1] - 3
+        ctx.set_materialize_grads(False)
+        return ref_terms
+
+    @staticmethod
+    def backward(ctx, g_terms):
+        if g_terms is None:
+            return (None,) * 10
+        d_grads, d_np = ctx.saved_tensors
+        if ctx.pad_np:
+            d_np = F.pad(d_np, (0, ctx.pad_np))
+        return (d_grads, d_np) + (None,) * 8
+
+
 def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes, fused, kwargs, rays_d=None):
     """fused: the FusedTail of render(..., _fused_loss=)"""
     sig, rgb_o, dsig_dx, np_raw, sem_logits = model._field(xyzs, dirs, kwargs)
+    if fused.normal_ref is not None and not dsig_dx.requires_grad:
+        raise RuntimeError("FusedTail(normal_ref=...) needs d(sigma)/dx with a graph: set model.second_order_normals = True "
+                           "(the Ro term must reach the density field)")
     rgb_bg = None
     if fused.sky:   # as in the reference, the skybox takes precedence over random_bg
         if not kwargs.get('use_skybox', False):
@@ -568,6 +615,10 @@ def _render_loss_fused(model, results, xyzs, dirs, rays_a, T_threshold, classes,
     results['Ro'], results['Rp'] = Ro, Rp
     results['Ro']._ngp_normals_have_grad = False
     results['_loss_terms'] = terms        # terms[0] carries the graph: NGPTrainer seeds its backward with 1
+    if fused.normal_ref is not None:
+        # behind the tail, on its stream: [lambda_rp mean(Rp), lambda_ro mean(Ro)], seeded with (1, 1) beside terms
+        results['_ref_terms'] = _NormalRefFn.apply(dsig_dx, np_raw, dirs, ws, rays_a, Ro, Rp, model._inv_span(),
+                                                   *fused.normal_ref)
     return results
 
 

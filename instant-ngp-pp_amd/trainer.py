@@ -203,8 +203,21 @@ class NGPTrainer:
                  exp_step_factor=0.0, num_classes=7, density_threshold=0.01, render_kwargs=None, group=None,
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
                  semantic=False, normal_mono=False, depth_mono=False, multi_terms=(), use_exposure=False,
-                 unit_exposure_rgb=0.5, use_skybox=False):
-        """use_skybox: the reference's skybox recipe (--use_skybox, train.py:160) for a model built with use_skybox=True
+                 unit_exposure_rgb=0.5, use_skybox=False, normal_ref=False):
+        """normal_ref: NeRFLoss's normal_ref terms (losses.py:107-109: lambda_normal_ref_rp mean(Rp) + lambda_normal_ref_ro
+        mean(Ro), what the reference's street-scene recipes train with) on the fused field node and the fused render + loss
+        tail.  The trainer sets model.second_order_normals: the field hands out d(sigma)/dx with a graph, whose backward is
+        the grid's double backward, ngp_density_head_bwd2 and four existing products (networks._FieldFn); behind the tail one
+        call of ngp_normal_ref_tail forms both terms and their gradients from the tail's ws, Ro and Rp
+        (rendering._NormalRefFn), and the step seeds `terms` and the two ref terms in its one backward call.
+        results['loss_terms'] holds [loss, rgb, opacity, distortion, normal_ref_rp, normal_ref_ro], with multi_terms the two
+        behind the eight; loss includes both.  The step takes the exact gradient norm (the norm bound is not shown to hold
+        for the second-order contributions).  step() then takes no target= and no per-step loss term.  Combines with
+        embedding_a, random_bg and multi_terms, any subset; not with msk_model, pose_refiner, a skybox, use_exposure or a
+        tone-mapped model, semantic=True / normal_mono=True / depth_mono=True (name those terms in multi_terms),
+        differentiable normals, an optional term in loss_kwargs or more than one rank.  loss_kwargs={'normal_ref': True}
+        remains the launch-per-operation route (differentiable normals, the NeRFLoss module).
+        use_skybox: the reference's skybox recipe (--use_skybox, train.py:160) for a model built with use_skybox=True
         and sigmoid colours, on fused kernels: from global_step >= warmup_steps on (the reference's schedule) the step
         passes use_skybox to render(), the skybox's colours come from ngp_skybox_fwd (networks._SkyFn), the tail composites
         over them per ray (ngp_render_loss_fused_sky) and hands the background's gradient to ngp_skybox_bwd, which adds
@@ -362,6 +375,22 @@ class NGPTrainer:
                  "use_skybox" in self.render_kwargs)) if bad]
             if why:
                 raise ValueError("use_skybox=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
+        self.normal_ref = bool(normal_ref)
+        if self.normal_ref:
+            ranks = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+            why = [f"{t}=True (name the term in multi_terms)" for t in MULTI_TERMS if getattr(self, t)] + [w for w, bad in (
+                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
+                ("a skybox", self.use_skybox or self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
+                ("use_exposure=True", self.use_exposure),
+                ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
+                ("differentiable normals (the launch-per-operation route: name one of the two)",
+                 getattr(model, "differentiable_normals", False)),
+                ("an optional term in loss_kwargs", optional),
+                ("more than one rank", ranks > 1 or self.force_sharded)) if bad]
+            if why:
+                raise ValueError("normal_ref=True runs on the fused field node and the fused render + loss tail, which do not "
+                                 "take " + ", ".join(why))
+            model.second_order_normals = True
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
         self.warmup_steps = 256
@@ -524,6 +553,12 @@ class NGPTrainer:
             s = self._seed4 = torch.tensor([1.0] + [0.0] * (terms.numel() - 1), device=terms.device)
         return s
 
+    def _ref_seed(self, ref_terms):
+        s = getattr(self, '_seed_ref', None)
+        if s is None or s.device != ref_terms.device:
+            s = self._seed_ref = torch.ones(2, device=ref_terms.device)
+        return s
+
     def _unit_exposure_rgb(self):
         """the tone-mappers at zero log-radiance and unit exposure, (1, 3) with a graph to their parameters"""
         z = getattr(self, '_unit_inputs', None)
@@ -642,6 +677,13 @@ class NGPTrainer:
             if not rays_o.is_cuda:
                 raise RuntimeError("use_skybox=True needs CUDA tensors: the fused tail has no other route")
         sky_on = NGPTrainer.sky_active(self)
+        nref = getattr(self, "normal_ref", False)
+        if nref:
+            if target or loss_kwargs:
+                raise ValueError("this trainer was built with normal_ref=True: the step stays on the fused render + loss tail "
+                                 "and takes no target= and no per-step loss term")
+            if not rays_o.is_cuda:
+                raise RuntimeError("normal_ref=True needs CUDA tensors: the fused tail has no other route")
         ref = self.pose_refiner
         if ref is not None:
             if rays_o is not None or rays_d is not None or next_rays is not None:
@@ -689,7 +731,8 @@ class NGPTrainer:
                 # size_delta of the step being taken (losses.py:60-69, 85)
                 size_delta=self.loss_fn.Annealing.getWeight(self.global_step) if masked else 0.0,
                 terms={n: _TAIL_TERMS[n].entry(self, given[_TAIL_TERMS[n].arg], rays_o.device) for n in tail_terms} or None,
-                packed=packed, sky=sky_on)
+                packed=packed, sky=sky_on,
+                normal_ref=(self.loss_fn.lambda_normal_ref_rp, self.loss_fn.lambda_normal_ref_ro) if nref else None)
             if tail_terms and not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes,
                                                  extra['_fused_loss']):
                 # (rgb_act or differentiable_normals changed after construction, ...): never a step without the targets
@@ -715,7 +758,7 @@ class NGPTrainer:
         # skybox adds nothing to a table gradient and its own parameters lie behind _mlp_lo, where squares are always
         # summed exactly: the bound holds)
         self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
-                                and not any(_TAIL_TERMS[n].exact_norm for n in tail_terms))
+                                and not nref and not any(_TAIL_TERMS[n].exact_norm for n in tail_terms))
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
@@ -728,12 +771,26 @@ class NGPTrainer:
         if sky_on and '_loss_terms' not in results:
             raise RuntimeError("use_skybox=True: render() did not take the fused tail (rendering._fused_tail_ok); the step "
                                "would run without its skybox kernels")
+        if nref and ('_loss_terms' not in results or '_ref_terms' not in results):
+            raise RuntimeError("normal_ref=True: render() did not take the fused tail with its normal_ref launch "
+                               "(rendering._fused_tail_ok); the two terms would be left out of the loss")
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]
             if tail_terms:
                 results['loss_terms'] = terms.detach()   # the entry's terms (rendering._RenderLossFn): for a caller's log
-            torch.autograd.backward([terms], [self._unit_seed(terms)])
+            if nref:
+                # [the entry's terms | normal_ref_rp, normal_ref_ro], loss with both; seeded in the same backward call (one
+                # backward per step: _norm_share_armed)
+                ref_terms = results.pop('_ref_terms')
+                with torch.no_grad():
+                    all_terms = torch.cat([terms, ref_terms])
+                    all_terms[0] += ref_terms.sum()
+                results['loss_terms'] = all_terms
+                loss = all_terms[0]
+                torch.autograd.backward([terms, ref_terms], [self._unit_seed(terms), self._ref_seed(ref_terms)])
+            else:
+                torch.autograd.backward([terms], [self._unit_seed(terms)])
         elif default_recipe and not masked:
             # same value and gradients as sum(term.mean()) over NeRFLoss's default terms; the
             # gradients are seeded directly (no loss node, no multiplications by 1)

@@ -26,6 +26,9 @@ reference: train.py:82-392).  GPU only.
   python tools/train_dataset.py --make_proxy /tmp/proxy_sky --dataset_name tnt --downsample 0.125 --num_epochs 3 \
       --steps_per_epoch 200 --use_skybox --ckpt_path out/sky.ckpt   # skybox recipe on the proxy over the analytic sky: held-out
       # PSNR, and test_sky_psnr over the held-out pixels that see only sky
+  python tools/train_dataset.py --make_proxy /tmp/proxy_ref --dataset_name tnt --downsample 0.1 --proxy_views 34 \
+      --num_epochs 3 --steps_per_epoch 200 --batch_size 2048 --normal_ref   # normal_ref terms on the fused field and tail:
+      # held-out PSNR, and test_normal_agree_deg_mean between the predicted and the density normals
 """
 import argparse
 import json
@@ -90,7 +93,7 @@ def cameras_outside(train_set, scale):
 def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_every=0, exp_step_factor=0.0,
           render_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6, semantic=False,
           num_classes=7, normal_mono=False, lambda_normal_mono=None, depth_mono=False, lambda_depth_mono=None,
-          multi_terms=(), use_exposure=False, use_skybox=False):
+          multi_terms=(), use_exposure=False, use_skybox=False, normal_ref=False):
     """the reference's schedule (NGPTrainer) fed by the dataset's own sampler, one batch ahead; msk_model: the transient
     mask field of --embed_msk, fed with the sampler's pixel coordinates and image indices; embedding_a: the appearance
     table of --embed_a, fed with the sampler's image indices; pose_refiner: the per-image corrections of --optimize_ext, fed
@@ -103,7 +106,9 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     tail (NGPTrainer(multi_terms=...)): the sampler feeds each named term as its own flag would, and `terms_log` holds the
     8 terms of every step; use_exposure: the HDR-NeRF recipe of --use_exposure, fed with the sampler's exposure times and the
     dataset's unit_exposure_rgb (`terms_log` then holds the 5 terms of every step); use_skybox: the skybox recipe of
-    --use_skybox (NGPTrainer(use_skybox=True): the skybox joins from the end of the warm-up on)"""
+    --use_skybox (NGPTrainer(use_skybox=True): the skybox joins from the end of the warm-up on); normal_ref: the normal_ref
+    terms of --normal_ref (NGPTrainer(normal_ref=True), alone or with multi_terms): `terms_log` then holds the 6 (with
+    multi_terms 10) terms of every step, the two ref terms last"""
     train_set.batch_size = batch_size
     multi_terms = tuple(multi_terms or ())
     if multi_terms and (semantic or normal_mono or depth_mono):
@@ -142,6 +147,8 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
         more.update(use_exposure=True, unit_exposure_rgb=train_set.unit_exposure_rgb)
     if use_skybox:
         more.update(use_skybox=True)
+    if normal_ref:
+        more.update(normal_ref=True)
     if multi_terms:
         more.update(multi_terms=multi_terms)
     else:
@@ -203,7 +210,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             more["exposure"] = cur[9]
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
-        if depth_mono or multi_terms or use_exposure:
+        if depth_mono or multi_terms or use_exposure or normal_ref:
             trainer.terms_log.append(res["loss_terms"])
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize()
@@ -315,7 +322,20 @@ def parse_args(argv=None):
                          "every pixel in opacity/*.npy.  Whenever the scene directory has those, the JSON line gains "
                          "test_sky_psnr, the PSNR over the held-out pixels whose opacity is below 0.01")
     ap.add_argument("--proxy_views", type=int, default=108, help="views of the scene --make_proxy writes")
+    ap.add_argument("--normal_ref", action="store_true",
+                    help="the reference's normal_ref terms (--normal_ref: Ref-NeRF's Rp and Ro regularisers) on the fused field "
+                         "node and the fused tail (NGPTrainer(normal_ref=True)); alone or with --multi_terms, --embed_a and "
+                         "--random_bg.  The JSON line gains the two terms' means over the first and the last ten steps and "
+                         "test_normal_agree_deg_mean, the mean angle over the held-out pixels with opacity above 0.5 "
+                         "between the rendered predicted normal and the rendered density normal")
     args = ap.parse_args(argv)
+    if args.make_proxy and args.normal_ref and args.dataset_name != "tnt":
+        ap.error("--make_proxy with --normal_ref writes the scene in the tnt layout: --dataset_name tnt")
+    if args.normal_ref and (args.embed_msk or args.optimize_ext or args.use_exposure or args.use_skybox or args.render_semantic
+                            or args.normal_mono or args.depth_mono):
+        ap.error("--normal_ref combines with --multi_terms, --embed_a and --random_bg, not with --embed_msk, --optimize_ext, "
+                 "--use_exposure, --use_skybox or a single term's own flag (--render_semantic, --normal_mono, --depth_mono: "
+                 "name the term in --multi_terms)")
     args.multi_terms = tuple(t for t in MULTI_TERMS if t in args.multi_terms)
     if args.multi_terms and (args.render_semantic or args.normal_mono or args.depth_mono):
         ap.error("--multi_terms names the terms itself: not together with --render_semantic, --normal_mono or --depth_mono")
@@ -388,6 +408,16 @@ def make_proxy_with_normals(root, scene, n_quad=256):
     c2w = scene.poses.cpu().numpy().astype("float64")
     K = scene.K.cpu().numpy().astype("float64")
     return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)], normals=normals)
+
+
+def make_tnt_proxy(root, scene, n_quad=256):
+    """the analytic proxy's images alone in the tnt layout, every 8th view held out (--normal_ref needs no map)"""
+    from ngp_amd.datasets import export
+    n = scene.poses.shape[0]
+    images = export.render_scene_views(scene, range(n), rgba=False, n_quad=n_quad)
+    c2w = scene.poses.cpu().numpy().astype("float64")
+    K = scene.K.cpu().numpy().astype("float64")
+    return export.export_tnt(root, images, c2w, K, [1 if i % 8 == 0 else 0 for i in range(n)])
 
 
 PROXY_DEPTH_SCALE, PROXY_DEPTH_SHIFT = 0.37, 0.11
@@ -501,6 +531,36 @@ def multi_terms_summary(terms_log, k=10):
     return {nm: (float(t[:k, 4 + i].mean()), float(t[-k:, 4 + i].mean())) for i, nm in enumerate(names)}
 
 
+def normal_ref_summary(terms_log, k=10):
+    """{term: (mean over the first k steps, over the last k steps)} for the last two entries of train()'s terms_log"""
+    t = torch.stack([v.detach() for v in terms_log]).cpu()
+    k = max(1, min(k, len(t) // 2))
+    return {nm: (float(t[:k, i].mean()), float(t[-k:, i].mean())) for nm, i in (("normal_ref_rp", -2), ("normal_ref_ro", -1))}
+
+
+class NormalAgreement:
+    """evaluate_split's on_image callback: the angle between results['normal_pred'] and results['normal_raw'] (both
+    normalised by the test-time renderer) pooled over the held-out pixels whose opacity is above `threshold`; `then`: the
+    callback to run behind it"""
+
+    def __init__(self, threshold=0.5, then=None):
+        self.threshold, self.then = threshold, then
+        self.deg, self.n = 0.0, 0
+
+    def __call__(self, i, rgb, results):
+        keep = results["opacity"].reshape(-1) > self.threshold
+        cos = (results["normal_pred"] * results["normal_raw"]).sum(-1).clamp(-1.0, 1.0)[keep]
+        self.deg = self.deg + torch.rad2deg(torch.acos(cos)).double().sum()
+        self.n = self.n + keep.sum()
+        if self.then is not None:
+            self.then(i, rgb, results)
+
+    def value(self):
+        """(mean angle in degrees, number of pixels); (None, 0) without a pixel"""
+        n = int(self.n)
+        return (float(self.deg) / n, n) if n else (None, 0)
+
+
 def terms_summary(terms_log, k=10):
     """(number of loss terms, mean of the last term over the first k steps, over the last k steps) of train()'s terms_log"""
     t = torch.stack([v.detach() for v in terms_log]).cpu()
@@ -535,6 +595,9 @@ def main():
             args.downsample = 1.0
         elif args.use_skybox:
             root = make_sky_proxy(args.make_proxy, scene)
+            args.downsample = 1.0
+        elif args.normal_ref:
+            root = make_tnt_proxy(args.make_proxy, scene)
             args.downsample = 1.0
         else:
             root = write_synthetic_dataset(args.make_proxy, scene, n_train=100, n_test=8, rgba=False)
@@ -588,7 +651,7 @@ def main():
           msk_model=msk_model, embedding_a=embedding_a, pose_refiner=pose_refiner, pose_lr=args.pose_lr,
           semantic=args.render_semantic, num_classes=args.num_classes, normal_mono=args.normal_mono,
                     depth_mono=args.depth_mono, lambda_depth_mono=args.lambda_depth_mono, multi_terms=args.multi_terms,
-                    use_exposure=args.use_exposure, use_skybox=args.use_skybox)
+                    use_exposure=args.use_exposure, use_skybox=args.use_skybox, normal_ref=args.normal_ref)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     more = {}
@@ -603,6 +666,8 @@ def main():
     sky_psnr = None
     if opacity is not None:
         on_image = sky_psnr = SkyPsnr(test_set, opacity, then=on_image)
+    # (always measured: a run without --normal_ref is what the term's effect is read against)
+    on_image = agree = NormalAgreement(then=on_image)
     res = evaluate_split(model, test_set, on_image=on_image, exp_step_factor=args.exp_step_factor, **more)
     psnrs, ssims = res["psnr"], res["ssim"]
     if args.ckpt_path:
@@ -611,6 +676,11 @@ def main():
     out = {"train_s": t_train, "test_psnr_mean": sum(psnrs) / len(psnrs), "test_psnr": psnrs,
            "test_ssim_mean": sum(ssims) / len(ssims), "test_ssim": ssims,
            "steps": args.num_epochs * args.steps_per_epoch, "img_wh": train_set.img_wh}
+    out["test_normal_agree_deg_mean"], out["test_normal_agree_pixels"] = agree.value()
+    if args.normal_ref:
+        out.update(normal_ref=True, loss_terms=int(trainer.terms_log[0].numel()))
+        for nm, (first, last) in normal_ref_summary(trainer.terms_log).items():
+            out[f"{nm}_term_first"], out[f"{nm}_term_last"] = first, last
     if args.use_skybox:
         out["use_skybox"] = True
     if sky_psnr is not None:   # over the held-out pixels that see only background
