@@ -20,7 +20,6 @@ MI355X-specific structure:
 """
 import math
 import os
-from typing import Callable, NamedTuple, Tuple
 
 import torch
 import torch.distributed as dist
@@ -28,53 +27,10 @@ import torch.distributed as dist
 from ._lib import call
 from .appearance import RayCodes
 from .losses import NeRFLoss, nerf_loss_and_grads
-from .rendering import MAX_SAMPLES, MULTI_TERMS, TAIL_LAYOUT, FusedTail, MarchAhead, _fused_tail_ok, render
+from .recipe import _TAIL_TERMS, resolve
+from .rendering import MAX_SAMPLES, FusedTail, MarchAhead, _fused_tail_ok, render
 
 _f32 = torch.float32
-
-
-class _TailTerm(NamedTuple):
-    """one of NeRFLoss's optional terms on the fused render + loss tail, as NGPTrainer sees it"""
-    arg: str                 # step()'s argument that carries the term's target
-    what: str
-    bad: Callable            # (target, n_rays) -> what the target must do instead, None for a good one
-    entry: Callable          # (trainer, target, device) -> the term's entry of FusedTail.terms
-    classes: Tuple[int, int]   # num_classes the tail takes with this term (of several terms: the larger of either end)
-    exact_norm: bool         # the term's head adds to the colour table's gradient, outside the norm bound
-
-
-_TAIL_TERMS = {
-    "semantic": _TailTerm(
-        "labels", "the class of every ray",
-        lambda x, n: None if x.numel() == n else f"hold {n} entries, one per ray: got {tuple(x.shape)}",
-        lambda tr, x, dev: (x.view(-1).to(torch.int64), tr.loss_fn.lambda_semantic, tr.loss_fn.lambda_sky),
-        (1, 16), True),
-    "normal_mono": _TailTerm(
-        "normals", "the target normal of every ray",
-        lambda x, n: None if x.dim() == 2 and tuple(x.shape) == (n, 3) and x.is_floating_point()
-        else f"be ({n}, 3) float: got {tuple(x.shape)} {x.dtype}",
-        lambda tr, x, dev: (x.to(dev, _f32).contiguous(), tr.loss_fn.lambda_normal_mono),
-        (0, 8), True),
-    "depth_mono": _TailTerm(
-        "depths", "the monocular depth of every ray",
-        lambda x, n: None if tuple(x.shape) == (n,) and x.is_floating_point()
-        else f"be ({n},) float: got {tuple(x.shape)} {x.dtype}",
-        lambda tr, x, dev: (x.to(dev, _f32).contiguous(), tr.loss_fn.lambda_depth_mono, float(tr.model.scale)),
-        (0, 8), False),
-}
-assert tuple(_TAIL_TERMS) == MULTI_TERMS
-
-
-def _tail_terms(trainer):
-    """(the optional terms `trainer` trains on the fused tail, in MULTI_TERMS' order; whether they take one term's own
-    entry; the option that asked for them).  getattr: the stand-ins of the host tests carry only some of the flags"""
-    multi = getattr(trainer, 'multi_terms', ())
-    if multi:
-        return multi, False, f"multi_terms={multi}"
-    for name in MULTI_TERMS:
-        if getattr(trainer, name, False):
-            return (name,), True, f"{name}=True"
-    return (), False, None
 
 
 class GradBuckets:
@@ -204,79 +160,9 @@ class NGPTrainer:
                  force_sharded=None, loss_kwargs=None, msk_model=None, embedding_a=None, pose_refiner=None, pose_lr=1e-6,
                  semantic=False, normal_mono=False, depth_mono=False, multi_terms=(), use_exposure=False,
                  unit_exposure_rgb=0.5, use_skybox=False, normal_ref=False):
-        """normal_ref: NeRFLoss's normal_ref terms (losses.py:107-109: lambda_normal_ref_rp mean(Rp) + lambda_normal_ref_ro
-        mean(Ro), what the reference's street-scene recipes train with) on the fused field node and the fused render + loss
-        tail.  The trainer sets model.second_order_normals: the field hands out d(sigma)/dx with a graph, whose backward is
-        the grid's double backward, ngp_density_head_bwd2 and four existing products (networks._FieldFn); behind the tail one
-        call of ngp_normal_ref_tail forms both terms and their gradients from the tail's ws, Ro and Rp
-        (rendering._NormalRefFn), and the step seeds `terms` and the two ref terms in its one backward call.
-        results['loss_terms'] holds [loss, rgb, opacity, distortion, normal_ref_rp, normal_ref_ro], with multi_terms the two
-        behind the eight; loss includes both.  The step takes the exact gradient norm (the norm bound is not shown to hold
-        for the second-order contributions).  step() then takes no target= and no per-step loss term.  Combines with
-        embedding_a, random_bg and multi_terms, any subset; not with msk_model, pose_refiner, a skybox, use_exposure or a
-        tone-mapped model, semantic=True / normal_mono=True / depth_mono=True (name those terms in multi_terms),
-        differentiable normals, an optional term in loss_kwargs or more than one rank.  loss_kwargs={'normal_ref': True}
-        remains the launch-per-operation route (differentiable normals, the NeRFLoss module).
-        use_skybox: the reference's skybox recipe (--use_skybox, train.py:160) for a model built with use_skybox=True
-        and sigmoid colours, on fused kernels: from global_step >= warmup_steps on (the reference's schedule) the step
-        passes use_skybox to render(), the skybox's colours come from ngp_skybox_fwd (networks._SkyFn), the tail composites
-        over them per ray (ngp_render_loss_fused_sky) and hands the background's gradient to ngp_skybox_bwd, which adds
-        straight into the flat gradient.  Before that the step is the default recipe (with random_bg if set) and the sky
-        parameters get a zero gradient.  As in the reference the skybox takes precedence over random_bg.  step() then takes
-        no target= and no per-step loss term.  Combines with embedding_a and random_bg; not with msk_model, pose_refiner,
-        semantic / normal_mono / depth_mono / multi_terms, use_exposure or a tone-mapped model, differentiable normals or an
-        optional term in loss_kwargs.  render_kwargs={'use_skybox': True} (without this flag) remains the
-        launch-per-operation route, from step 0.
-        use_exposure: the reference's HDR-NeRF recipe (--use_exposure, train.py:99, 169-170, 301-306) for a model built with
-        rgb_act='None': step() then needs exposure= (the exposure time of every ray), which reaches the three tone-mappers
-        through render(), and the loss gains unit_exposure = 0.5 (tone(0, exposure=1) - unit_exposure_rgb)^2, its mean over
-        the three channels (unit_exposure_rgb: the dataset's, 0.73 synthetic / 0.5 real); results['loss_terms'] holds
-        [loss, rgb, opacity, distortion, unit_exposure] (on the NeRFLoss module's route, taken with an optional term in
-        loss_kwargs or a per-step target=, that term's means sit between distortion and unit_exposure).  The tone-mappers run on ngp_tonemap_fwd / ngp_tonemap_bwd, whose
-        backward adds straight into the flat gradient; the term touches only the tone-mapper parameters, whose squares are
-        always summed exactly, so the step's clip route is that of any tone-mapped model.  Combines with embedding_a and
-        random_bg; not with msk_model, pose_refiner or a skybox (and the fused-tail options refuse a tone-mapped model).
-        multi_terms: a non-empty subset of ('semantic', 'normal_mono', 'depth_mono'): those of NeRFLoss's optional terms
-        TOGETHER on the fused render + loss tail (ngp_render_loss_fused_multi), as the reference's street-scene recipes use
-        them.  Each term is the one its own flag below trains; step() then needs exactly the named terms' targets (labels=,
-        normals=, depths=), and results['loss_terms'] holds the 8 terms [loss, rgb, opacity, distortion, CELoss, sky_depth,
-        normal_mono, depth_mono].  The step takes the exact gradient norm when semantic or normal_mono is named and keeps
-        the norm-bound clip for ('depth_mono',) alone.  Combines with embedding_a and random_bg; not with semantic=True,
-        normal_mono=True, depth_mono=True (each of those is one term alone), msk_model, pose_refiner, a skybox, a tone-mapped
-        model, differentiable normals, an optional term in loss_kwargs (normal_ref included) or a num_classes that is not the
-        model's head (1..16 with the semantic term, at most 8 without).
-        depth_mono: NeRFLoss's depth_mono term (losses.py:7-30, 125-131: composited depth against per-pixel monocular depth
-        up to the batch's least-squares scale and shift, weight lambda_depth_mono) on the fused render + loss tail
-        (ngp_render_loss_fused_dep: a fit kernel, then the tail).  step() then needs depths= (n_rays) float, the raw depth
-        (z = depth / 25); zero, negative and NaN mark a ray without depth, which takes no part in the fit, the term or any
-        gradient (the mean stays over n_rays); the falloff's scene scale is the model's `scale`.  The term reaches the
-        parameters through d_sigmas alone, the density head's backward stays the one writer of its table's gradient, and the
-        step keeps the norm-bound clip.  Combines with embedding_a and random_bg; not with msk_model, pose_refiner,
-        semantic=True, normal_mono=True, a skybox, a tone-mapped model, differentiable normals or an optional term in
-        loss_kwargs.  loss_kwargs={'depth_mono': True} with step(target={'depth': ...}) remains the launch-per-operation route
-        through the NeRFLoss module.
-        normal_mono: NeRFLoss's normal_mono term (losses.py:111-118: the predicted-normal head against per-pixel normal
-        maps, weight lambda_normal_mono) on the fused render + loss tail (ngp_render_loss_fused_nrm).  step() then needs
-        normals= (n_rays, 3) float; a row of three exact zeros marks a ray without a normal, which takes no part in the term
-        (the divisor stays 3 n_rays).  The normal head's backward adds to the colour table's gradient, outside the norm
-        bound: the step takes the exact gradient norm.  Combines with embedding_a and random_bg; not with msk_model,
-        pose_refiner, semantic=True, a skybox, a tone-mapped model, differentiable normals or an optional term in
-        loss_kwargs.  loss_kwargs={'normal_mono': True} with step(target={'normal': ...}) remains the launch-per-operation
-        route through the NeRFLoss module.
-        semantic: the reference's render_semantic recipe (train.py:197, 293; NeRFLoss(semantic=True), losses.py:120-123)
-        on the fused render + loss tail (ngp_render_loss_fused_sem).  step() then needs labels= (n_rays) int64; a label
-        outside [0, num_classes) is ignored (256, the reference's ignore_index, and the 255 an 8-bit label image holds in
-        its place), and a batch without a valid label has a zero CE term where torch's cross-entropy gives NaN.  The
-        semantic head's backward adds to the colour table's gradient, outside the norm bound: the step takes the exact
-        gradient norm.  Combines with embedding_a and random_bg; not with msk_model, pose_refiner, a skybox, a tone-mapped
-        model or an optional term in loss_kwargs.  loss_kwargs={'semantic': True} with step(target={'label': ...}) remains
-        the launch-per-operation route through the NeRFLoss module.
-        pose_refiner: a pose.PoseRefiner (the reference's --optimize_ext, train.py:143-149, 225-230).  step() then takes
-        img_idxs= and pix_idxs= instead of ray tensors and forms the rays itself from the current dR, dT; the samples enter
-        the field requiring a gradient, which ngp_pose_rays_bwd reduces per image.  dR and dT live in a small buffer of their
-        own OUTSIDE the flat store, as the reference keeps them out of net_opt: their own Adam at the constant `pose_lr` (no
-        cosine schedule) and their own clip at clip_norm (Lightning clips per optimizer).  A pose step takes the exact
-        gradient norm for the model (the norm bound is not shown to hold on the field's dL/dx route).  One rank only.
+        """The options semantic, normal_mono, depth_mono, multi_terms, use_exposure (with unit_exposure_rgb), use_skybox,
+        normal_ref and pose_refiner are described in recipe.py, each next to its row of the table that says what it combines
+        with, what it needs from step() and which clip route its step takes; recipe.resolve() checks them here.
         embedding_a: the nn.Embedding(n_imgs, embed_a_len) of the embed_a recipe (or a FrameEmbedding, whose table is
         taken), for a model built with embed_a=True.  Its weight joins the flat store behind the model's parameters as
         'embedding_a.weight' (the reference keeps it in net_opt, train.py:238-244: one Adam, one schedule, one clip), step()
@@ -301,9 +187,6 @@ class NGPTrainer:
                                  f"was built with embed_a={bool(E)}, embed_a_len={E}")
         self.force_sharded = bool(os.environ.get("NGP_FORCE_SHARDED")) if force_sharded is None else bool(force_sharded)
         self.pose_refiner, self.pose_lr = pose_refiner, float(pose_lr)
-        if pose_refiner is not None and (self.force_sharded or (dist.is_available() and dist.is_initialized()
-                                                                 and dist.get_world_size(group) > 1)):
-            raise ValueError("pose refinement runs on one rank: a sharded trainer takes no pose_refiner")
         self.base_lr = lr
         self.num_epochs = num_epochs
         self.steps_per_epoch = steps_per_epoch
@@ -314,82 +197,13 @@ class NGPTrainer:
         self.render_kwargs = dict(render_kwargs or {})
         self.loss_fn = NeRFLoss()
         self.loss_kwargs = dict(loss_kwargs or {})
-        optional = any(self.loss_kwargs.get(k) for k in ("normal_ref", "normal_mono", "semantic", "depth_mono", "embed_msk"))
-        self.fused_loss = not optional   # default recipe (rgb + opacity + distortion); False -> NeRFLoss module
-        if pose_refiner is not None and (optional or self.render_kwargs.get("use_skybox")
-                                         or getattr(model, "differentiable_normals", False)):
-            # only the field's dL/dx and dL/dd feed the pose gradient; the Ro term (rendering._RefLossInputs returns no
-            # gradient for dirs), a skybox (a function of rays_d) and second-order normals would leave it silently incomplete
-            raise ValueError("pose refinement runs on the fused render + loss tail: a trainer with a pose_refiner takes no "
-                             "optional loss term, no skybox and no differentiable normals")
-        self.use_exposure, self.unit_exposure_rgb = bool(use_exposure), float(unit_exposure_rgb)
-        if self.use_exposure:
-            if getattr(model, "rgb_act", "Sigmoid") != "None":
-                raise ValueError("use_exposure=True needs a model built with rgb_act='None' (log-radiance and the three "
-                                 f"tone-mappers): this one has rgb_act={getattr(model, 'rgb_act', 'Sigmoid')!r}")
-            why = [w for w, bad in (
-                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False))) if bad]
-            if why:
-                raise ValueError("use_exposure=True does not combine with " + ", ".join(why))
-        self.semantic, self.normal_mono, self.depth_mono = bool(semantic), bool(normal_mono), bool(depth_mono)
-        if isinstance(multi_terms, str):
-            multi_terms = (multi_terms,)
-        multi_terms = tuple(multi_terms or ())
-        unknown = [t for t in multi_terms if t not in MULTI_TERMS]
-        if unknown or len(set(multi_terms)) != len(multi_terms):
-            raise ValueError(f"multi_terms is a subset of {MULTI_TERMS} without repeats: got {multi_terms}")
-        self.multi_terms = tuple(t for t in MULTI_TERMS if t in multi_terms)
-        # the options that put optional terms on the fused tail: one at a time (the last one speaks, the others are refused)
-        asked = [f"{t}=True" for t in MULTI_TERMS if getattr(self, t)]
-        if self.multi_terms:
-            asked.append(f"multi_terms={self.multi_terms}")
-        if asked:
-            named = [t for t in MULTI_TERMS if getattr(self, t) or t in self.multi_terms]
-            lo, hi = (max(_TAIL_TERMS[t].classes[k] for t in named) for k in (0, 1))
-            head = getattr(getattr(model, "semantic_header", None), "n_output_dims", None)
-            why = asked[:-1] + [w for w, bad in (
-                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                ("a skybox", self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
-                ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                ("an optional term in loss_kwargs", optional),
-                ("differentiable normals", getattr(model, "differentiable_normals", False)),
-                (f"num_classes = {num_classes} " + (f"outside {lo}..{hi}" if lo else f"above {hi}"),
-                 not lo <= int(num_classes) <= hi),
-                (f"a model with {head} classes for num_classes = {num_classes}",
-                 "semantic" in named and head != int(num_classes))) if bad]
-            if why:
-                raise ValueError(f"{asked[-1]} runs on the fused render + loss tail, which does not take " + ", ".join(why))
-        self.use_skybox = bool(use_skybox)
-        if self.use_skybox:
-            if not getattr(model, "use_skybox", False):
-                raise ValueError("use_skybox=True needs a model built with use_skybox=True (skybox_dir_encoder and "
-                                 "skybox_rgb_net)")
-            why = asked + [w for w, bad in (
-                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                ("use_exposure=True", self.use_exposure),
-                ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                ("an optional term in loss_kwargs", optional),
-                ("differentiable normals", getattr(model, "differentiable_normals", False)),
-                ("render_kwargs['use_skybox'] (the launch-per-operation route: name one of the two)",
-                 "use_skybox" in self.render_kwargs)) if bad]
-            if why:
-                raise ValueError("use_skybox=True runs on the fused render + loss tail, which does not take " + ", ".join(why))
-        self.normal_ref = bool(normal_ref)
-        if self.normal_ref:
-            ranks = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-            why = [f"{t}=True (name the term in multi_terms)" for t in MULTI_TERMS if getattr(self, t)] + [w for w, bad in (
-                ("a msk_model", msk_model is not None), ("a pose_refiner", pose_refiner is not None),
-                ("a skybox", self.use_skybox or self.render_kwargs.get("use_skybox") or getattr(model, "use_skybox", False)),
-                ("use_exposure=True", self.use_exposure),
-                ("rgb_act != 'Sigmoid'", getattr(model, "rgb_act", "Sigmoid") != "Sigmoid"),
-                ("differentiable normals (the launch-per-operation route: name one of the two)",
-                 getattr(model, "differentiable_normals", False)),
-                ("an optional term in loss_kwargs", optional),
-                ("more than one rank", ranks > 1 or self.force_sharded)) if bad]
-            if why:
-                raise ValueError("normal_ref=True runs on the fused field node and the fused render + loss tail, which do not "
-                                 "take " + ", ".join(why))
+        self.recipe = resolve(
+            model, msk_model=msk_model, embedding_a=self.embedding_a, pose_refiner=pose_refiner, render_kwargs=self.render_kwargs,
+            loss_kwargs=self.loss_kwargs, num_classes=num_classes, force_sharded=self.force_sharded,
+            ranks=dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1,
+            semantic=semantic, normal_mono=normal_mono, depth_mono=depth_mono, multi_terms=multi_terms,
+            use_exposure=use_exposure, unit_exposure_rgb=unit_exposure_rgb, use_skybox=use_skybox, normal_ref=normal_ref)
+        if self.recipe.normal_ref:
             model.second_order_normals = True
         if self.loss_kwargs.get("normal_ref"):
             model.differentiable_normals = True
@@ -572,7 +386,7 @@ class NGPTrainer:
         0.5 (unit - unit_exposure_rgb)^2 (train.py:301-306), seeded directly as the default terms are"""
         unit = self._unit_exposure_rgb()
         with torch.no_grad():
-            diff = unit - self.unit_exposure_rgb
+            diff = unit - self.recipe.unit_exposure_rgb
             return unit, diff / 3.0, 0.5 * (diff * diff).mean()
 
     def _early_norm_share(self):
@@ -594,29 +408,16 @@ class NGPTrainer:
     def sky_active(self):
         """whether the step about to be taken composites over the skybox: a trainer built with use_skybox=True, from
         global_step >= warmup_steps on (train.py:160)"""
-        return bool(getattr(self, "use_skybox", False) and self.global_step >= self.warmup_steps)
+        return bool(self.recipe.use_skybox and self.global_step >= self.warmup_steps)
 
     def step(self, rays_o, rays_d, rgb_gt, next_rays=None, target=None, uvi=None, img_idxs=None, pix_idxs=None, labels=None,
              normals=None, depths=None, exposure=None, **loss_kwargs):
         """one training step on this rank's ray batch; returns (loss tensor, results dict).
 
-        A trainer built with use_skybox=True takes no target= and no per-step loss term; the skybox joins the step from
-        global_step >= warmup_steps on.
-
-        exposure: (n_rays) or (n_rays, 1) float exposure time of every ray in seconds, required by a trainer built with
-        use_exposure=True and refused by any other.
-
-        A trainer built with multi_terms= needs exactly the named terms' targets among labels=, normals=, depths= (as
-        described below), and takes no target= and no per-step loss term.
-
-        depths: (n_rays) float raw monocular depth of every ray (zero, negative, NaN: none), required by a trainer built with
-        depth_mono=True (which then takes no target= and no per-step loss term).
-
-        normals: (n_rays, 3) float target normal of every ray (three exact zeros: none), required by a trainer built with
-        normal_mono=True (which then takes no target= and no per-step loss term).
-
-        labels: (n_rays) int64 class of every ray, required by a trainer built with semantic=True (which then takes no
-        target= and no per-step loss term).
+        labels, normals, depths, exposure: the per-ray targets of the options the trainer was built with (recipe.py describes
+        each next to its option's row): exactly those it needs, any other is refused.  A trainer built with a term on the
+        fused tail, with use_skybox=True (the skybox joins the step from global_step >= warmup_steps on) or with
+        normal_ref=True takes no target= and no per-step loss term.
 
         uvi: (n_rays, 3) input of the trainer's msk_model (implicit_mask.uvi), required when there is one.
         img_idxs: (n_rays) image index of every ray, required when the trainer has an embedding_a or a pose_refiner.
@@ -632,72 +433,16 @@ class NGPTrainer:
         data loader that is one batch ahead): their AABB test and occupancy march are then run on a
         side stream under this step's backward and the next call picks the result up, provided it
         is called with the very same tensors and no density-grid update lies in between."""
-        model = self.model
-        masked = self.msk_model is not None
-        if masked and uvi is None:
-            raise ValueError("this trainer has a msk_model: step() needs uvi= (implicit_mask.uvi of the ray batch)")
-        if self.embedding_a is not None and img_idxs is None:
-            raise ValueError("this trainer has an embedding_a: step() needs img_idxs= (the image index of every ray)")
-        if getattr(self, "use_exposure", False):   # (getattr: as in _tail_terms, the host tests' stand-ins carry only some flags)
-            if exposure is None:
-                raise ValueError("this trainer was built with use_exposure=True: step() needs exposure= (the exposure time "
-                                 "of every ray)")
-            if not (torch.is_tensor(exposure) and exposure.is_floating_point() and exposure.numel() == rgb_gt.shape[0]
-                    and exposure.dim() in (1, 2)):
-                raise ValueError(f"exposure= must be ({rgb_gt.shape[0]},) or ({rgb_gt.shape[0]}, 1) float: got "
-                                 f"{tuple(exposure.shape) if torch.is_tensor(exposure) else type(exposure).__name__}")
-            if not exposure.is_cuda:
-                raise RuntimeError("exposure must be a CUDA tensor")
-        elif exposure is not None:
-            raise ValueError("exposure= is for a trainer built with use_exposure=True")
-        tail_terms, packed, asked = _tail_terms(self)
+        model, recipe = self.model, self.recipe
+        recipe.check_step(rays_o, rays_d, rgb_gt, next_rays=next_rays, target=target, uvi=uvi, img_idxs=img_idxs,
+                          pix_idxs=pix_idxs, labels=labels, normals=normals, depths=depths, exposure=exposure,
+                          loss_kwargs=loss_kwargs)
+        masked, tail_terms, nref, sky_on = recipe.masked, recipe.tail_terms, recipe.normal_ref, self.sky_active()
         given = {"labels": labels, "normals": normals, "depths": depths}
-        for name in MULTI_TERMS:
-            t = _TAIL_TERMS[name]
-            if name in tail_terms:
-                if given[t.arg] is None:
-                    raise ValueError(f"this trainer was built with {asked}: step() needs {t.arg}= ({t.what})")
-                why = t.bad(given[t.arg], rgb_gt.shape[0])
-                if why:
-                    raise ValueError(f"{t.arg}= must {why}")
-            elif given[t.arg] is not None:
-                raise ValueError(f"{t.arg}= is for a trainer built with {name}=True or with multi_terms naming '{name}'"
-                                 + (f": this one has {asked}" if asked else ""))
-        if tail_terms:
-            if target or loss_kwargs:
-                raise ValueError(f"this trainer was built with {asked}: the step stays on the fused render + loss tail and "
-                                 "takes no target= and no per-step loss term")
-            if not rays_o.is_cuda:
-                raise RuntimeError(f"{asked} needs CUDA tensors: the fused tail has no other route")
-        sky = getattr(self, "use_skybox", False)   # (getattr: the host tests' stand-ins carry only some flags)
-        if sky:
-            if target or loss_kwargs:
-                raise ValueError("this trainer was built with use_skybox=True: the step stays on the fused render + loss tail "
-                                 "and takes no target= and no per-step loss term")
-            if not rays_o.is_cuda:
-                raise RuntimeError("use_skybox=True needs CUDA tensors: the fused tail has no other route")
-        sky_on = NGPTrainer.sky_active(self)
-        nref = getattr(self, "normal_ref", False)
-        if nref:
-            if target or loss_kwargs:
-                raise ValueError("this trainer was built with normal_ref=True: the step stays on the fused render + loss tail "
-                                 "and takes no target= and no per-step loss term")
-            if not rays_o.is_cuda:
-                raise RuntimeError("normal_ref=True needs CUDA tensors: the fused tail has no other route")
         ref = self.pose_refiner
         if ref is not None:
-            if rays_o is not None or rays_d is not None or next_rays is not None:
-                raise ValueError("this trainer has a pose_refiner: step() forms the rays itself from img_idxs= and pix_idxs= "
-                                 "(pass rays_o = rays_d = None and no next_rays: a march-ahead would use poses one update old)")
-            if img_idxs is None or pix_idxs is None:
-                raise ValueError("this trainer has a pose_refiner: step() needs img_idxs= and pix_idxs=")
-            if target or loss_kwargs:
-                raise ValueError("this trainer has a pose_refiner: the step stays on the fused render + loss tail and takes "
-                                 "no target= and no per-step loss term")
             with torch.no_grad():   # the values only: the graph starts at the samples (rendering._render_rays_train)
                 rays_o, rays_d = ref.rays(img_idxs, pix_idxs)
-        elif pix_idxs is not None:
-            raise ValueError("pix_idxs= is for a trainer with a pose_refiner")
         self._join_grad_zeroing()
         if self.global_step % self.update_interval == 0:
             model.update_density_grid(self.density_threshold * MAX_SAMPLES / 3 ** 0.5,
@@ -718,7 +463,7 @@ class NGPTrainer:
                     ahead.launch(model, next_rays[0], next_rays[1], self.exp_step_factor)
         elif ahead is not None:
             marched = ahead.take(rays_o, rays_d, self.exp_step_factor)
-        default_recipe = bool(self.fused_loss and not loss_kwargs and not target)
+        default_recipe = bool(recipe.fused_loss and not loss_kwargs and not target)
         extra = {}
         mask = None
         if masked:
@@ -731,13 +476,13 @@ class NGPTrainer:
                 # size_delta of the step being taken (losses.py:60-69, 85)
                 size_delta=self.loss_fn.Annealing.getWeight(self.global_step) if masked else 0.0,
                 terms={n: _TAIL_TERMS[n].entry(self, given[_TAIL_TERMS[n].arg], rays_o.device) for n in tail_terms} or None,
-                packed=packed, sky=sky_on,
+                packed=recipe.packed, sky=sky_on,
                 normal_ref=(self.loss_fn.lambda_normal_ref_rp, self.loss_fn.lambda_normal_ref_ro) if nref else None)
             if tail_terms and not _fused_tail_ok(model, self.render_kwargs, self.exp_step_factor, self.num_classes,
                                                  extra['_fused_loss']):
                 # (rgb_act or differentiable_normals changed after construction, ...): never a step without the targets
-                raise RuntimeError(f"{asked}: the model no longer fits the fused tail (rendering._fused_tail_ok); the targets "
-                                   "would be left out of the loss")
+                raise RuntimeError(f"{recipe.asked}: the model no longer fits the fused tail (rendering._fused_tail_ok); the "
+                                   "targets would be left out of the loss")
         if self.embedding_a is not None:
             extra['embedding_a'] = RayCodes(self.embedding_a.weight, img_idxs)
         if ref is not None:
@@ -752,28 +497,14 @@ class NGPTrainer:
             ahead.launch(model, next_rays[0], next_rays[1], self.exp_step_factor)
         self._norm_share_armed, self._norm_share_fired = True, 0   # one backward follows, then the optimizer step
         # clip_grad_norm_(50) from an upper bound of the norm (ngp_clip_decide) instead of the 0.8 GB sum-of-squares
-        # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients
-        # (the semantic and the normal head add to the colour table's gradient: outside the bound, the exact norm from the
-        # start; the depth_mono term only changes d_sigmas, which the density head's backward notes: the bound holds; the
-        # skybox adds nothing to a table gradient and its own parameters lie behind _mlp_lo, where squares are always
-        # summed exactly: the bound holds)
-        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals and ref is None
-                                and not nref and not any(_TAIL_TERMS[n].exact_norm for n in tail_terms))
+        # pass: only on the default recipe, where the fused field backward is the one writer of the table gradients, and
+        # with the options for which the bound holds (recipe.py says why, row by row)
+        self._bound_step = bool(self.norm_bound and default_recipe and not model.differentiable_normals
+                                and not recipe.exact_norm())
         model.link.begin_bound_step(self.norm_acc if self._bound_step else None)
         if self.norm_bound:
             model.rgb_encoder._bound_valid = model.xyz_encoder._bound_valid = True
-        fused = extra.get('_fused_loss')
-        if tail_terms and (fused is None or '_loss_terms' not in results
-                           or results['_loss_terms'].numel() != TAIL_LAYOUT[fused.entry].n_terms):
-            # (rgb_act / differentiable_normals changed after construction, a model without _field, ...)
-            raise RuntimeError(f"{asked}: render() did not take the fused tail (rendering._fused_tail_ok); the targets would "
-                               "be left out of the loss")
-        if sky_on and '_loss_terms' not in results:
-            raise RuntimeError("use_skybox=True: render() did not take the fused tail (rendering._fused_tail_ok); the step "
-                               "would run without its skybox kernels")
-        if nref and ('_loss_terms' not in results or '_ref_terms' not in results):
-            raise RuntimeError("normal_ref=True: render() did not take the fused tail with its normal_ref launch "
-                               "(rendering._fused_tail_ok); the two terms would be left out of the loss")
+        recipe.check_took_fused_tail(results, extra.get('_fused_loss'), sky_on)
         if '_loss_terms' in results:
             terms = results.pop('_loss_terms')
             loss = terms[0]
@@ -821,7 +552,7 @@ class NGPTrainer:
             loss_d = self.loss_fn(results, batch, **kw)
             if exposure is not None:
                 unit = self._unit_exposure_rgb()
-                loss_d['unit_exposure'] = 0.5 * (unit - self.unit_exposure_rgb) ** 2
+                loss_d['unit_exposure'] = 0.5 * (unit - recipe.unit_exposure_rgb) ** 2
             loss = sum(lo.mean() for lo in loss_d.values())
             if exposure is not None:
                 # [loss, rgb, opacity, distortion, (the optional terms of loss_kwargs, in NeRFLoss's order,) unit_exposure]

@@ -663,7 +663,7 @@ def trainer_against_module(ngp, terms, fused_kw, lr, tracked, after_step=None):
         model = _grid_buffers(ngp.networks.NGP(scale=0.5).to(DEV))
         start = params(model)[2:]
         tr = NGPTrainer(model, lr=lr, **(fused_kw if fused else dict(loss_kwargs=module_kw)))
-        assert tr.fused_loss == fused
+        assert tr.recipe.fused_loss == fused
         torch.manual_seed(53)
         steps = []
         for o, d, gt, tg in batches:

@@ -203,7 +203,7 @@ def test_trainer_depth_route_matches_module_route(ngp):
     why not 1e-2), within the bars of the semantic and normal counterparts: losses rtol 1e-3, parameters rtol 5e-3 / atol
     5e-5.  The fused route keeps the norm-bound clip (the term reaches the parameters through d_sigmas alone)."""
     runs = trainer_against_module(ngp, ("depth_mono",), dict(depth_mono=True), TRAJ_LR, ("xyz_encoder.params",))
-    assert runs[True]["tr"].depth_mono and not runs[False]["tr"].depth_mono
+    assert runs[True]["tr"].recipe.depth_mono and not runs[False]["tr"].recipe.depth_mono
     steps = runs[True]["steps"]
     assert all(s[1]["loss_terms"].shape == (5,) for s in steps)
     dm = [float(s[1]["loss_terms"][4]) for s in steps]

@@ -294,12 +294,11 @@ def test_trainer_refuses_what_the_depth_tail_does_not_cover(ngp):
 def test_step_checks_the_depths_argument(ngp):
     """step()'s checks of depths= come before anything touches the device: a missing, misshapen or integer depths=, a
     target= beside it, CPU tensors, and depths= handed to a trainer without the flag"""
+    from ngp_amd.recipe import Recipe
     from ngp_amd.trainer import NGPTrainer
 
     class _Trainer:          # what step() looks at before its first launch
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = False
-        depth_mono = True
+        model, recipe = None, Recipe(depth_mono=True)
     o, d, gt = torch.zeros(6, 3), torch.ones(6, 3), torch.zeros(6, 3)
     good = torch.ones(6)
     with pytest.raises(ValueError, match="needs depths="):
@@ -314,6 +313,6 @@ def test_step_checks_the_depths_argument(ngp):
     with pytest.raises(RuntimeError, match="CUDA"):
         NGPTrainer.step(_Trainer(), o, d, gt, depths=good)
     plain = _Trainer()
-    plain.depth_mono = False
+    plain.recipe = Recipe()
     with pytest.raises(ValueError, match="depths= is for"):
         NGPTrainer.step(plain, o, d, gt, depths=good)

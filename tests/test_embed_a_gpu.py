@@ -266,7 +266,7 @@ def test_trainer_owns_the_table(ngp):
     assert emb.weight.data_ptr() == tr.flat_param[off:].data_ptr()
     assert emb.weight.grad.data_ptr() == tr.flat_grad[off:].data_ptr()
     assert tr.model.link.grad_sinks["embedding_a"].data_ptr() == tr.flat_grad[off:].data_ptr()
-    assert tr.fused_loss is True and tr.norm_bound is True
+    assert tr.recipe.fused_loss is True and tr.norm_bound is True
     assert np.isfinite(losses).all()
     assert torch.isfinite(tr.flat_param).all()
     w = emb.weight.detach()

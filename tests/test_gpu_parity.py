@@ -1593,7 +1593,7 @@ def test_trainer_fused_loss_path_matches_module_path(ngp):
         coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=DEV)] * 3, indexing="ij"), -1)
         model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
         tr = NGPTrainer(model, lr=1e-2)
-        tr.fused_loss = fused
+        tr.recipe.fused_loss = fused
         torch.manual_seed(53)
         losses = [float(tr.step(o, d, gt)[0]) for o, d, gt in batches]
         tr.wait()
@@ -2336,7 +2336,7 @@ def test_trainer_checkpoint_roundtrip_and_optional_losses(ngp, tmp_path):
         assert dist <= 1.01e-2, (k, dist)          # one Adam step (lr 1e-2) away from the CHECKPOINT values
     # optional loss terms through the trainer
     tr2 = NGPTrainer(model, lr=1e-2, loss_kwargs={"normal_mono": True, "semantic": True})
-    assert not tr2.fused_loss
+    assert not tr2.recipe.fused_loss
     tr2.global_step = 1
     target = {"normal": T(g.normal(size=(n_rays, 3)).astype(np.float32)),
               "label": torch.randint(0, 7, (n_rays,), device=DEV)}
@@ -2347,7 +2347,7 @@ def test_trainer_checkpoint_roundtrip_and_optional_losses(ngp, tmp_path):
     assert torch.isfinite(loss) and not torch.equal(before, model.semantic_header.params)
     # normal_ref: the trainer switches the field to differentiable normals; without that NeRFLoss refuses
     tr3 = NGPTrainer(model, lr=1e-2, loss_kwargs={"normal_ref": True})
-    assert model.differentiable_normals and not tr3.fused_loss
+    assert model.differentiable_normals and not tr3.recipe.fused_loss
     tr3.global_step = 1
     loss, _ = tr3.step(o, d, gt)
     tr3.wait()

@@ -306,7 +306,7 @@ def test_trainer_with_a_mask_model(ngp, tmp_path):
         orig = tr.optimizer_step
 
         def spy():
-            seen["bound"], seen["fused"] = tr._bound_step, tr.fused_loss
+            seen["bound"], seen["fused"] = tr._bound_step, tr.recipe.fused_loss
             orig()
         tr.optimizer_step = spy
         loss, res = tr.step(o, d, gt, uvi=uvi)
@@ -315,7 +315,7 @@ def test_trainer_with_a_mask_model(ngp, tmp_path):
         assert "_loss_terms" not in res and res["rgb"].shape == (2048, 3)
         losses.append(float(loss))
     tr.wait()
-    assert tr.fused_loss is True
+    assert tr.recipe.fused_loss is True
     assert np.isfinite(losses).all()
     assert np.mean(losses[-4:]) < np.mean(losses[:4])
     assert torch.isfinite(tr.flat_param).all()

@@ -296,7 +296,7 @@ def test_trainer_multi_route_matches_module_route(ngp):
                                   after_step=exact_norm)
     for fused, run in runs.items():
         tr = run["tr"]
-        assert tr.multi_terms == (ALL if fused else ()) and not (tr.semantic or tr.normal_mono or tr.depth_mono)
+        assert tr.recipe.multi_terms == (ALL if fused else ()) and not (tr.recipe.semantic or tr.recipe.normal_mono or tr.recipe.depth_mono)
     steps = runs[True]["steps"]
     assert all(s[1]["loss_terms"].shape == (8,) for s in steps)
     opt = np.stack([N(s[1]["loss_terms"])[4:] for s in steps])

@@ -276,13 +276,15 @@ def test_trainer_refuses_what_the_multi_tail_does_not_cover(ngp):
 
 def test_step_checks_the_targets(ngp):
     """step()'s checks come before anything touches the device: exactly the named terms' targets, their shapes and dtypes,
-    no target= and no per-step loss term, CUDA tensors; a trainer without the new attribute keeps the old messages"""
+    no target= and no per-step loss term, CUDA tensors; the default recipe keeps the single flags' messages"""
+    from ngp_amd.recipe import Recipe
     from ngp_amd.trainer import NGPTrainer
 
     class _Trainer:          # what step() looks at before its first launch
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = depth_mono = False
-        multi_terms = ALL
+        model = None
+
+        def __init__(self, **options):
+            self.recipe = Recipe(**options) if options else Recipe(multi_terms=ALL)
     o, d, gt = torch.zeros(6, 3), torch.ones(6, 3), torch.zeros(6, 3)
     lab, nrm, dep = torch.zeros(6, dtype=torch.int64), torch.ones(6, 3), torch.ones(6)
     full = dict(labels=lab, normals=nrm, depths=dep)
@@ -304,16 +306,14 @@ def test_step_checks_the_targets(ngp):
     with pytest.raises(RuntimeError, match="CUDA"):
         NGPTrainer.step(_Trainer(), o, d, gt, **full)
     # a target of a term that is not named is refused with the single flags' message
-    two = _Trainer()
-    two.multi_terms = ("normal_mono", "depth_mono")
+    two = _Trainer(multi_terms=("normal_mono", "depth_mono"))
     with pytest.raises(ValueError, match="labels= is for"):
         NGPTrainer.step(two, o, d, gt, **full)
     with pytest.raises(RuntimeError, match="CUDA"):
         NGPTrainer.step(two, o, d, gt, normals=nrm, depths=dep)
 
-    class _Old:          # the stand-ins of the sibling suites carry only the single flags
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = depth_mono = False
+    class _Old:          # the default recipe
+        model, recipe = None, Recipe()
     for kw, msg in ((dict(labels=lab), "labels= is for"), (dict(normals=nrm), "normals= is for"), (dict(depths=dep), "depths= is for")):
         with pytest.raises(ValueError, match=msg):
             NGPTrainer.step(_Old(), o, d, gt, **kw)

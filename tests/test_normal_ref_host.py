@@ -125,13 +125,11 @@ def test_trainer_refuses_what_normal_ref_does_not_cover(ngp):
 
 
 def test_step_checks_come_before_the_device(ngp):
+    from ngp_amd.recipe import Recipe
     from ngp_amd.trainer import NGPTrainer
 
     class _Ref:          # what step() looks at before its first launch
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = depth_mono = use_exposure = use_skybox = False
-        multi_terms = ()
-        normal_ref = True
+        model, recipe = None, Recipe(normal_ref=True)
         warmup_steps, global_step = 256, 0
     o, d, gt = torch.zeros(6, 3), torch.ones(6, 3), torch.zeros(6, 3)
     with pytest.raises(ValueError, match="normal_ref=True: the step stays on the fused render \\+ loss tail"):

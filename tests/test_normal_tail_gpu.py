@@ -208,7 +208,7 @@ def test_trainer_normal_route_matches_module_route(ngp):
     head = "norm_pred_header.params"
     runs = trainer_against_module(ngp, ("normal_mono",), dict(normal_mono=True), TRAJ_LR, (head,))
     for fused, run in runs.items():
-        assert run["tr"].normal_mono == fused
+        assert run["tr"].recipe.normal_mono == fused
         moved = np.abs(run["end"][head] - run["start"][head]).max()
         print(f"FIG trainer {'fused' if fused else 'module'}: norm_pred_header moved by at most {moved:.3g}")
         assert moved > 3 * TRAJ_LR          # the head was trained: Adam moves a parameter by about lr per step
@@ -296,7 +296,7 @@ def test_train_dataset_with_normals_end_to_end(ngp, tmp_path):
         model = td.build_model(0.5, DEV)
         tr = td.train(model, train_set, num_epochs=3, steps_per_epoch=200, batch_size=2048, lr=1e-2, normal_mono=True,
                       lambda_normal_mono=lam)
-        assert tr.global_step == 600 and tr.normal_mono and tr.loss_fn.lambda_normal_mono == (1e-3 if lam is None else 0.0)
+        assert tr.global_step == 600 and tr.recipe.normal_mono and tr.loss_fn.lambda_normal_mono == (1e-3 if lam is None else 0.0)
         res = evaluate_split(model, test_set)
         assert len(res["normal_deg"]) == 5 and all(np.isfinite(res["normal_deg"]))
         runs[tag] = (sum(res["psnr"]) / 5, normal_summary(res), res["normal_deg"], res["psnr"])

@@ -376,7 +376,7 @@ def test_one_step_against_torch_autograd(ngp, recipe):
     emb = torch.nn.Embedding(3, 4).to(DEV) if full else None
     msk = implicit_mask().to(DEV) if full else None
     tr = NGPTrainer(model, pose_refiner=ref, embedding_a=emb, msk_model=msk)
-    assert tr.fused_loss and ref.dR.data_ptr() == tr.pose_param.data_ptr() and ref.dR.data_ptr() % 16 == 0
+    assert tr.recipe.fused_loss and ref.dR.data_ptr() == tr.pose_param.data_ptr() and ref.dR.data_ptr() % 16 == 0
     assert ref.dT.data_ptr() % 16 == 0 and "dR" not in tr.names and not any("pose" in n for n in tr.names)
     gen = torch.Generator(device=DEV).manual_seed(72)
     with torch.no_grad():

@@ -197,7 +197,7 @@ def test_trainer_semantic_route_matches_module_route(ngp):
     head = "semantic_header.params"
     runs = trainer_against_module(ngp, ("semantic",), dict(semantic=True), 1e-2, (head,))
     for fused, run in runs.items():
-        assert run["tr"].semantic == fused
+        assert run["tr"].recipe.semantic == fused
         assert np.abs(run["end"][head] - run["start"][head]).max() > 1e-3          # the head was trained
 
 
@@ -287,7 +287,7 @@ def test_train_dataset_with_labels_end_to_end(ngp, tmp_path, fmt):
     torch.manual_seed(43)
     model = td.build_model(2.0, DEV, num_classes=C)
     tr = td.train(model, train_set, num_epochs=3, steps_per_epoch=200, batch_size=2048, lr=1e-2, semantic=True, num_classes=C)
-    assert tr.global_step == 600 and tr.semantic and train_set.labels.shape == (29, 80 * 80)
+    assert tr.global_step == 600 and tr.recipe.semantic and train_set.labels.shape == (29, 80 * 80)
     res = evaluate_split(model, test_set, num_classes=C)
     psnrs = res["psnr"]
     assert len(psnrs) == 5 and sum(psnrs) / 5 > 20.0, psnrs

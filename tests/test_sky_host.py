@@ -199,22 +199,24 @@ def test_trainer_refuses_what_use_skybox_does_not_cover(ngp):
 def test_warmup_gate_and_step_checks(ngp):
     """the skybox joins at global_step >= warmup_steps (train.py:160); step()'s checks come before anything touches the
     device"""
+    from ngp_amd.recipe import Recipe
     from ngp_amd.trainer import NGPTrainer
 
     class _Sky:          # what step() looks at before its first launch
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = depth_mono = use_exposure = False
-        multi_terms = ()
-        use_skybox = True
+        model = None
         warmup_steps, global_step = 256, 0
 
-    class _Old:          # the stand-ins of the sibling suites do not carry the flag
+        def __init__(self):
+            self.recipe = Recipe(use_skybox=True)
+
+    class _Old:          # the default recipe
+        recipe = Recipe()
         warmup_steps, global_step = 256, 1000
     tr = _Sky()
     for step, on in ((0, False), (255, False), (256, True), (257, True), (10 ** 6, True)):
         tr.global_step = step
         assert NGPTrainer.sky_active(tr) is on, step
-    tr.use_skybox = False
+    tr.recipe.use_skybox = False
     assert NGPTrainer.sky_active(tr) is False and NGPTrainer.sky_active(_Old()) is False
     o, d, gt = torch.zeros(6, 3), torch.ones(6, 3), torch.zeros(6, 3)
     for step in (0, 300):

@@ -355,7 +355,7 @@ def test_trainer_step_against_the_step_composed_by_hand(ngp):
     # switches it) fills loss_terms with the same five terms
     c = _field_model(ngp, 71)
     tr_c = NGPTrainer(c, lr=1e-2, use_exposure=True, unit_exposure_rgb=UNIT)
-    tr_c.fused_loss = False
+    tr_c.recipe.fused_loss = False
     tr_c.optimizer_step = lambda: None
     torch.manual_seed(73)
     loss_c, res_c = tr_c.step(o, d, gt, exposure=e.reshape(-1, 1))

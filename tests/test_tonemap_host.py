@@ -197,20 +197,17 @@ def test_trainer_refuses_what_use_exposure_does_not_cover(ngp):
 
 def test_step_checks_the_exposure(ngp):
     """step()'s checks come before anything touches the device"""
+    from ngp_amd.recipe import Recipe
     from ngp_amd.trainer import NGPTrainer
 
     class _Plain:          # what step() looks at before its first launch
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = depth_mono = False
-        multi_terms = ()
-        use_exposure = False
+        model, recipe = None, Recipe(use_exposure=False)
 
     class _Hdr(_Plain):
-        use_exposure = True
+        recipe = Recipe(use_exposure=True)
 
-    class _Old:          # the stand-ins of the sibling suites do not carry the flag
-        model = msk_model = embedding_a = pose_refiner = None
-        semantic = normal_mono = depth_mono = False
+    class _Old:          # the default recipe
+        model, recipe = None, Recipe()
     o, d, gt, e = torch.zeros(6, 3), torch.ones(6, 3), torch.zeros(6, 3), torch.ones(6, 1)
     for tr in (_Plain(), _Old()):
         with pytest.raises(ValueError, match="exposure= is for a trainer built with use_exposure=True"):

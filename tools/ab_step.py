@@ -3,7 +3,7 @@
 training steps with the switch off / on (box-to-box and run-to-run spread of bench.py is +-3 %, more than most single
 changes are worth; alternating inside one process removes it).
 
-    python tools/ab_step.py fused_loss            # NGPTrainer attribute toggled False / True
+    python tools/ab_step.py fused_loss            # attribute of the trainer's recipe (or of the trainer) toggled False / True
     AB_WINDOWS=12 AB_STEPS=40 python tools/ab_step.py fused_loss"""
 import os
 import sys
@@ -46,7 +46,7 @@ for _ in range(int(os.environ.get("AB_PRETRAIN", "600"))):
 
 
 def set_switch(on):
-    setattr(tr, what, on)
+    setattr(tr.recipe if hasattr(tr.recipe, what) else tr, what, on)
 
 
 def window(i0):

@@ -145,7 +145,7 @@ def main():
     print(json.dumps({"rays": args.rays, "steps_total": k, "loss": float(loss), "samples_last": int(np.median(samples)),
                       **{f"{leg}_ms_per_step_median": round(median(v), 4) for leg, v in windows.items()},
                       **{f"{leg}_ms_per_step_windows": [round(x, 4) for x in v] for leg, v in windows.items()},
-                      "fused_loss": tr.fused_loss, "norm_bound": tr.norm_bound}))
+                      "fused_loss": tr.recipe.fused_loss, "norm_bound": tr.norm_bound}))
 
 
 if __name__ == "__main__":

@@ -41,11 +41,11 @@ SHARE = ("grid_bwd_bwd_input", "linear_fwd", "density_head_bwd2", "linear_bwd_we
 
 
 def set_leg(tr, leg):
-    tr.normal_ref = leg == "fused"
+    tr.recipe.normal_ref = leg == "fused"
     tr.model.second_order_normals = leg == "fused"
     tr.model.differentiable_normals = leg == "module"
     tr.loss_kwargs = {"normal_ref": True} if leg == "module" else {}
-    tr.fused_loss = leg != "module"
+    tr.recipe.fused_loss = leg != "module"
 
 
 def median(v):

@@ -146,7 +146,7 @@ def main():
     print(json.dumps({"leg": args.leg, "rays": args.rays, "steps_total": k, "loss": float(loss),
                       "ms_per_step_median": round(sorted(windows)[len(windows) // 2], 4),
                       "ms_per_step_windows": [round(w, 4) for w in windows],
-                      "fused_loss": tr.fused_loss, "semantic": tr.semantic, "norm_bound": tr.norm_bound}))
+                      "fused_loss": tr.recipe.fused_loss, "semantic": tr.recipe.semantic, "norm_bound": tr.norm_bound}))
 
 
 if __name__ == "__main__":

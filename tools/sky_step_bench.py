@@ -38,7 +38,7 @@ LEGS = ("default", "module", "fused")
 
 
 def set_leg(tr, leg):
-    tr.use_skybox = leg == "fused"
+    tr.recipe.use_skybox = leg == "fused"
     tr.render_kwargs = {"use_skybox": True} if leg == "module" else {}
 
 

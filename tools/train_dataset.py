@@ -49,6 +49,7 @@ from ngp_amd.implicit_mask import implicit_mask
 from ngp_amd.metrics import psnr
 from ngp_amd.networks import NGP
 from ngp_amd.pose import PoseRefiner, perturb_poses, pose_errors
+from ngp_amd.recipe import conflicts
 from ngp_amd.rendering import MULTI_TERMS
 from ngp_amd.trainer import NGPTrainer
 
@@ -145,19 +146,9 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
             raise ValueError("--use_exposure needs an exposure time per ray: the dataset has none (the colmap loader reads "
                              "them for the HDR-NeRF layouts)")
         more.update(use_exposure=True, unit_exposure_rgb=train_set.unit_exposure_rgb)
-    if use_skybox:
-        more.update(use_skybox=True)
-    if normal_ref:
-        more.update(normal_ref=True)
-    if multi_terms:
-        more.update(multi_terms=multi_terms)
-    else:
-        if semantic:
-            more.update(semantic=True)
-        if normal_mono:
-            more.update(normal_mono=True)
-        if depth_mono:
-            more.update(depth_mono=True)
+    more.update(use_skybox=use_skybox, normal_ref=normal_ref, multi_terms=multi_terms)
+    if not multi_terms:
+        more.update(semantic=semantic, normal_mono=normal_mono, depth_mono=depth_mono)
     trainer = NGPTrainer(model, lr=lr, num_epochs=num_epochs, steps_per_epoch=steps_per_epoch,
                          exp_step_factor=exp_step_factor, render_kwargs=render_kwargs, msk_model=msk_model, **more)
     if lambda_normal_mono is not None:
@@ -197,17 +188,7 @@ def train(model, train_set, num_epochs, steps_per_epoch, batch_size, lr, log_eve
     t0 = time.perf_counter()
     for i in range(total):
         nxt = next_batch() if i + 1 < total else None
-        more = {} if cur[4] is None else {"img_idxs": cur[4]}
-        if cur[5] is not None:
-            more["pix_idxs"] = cur[5]
-        if cur[6] is not None:
-            more["labels"] = cur[6]
-        if cur[7] is not None:
-            more["normals"] = cur[7]
-        if cur[8] is not None:
-            more["depths"] = cur[8]
-        if cur[9] is not None:
-            more["exposure"] = cur[9]
+        more = {k: v for k, v in zip(("img_idxs", "pix_idxs", "labels", "normals", "depths", "exposure"), cur[4:]) if v is not None}
         ahead = None if nxt is None or pose_refiner is not None else nxt[:2]
         loss, res = trainer.step(*cur[:3], next_rays=ahead, uvi=cur[3], **more)
         if depth_mono or multi_terms or use_exposure or normal_ref:
@@ -260,6 +241,21 @@ def evaluate(model, test_set, chunk=131072, save_dir=None, exp_step_factor=0.0):
     """per-image PSNR of the test split through render(test_time=True) (train.py:347-392)"""
     return evaluate_split(model, test_set, chunk, on_image=_save_rgb(save_dir, test_set.img_wh) if save_dir else None,
                           exp_step_factor=exp_step_factor)["psnr"]
+
+
+# flag -> the trainer's option (or the condition of recipe.py) it stands for
+FLAG_OPTIONS = dict({f: f for f in ("use_exposure", "normal_mono", "depth_mono", "multi_terms", "use_skybox", "normal_ref")},
+                    embed_msk="msk_model", optimize_ext="pose_refiner", render_semantic="semantic")
+# flag -> (the --dataset_name layouts --make_proxy can write its scene in, what that scene is)
+PROXY_LAYOUTS = {
+    "normal_ref": (("tnt",), "the scene in the tnt layout"),
+    "multi_terms": (("tnt",), "a scene with labels, normal and depth maps (the layout that carries all three)"),
+    "depth_mono": (("tnt",), "a scene with depth maps (the layout that carries depth/*.npy)"),
+    "normal_mono": (("tnt",), "a scene with normal maps (the layout that carries normal/*.npy)"),
+    "use_skybox": (("tnt",), "the scene over the analytic sky (the layout whose images carry their background)"),
+    "use_exposure": (("colmap",), "the HDR-NeRF synthetic layout (the loader that reads it)"),
+    "render_semantic": (("tnt", "colmap"), "a labelled scene (the layouts that carry semantic/*.pgm)"),
+}
 
 
 def parse_args(argv=None):
@@ -329,56 +325,18 @@ def parse_args(argv=None):
                          "test_normal_agree_deg_mean, the mean angle over the held-out pixels with opacity above 0.5 "
                          "between the rendered predicted normal and the rendered density normal")
     args = ap.parse_args(argv)
-    if args.make_proxy and args.normal_ref and args.dataset_name != "tnt":
-        ap.error("--make_proxy with --normal_ref writes the scene in the tnt layout: --dataset_name tnt")
-    if args.normal_ref and (args.embed_msk or args.optimize_ext or args.use_exposure or args.use_skybox or args.render_semantic
-                            or args.normal_mono or args.depth_mono):
-        ap.error("--normal_ref combines with --multi_terms, --embed_a and --random_bg, not with --embed_msk, --optimize_ext, "
-                 "--use_exposure, --use_skybox or a single term's own flag (--render_semantic, --normal_mono, --depth_mono: "
-                 "name the term in --multi_terms)")
     args.multi_terms = tuple(t for t in MULTI_TERMS if t in args.multi_terms)
-    if args.multi_terms and (args.render_semantic or args.normal_mono or args.depth_mono):
-        ap.error("--multi_terms names the terms itself: not together with --render_semantic, --normal_mono or --depth_mono")
-    if args.multi_terms and (args.embed_msk or args.optimize_ext):
-        ap.error("--multi_terms combines with --embed_a and --random_bg, not with --embed_msk or --optimize_ext")
-    if args.make_proxy and args.multi_terms and args.dataset_name != "tnt":
-        ap.error("--make_proxy with --multi_terms writes a scene with labels, normal and depth maps: --dataset_name tnt "
-                 "(the layout that carries all three)")
-    if args.make_proxy and args.depth_mono and args.dataset_name != "tnt":
-        ap.error("--make_proxy with --depth_mono writes a scene with depth maps: --dataset_name tnt (the layout that "
-                 "carries depth/*.npy)")
-    if args.depth_mono and (args.embed_msk or args.optimize_ext or args.render_semantic or args.normal_mono):
-        ap.error("--depth_mono combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext, "
-                 "--render_semantic or --normal_mono")
-    if args.make_proxy and args.normal_mono and args.dataset_name != "tnt":
-        ap.error("--make_proxy with --normal_mono writes a scene with normal maps: --dataset_name tnt (the layout that "
-                 "carries normal/*.npy)")
-    if args.normal_mono and (args.embed_msk or args.optimize_ext or args.render_semantic):
-        ap.error("--normal_mono combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext or "
-                 "--render_semantic")
+    # what combines is the trainer's to say (recipe.py's table): everything goes with --embed_a and --random_bg
+    given = {opt: "--" + flag for flag, opt in FLAG_OPTIONS.items() if getattr(args, flag)}
+    for opt, refused in conflicts(given):
+        ap.error(f"{given[opt]} does not combine with {given[refused]}")
+    for flag, (layouts, what) in PROXY_LAYOUTS.items():
+        if args.make_proxy and getattr(args, flag) and args.dataset_name not in layouts:
+            ap.error(f"--make_proxy with --{flag} writes {what}: --dataset_name {' or '.join(layouts)}")
     if not 1 <= args.num_classes <= 16:
         ap.error("--num_classes must lie in [1, 16]")
-    if args.use_exposure and (args.embed_msk or args.optimize_ext or args.multi_terms or args.render_semantic
-                              or args.normal_mono or args.depth_mono):
-        ap.error("--use_exposure combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext or a term on "
-                 "the fused tail (--render_semantic, --normal_mono, --depth_mono, --multi_terms)")
-    if args.use_skybox and (args.embed_msk or args.optimize_ext or args.multi_terms or args.render_semantic
-                            or args.normal_mono or args.depth_mono or args.use_exposure):
-        ap.error("--use_skybox combines with --embed_a and --random_bg, not with --embed_msk, --optimize_ext, --use_exposure or "
-                 "a term on the fused tail (--render_semantic, --normal_mono, --depth_mono, --multi_terms)")
-    if args.make_proxy and args.use_skybox and args.dataset_name != "tnt":
-        ap.error("--make_proxy with --use_skybox writes the scene over the analytic sky: --dataset_name tnt (the layout "
-                 "whose images carry their background)")
-    if args.make_proxy and args.use_exposure and args.dataset_name != "colmap":
-        ap.error("--make_proxy with --use_exposure writes the HDR-NeRF synthetic layout: --dataset_name colmap (the loader "
-                 "that reads it)")
-    if args.make_proxy and args.render_semantic and args.dataset_name not in ("tnt", "colmap"):
-        ap.error("--make_proxy with --render_semantic writes a labelled scene: --dataset_name tnt or colmap (the layouts "
-                 "that carry semantic/*.pgm)")
     if args.scale is None:
         args.scale = 2.0 if args.make_proxy and (args.render_semantic or "semantic" in args.multi_terms) else 0.5
-    if args.render_semantic and (args.embed_msk or args.optimize_ext):
-        ap.error("--render_semantic combines with --embed_a and --random_bg, not with --embed_msk or --optimize_ext")
     if not 1 <= args.embed_a_len <= 32:
         ap.error("--embed_a_len must lie in [1, 32]")
     if args.perturb_poses and not args.optimize_ext:
