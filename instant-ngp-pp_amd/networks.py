@@ -741,6 +741,15 @@ class NGP(nn.Module):
                     network_config={"otype": "CutlassMLP", "activation": "ReLU", "output_activation": "Sigmoid",
                                     "n_neurons": 64, "n_hidden_layers": 1}, seed=1343 + i))
 
+    def add_occupancy_grid(self):
+        """registers the two buffers a trainer adds to the model (the reference's train.py:128-132): density_grid
+        (cascades, G^3) float32 zeros and grid_coords (G^3, 3) int32, on the device the model is on.  -> self"""
+        G, dev = self.grid_size, self.density_bitfield.device
+        self.register_buffer("density_grid", torch.zeros(self.cascades, G ** 3, device=dev))
+        coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=dev)] * 3, indexing="ij"), -1)
+        self.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
+        return self
+
     # ------------------------------------------------------------------ density / normals
     def _density_head(self, feat):
         """feat (N,128) -> sigma (N) through autograd-visible layers (used when a caller wants

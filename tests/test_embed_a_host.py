@@ -145,15 +145,16 @@ def test_header_prototypes_parse(ngp):
     ("render.py", ("--embed_a", "--embed_a_len", "--embed_a_mode")),
     ("render_panorama.py", ("--embed_a", "--embed_a_len")),
     ("extract_mesh.py", ("--embed_a", "--embed_a_len")),
-    ("embed_a_step_bench.py", ("--leg", "--solo")),
+    pytest.param("step_bench.py embed_a", ("--leg", "--solo"), id="step_bench.py-embed_a"),
 ])
 def test_tools_accept_the_new_flags(tool, flags):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool), "--help"], capture_output=True, text=True,
+    tool, *recipe = tool.split()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool), *recipe, "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     for f in flags:
         assert f in out.stdout, (tool, f)
     if tool == "render.py":
         assert "{mean,nearest,index}" in out.stdout
-    if tool == "embed_a_step_bench.py":
+    if recipe == ["embed_a"]:
         assert "{none,tensor,fused}" in out.stdout

@@ -22,11 +22,7 @@ windows = int(os.environ.get("AB_WINDOWS", "10"))
 steps = int(os.environ.get("AB_STEPS", "48"))
 dev = torch.device("cuda", 0)
 torch.manual_seed(20220806)
-model = NGP(scale=0.5).to(dev)
-G = model.grid_size
-model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=dev))
-coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=dev)] * 3, indexing="ij"), -1)
-model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
+model = NGP(scale=0.5).to(dev).add_occupancy_grid()
 model.grid_rng = torch.Generator(device=dev).manual_seed(20220806)
 scene = LegoProxy(device=dev)
 tr = NGPTrainer(model)

@@ -18,11 +18,7 @@ ap.add_argument("--steps", type=int, nargs="+", default=[100, 600, 2000, 6000])
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(20220806)
-model = NGP(scale=0.5).to(dev)
-G = model.grid_size
-model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=dev))
-coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=dev)] * 3, indexing="ij"), -1)
-model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
+model = NGP(scale=0.5).to(dev).add_occupancy_grid()
 scene = LegoProxy(img_wh=(800, 800), device=dev)
 tr = NGPTrainer(model, lr=1e-2)
 gen = torch.Generator(device=dev).manual_seed(1)

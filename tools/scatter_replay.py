@@ -72,11 +72,7 @@ if cap_file and os.path.exists(cap_file):
     launches = torch.load(cap_file, map_location=dev, weights_only=False)
     replay(launches)
     raise SystemExit(0)
-model = NGP(scale=0.5).to(dev)
-G = model.grid_size
-model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=dev))
-coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=dev)] * 3, indexing="ij"), -1)
-model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
+model = NGP(scale=0.5).to(dev).add_occupancy_grid()
 scene = LegoProxy(n_images=100, img_wh=(800, 800), device=dev, seed=20220806)
 tr = NGPTrainer(model)
 gen = torch.Generator(device=dev).manual_seed(20220806)

@@ -60,11 +60,7 @@ def build_model(scale, device, embed_a=False, embed_a_len=4, num_classes=7, use_
         more["use_skybox"] = True
     if use_exposure:   # log-radiance and the three tone-mappers (train.py:99)
         more["rgb_act"] = "None"
-    model = NGP(scale=scale, classes=num_classes, **more).to(device)
-    G = model.grid_size
-    model.register_buffer("density_grid", torch.zeros(model.cascades, G ** 3, device=device))
-    coords = torch.stack(torch.meshgrid(*[torch.arange(G, dtype=torch.int32, device=device)] * 3, indexing="ij"), -1)
-    model.register_buffer("grid_coords", coords.reshape(-1, 3).contiguous())
+    model = NGP(scale=scale, classes=num_classes, **more).to(device).add_occupancy_grid()
     return model
 
 
