@@ -492,68 +492,6 @@ __global__ void __launch_bounds__(256) nerf_loss_kernel(const float* __restrict_
     }
 }
 
-// ---- W-lane groups (W = 32: a half-wave, W = 64: a whole wave per ray) for the fused kernel below ------------------
-template <int W> __device__ __forceinline__ float grp_sum(float v)
-{
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, W);
-    return v;
-}
-template <int W> __device__ __forceinline__ float grp_scan_add(float v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < W; o <<= 1) {
-        const float u = __shfl_up(v, o, W);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-template <int W> __device__ __forceinline__ float grp_scan_mul(float v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < W; o <<= 1) {
-        const float u = __shfl_up(v, o, W);
-        if (lane >= o) v *= u;
-    }
-    return v;
-}
-template <int W> __device__ __forceinline__ int grp_first(unsigned long long ballot, int lane64)
-{
-    if (W == 64) return ballot ? (int)__builtin_ctzll(ballot) : -1;
-    const unsigned m = (unsigned)(ballot >> (lane64 & 32));
-    return m ? (__ffs((int)m) - 1) : -1;
-}
-template <int W> __device__ __forceinline__ bool seg_load_w(const int64_t* __restrict__ rays_a, int n_rays, Seg& s, int& lane)
-{
-    const int gtid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int row = gtid / W;
-    lane = threadIdx.x & (W - 1);
-    if (row >= n_rays) return false;
-    s.ray = rays_a[3 * (size_t)row];
-    s.start = rays_a[3 * (size_t)row + 1];
-    s.n = (int)rays_a[3 * (size_t)row + 2];
-    return true;
-}
-template <int W> __device__ __forceinline__ Chunk chunk_alpha_w(const float* __restrict__ sigmas, const float* __restrict__ deltas,
-                                                                int64_t s, bool valid, float T_run, float T_thr, int lane)
-{
-    Chunk c;
-    c.valid = valid;
-    const float sig = valid ? sigmas[s] : 0.0f;
-    const float dl = valid ? deltas[s] : 0.0f;
-    c.a = valid ? 1.0f - __expf(-sig * dl) : 0.0f;
-    const float om = 1.0f - c.a;
-    const float pin = grp_scan_mul<W>(om, lane);
-    float pex = __shfl_up(pin, 1, W);
-    if (lane == 0) pex = 1.0f;
-    c.T_before = T_run * pex;
-    c.T_after = T_run * pin;
-    const bool stopped = valid && (c.T_after <= T_thr);
-    c.first = grp_first<W>(__ballot(stopped), threadIdx.x & 63);
-    c.active = valid && (c.first < 0 || lane <= c.first);
-    return c;
-}
-
 // ------------------------------------------------------------------ fused render + default loss + its gradients
 // Everything between the field's raw outputs and the field's backward on the default recipe (rendering.py:221-249,
 // losses.py:96-105, train.py:307), per ray, in ONE launch (it replaces -normalize x2, softmax, composite_train_fw,
@@ -687,17 +625,17 @@ __global__ void __launch_bounds__(256) depth_fit_kernel(const float* __restrict_
                                                         const float* __restrict__ depth_gt, int n_rays, float T_thr,
                                                         int* __restrict__ dep_ws)
 {
-    constexpr int W = 32, RPB = 256 / W;
+    constexpr int RPB = 256 / 32;
     __shared__ float part_d[RPB], part_z[RPB];
     Seg sg; int lane;
-    const bool have = seg_load_w<W>(rays_a, n_rays, sg, lane);
+    const bool have = seg_load(rays_a, n_rays, sg, lane);
     float aD = 0.0f, z = 0.0f;
     if (have) {
         float T_run = 1.0f;
-        for (int k0 = 0; k0 < sg.n; k0 += W) {
+        for (int k0 = 0; k0 < sg.n; k0 += 32) {
             const int k = k0 + lane;
             const int64_t s = sg.start + k;
-            const Chunk c = chunk_alpha_w<W>(sigmas, deltas, s, k < sg.n, T_run, T_thr, lane);
+            const Chunk c = chunk_alpha(sigmas, deltas, s, k < sg.n, T_run, T_thr, lane);
             const float w = c.active ? c.a * c.T_before : 0.0f;
             float tt = 0.0f;
             if (c.valid) tt = ts[s];
@@ -708,14 +646,14 @@ __global__ void __launch_bounds__(256) depth_fit_kernel(const float* __restrict_
                 if (c.active) aD += w * tt;
             }
             if (c.first >= 0) break;
-            T_run = __shfl(c.T_after, W - 1, W);
+            T_run = __shfl(c.T_after, 31, 32);
         }
-        aD = grp_sum<W>(aD);
+        aD = half_sum(aD);
         z = depth_gt[sg.ray] / 25.0f;
     }
-    if ((threadIdx.x & (W - 1)) == 0) {
-        part_d[threadIdx.x / W] = aD;
-        part_z[threadIdx.x / W] = z > 0.0f ? z : 0.0f;   // (0: the ray takes no part; NaN compares false)
+    if ((threadIdx.x & 31) == 0) {
+        part_d[threadIdx.x / 32] = aD;
+        part_z[threadIdx.x / 32] = z > 0.0f ? z : 0.0f;   // (0: the ray takes no part; NaN compares false)
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -753,19 +691,20 @@ __global__ void __launch_bounds__(256) depth_fit_kernel(const float* __restrict_
 // SKY: the background is a colour per ray, bg[3 r + c] (the skybox's, rendering.py:236-241), and the launch also writes the
 // loss's gradient w.r.t. it, d_bg[r] = g_rgb (1 - opacity), for every row (a ray without samples: opacity 0, d_bg = g_rgb).
 // Everything else is the default form's arithmetic on bg0..2.
-template <int CMAX, int W, bool MASKED, bool SEM, bool NRM, bool DEP, bool SKY = false>
+template <int CMAX, bool MASKED, bool SEM, bool NRM, bool DEP, bool SKY = false>
 __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p)
 {
     static_assert(!(MASKED && (SEM || NRM || DEP)), "MASKED x SEM, MASKED x NRM and MASKED x DEP are not built");
     static_assert(!(SKY && (MASKED || SEM || NRM || DEP)), "SKY is built with the default terms only");
-    constexpr int RPB = 256 / W;          // rays per block
+    // rays per block, a half-wave each (a whole wave per ray was measured: 144 us per launch in the step against 85 -
+    // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
+    constexpr int RPB = 256 / 32;
     // one row of partials per active term behind the three of the default recipe: [ms] or [ce, sky][nm][dm]
     constexpr int ROW_SEM = 3, ROW_NRM = 3 + (SEM ? 2 : 0), ROW_DEP = ROW_NRM + (NRM ? 1 : 0);
-    constexpr bool MULTI = (SEM ? 1 : 0) + (NRM ? 1 : 0) + (DEP ? 1 : 0) > 1;
     __shared__ float part[MASKED ? 4 : ROW_DEP + (DEP ? 1 : 0)][RPB];
     __shared__ unsigned long long part_n[RPB];
     Seg sg; int lane;
-    const bool have = seg_load_w<W>(p.rays_a, p.n_rays, sg, lane);
+    const bool have = seg_load(p.rays_a, p.n_rays, sg, lane);
     float s_rgb = 0.0f, s_op = 0.0f, s_dist = 0.0f, s_ms = 0.0f, s_ce = 0.0f, s_sky = 0.0f, s_nm = 0.0f, s_dm = 0.0f;
     unsigned long long n_used = 0;
     const int n_valid = SEM ? p.sem_ws[SEM_WS_NVALID] : 0;
@@ -782,10 +721,10 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
         float w_run = 0, wt_run = 0, dacc = 0;
         int stop = -1;
         int k0 = 0;
-        for (; k0 < sg.n; k0 += W) {
+        for (; k0 < sg.n; k0 += 32) {
             const int k = k0 + lane;
             const int64_t s = sg.start + k;
-            const Chunk c = chunk_alpha_w<W>(p.sigmas, p.deltas, s, k < sg.n, T_run, p.T_thr, lane);
+            const Chunk c = chunk_alpha(p.sigmas, p.deltas, s, k < sg.n, T_run, p.T_thr, lane);
             const float w = c.active ? c.a * c.T_before : 0.0f;
             float tt = 0.0f, dl = 0.0f;
             if (c.valid) {
@@ -832,16 +771,16 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             }
             // distortion loss (losses.cu:8-59): inclusive scans of w and w t over the ray
             const float wt = w * tt;
-            const float wi = w_run + grp_scan_add<W>(w, lane);
-            const float wti = wt_run + grp_scan_add<W>(wt, lane);
-            float we = __shfl_up(wi, 1, W), wte = __shfl_up(wti, 1, W);
+            const float wi = w_run + half_incl_scan_add(w, lane);
+            const float wti = wt_run + half_incl_scan_add(wt, lane);
+            float we = __shfl_up(wi, 1, 32), wte = __shfl_up(wti, 1, 32);
             if (lane == 0) { we = w_run; wte = wt_run; }
             if (c.valid) dacc += 2 * (wti * we - wi * wte) + 1.0f / 3 * w * w * dl;
-            w_run = __shfl(wi, W - 1, W); wt_run = __shfl(wti, W - 1, W);
-            if (c.first >= 0) { stop = k0 + c.first; k0 += W; break; }
-            T_run = __shfl(c.T_after, W - 1, W);
+            w_run = __shfl(wi, 31, 32); wt_run = __shfl(wti, 31, 32);
+            if (c.first >= 0) { stop = k0 + c.first; k0 += 32; break; }
+            T_run = __shfl(c.T_after, 31, 32);
         }
-        for (; k0 < sg.n; k0 += W) {   // behind the stop: zero weight, zero gradients
+        for (; k0 < sg.n; k0 += 32) {   // behind the stop: zero weight, zero gradients
             const int k = k0 + lane;
             if (k < sg.n) {
                 const int64_t s = sg.start + k;
@@ -855,13 +794,13 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 if (NRM) { p.d_np[3 * s] = 0.0f; p.d_np[3 * s + 1] = 0.0f; p.d_np[3 * s + 2] = 0.0f; }
             }
         }
-        const int n_live = stop >= 0 ? (stop / W + 1) * W : sg.n;   // passes B and C stop behind the stop sample's chunk
-        aO = grp_sum<W>(aO); aD = grp_sum<W>(aD); aR = grp_sum<W>(aR); aG = grp_sum<W>(aG); aB = grp_sum<W>(aB);
-        aNx = grp_sum<W>(aNx); aNy = grp_sum<W>(aNy); aNz = grp_sum<W>(aNz);
-        aRo = grp_sum<W>(aRo); aPx = grp_sum<W>(aPx); aPy = grp_sum<W>(aPy); aPz = grp_sum<W>(aPz);
-        dacc = grp_sum<W>(dacc);
+        const int n_live = stop >= 0 ? (stop / 32 + 1) * 32 : sg.n;   // passes B and C stop behind the stop sample's chunk
+        aO = half_sum(aO); aD = half_sum(aD); aR = half_sum(aR); aG = half_sum(aG); aB = half_sum(aB);
+        aNx = half_sum(aNx); aNy = half_sum(aNy); aNz = half_sum(aNz);
+        aRo = half_sum(aRo); aPx = half_sum(aPx); aPy = half_sum(aPy); aPz = half_sum(aPz);
+        dacc = half_sum(dacc);
 #pragma unroll
-        for (int cc = 0; cc < CMAX; cc++) aS[cc] = grp_sum<W>(aS[cc]);
+        for (int cc = 0; cc < CMAX; cc++) aS[cc] = half_sum(aS[cc]);
         // ---------------- loss terms and gradient seeds of the ray
         // the image colour: composited colour over the background (black when bg == NULL)
         float fR = aR, fG = aG, fB = aB, bg0 = 0.0f, bg1 = 0.0f, bg2 = 0.0f;
@@ -973,44 +912,44 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
         float tot = 0.0f;
         if (gd != 0.0f) {
             float wr = 0, wtr = 0;
-            for (int q0 = 0; q0 < n_live; q0 += W) {
+            for (int q0 = 0; q0 < n_live; q0 += 32) {
                 const int k = q0 + lane;
                 const int64_t s = sg.start + k;
                 const bool valid = k < sg.n;
                 const float w = valid ? p.ws[s] : 0.0f, tt = valid ? p.ts[s] : 0.0f, dl = valid ? p.deltas[s] : 0.0f;
-                const float wi = wr + grp_scan_add<W>(w, lane);
-                const float wti = wtr + grp_scan_add<W>(w * tt, lane);
-                float we = __shfl_up(wi, 1, W), wte = __shfl_up(wti, 1, W);
+                const float wi = wr + half_incl_scan_add(w, lane);
+                const float wti = wtr + half_incl_scan_add(w * tt, lane);
+                float we = __shfl_up(wi, 1, 32), wte = __shfl_up(wti, 1, 32);
                 if (lane == 0) { we = wr; wte = wtr; }
                 const float dws = gd * 2 * ((tt * we - wte) + (wt_sum - wti - tt * (w_sum - wi))) + gd * 2.0f / 3 * w * dl;
                 tot += dws * w;
-                wr = __shfl(wi, W - 1, W); wtr = __shfl(wti, W - 1, W);
+                wr = __shfl(wi, 31, 32); wtr = __shfl(wti, 31, 32);
             }
-            tot = grp_sum<W>(tot);
+            tot = half_sum(tot);
         }
         // ---------------- pass C: composite_train_bw
         {
             float T2 = 1.0f, r_run = 0, g_run = 0, b_run = 0, p_run = 0, wr = 0, wtr = 0;
-            for (int q0 = 0; q0 < n_live; q0 += W) {
+            for (int q0 = 0; q0 < n_live; q0 += 32) {
                 const int k = q0 + lane;
                 const int64_t s = sg.start + k;
-                const Chunk c = chunk_alpha_w<W>(p.sigmas, p.deltas, s, k < sg.n, T2, p.T_thr, lane);
+                const Chunk c = chunk_alpha(p.sigmas, p.deltas, s, k < sg.n, T2, p.T_thr, lane);
                 const float w = c.valid ? c.a * c.T_before : 0.0f;
                 float cr = 0, cg = 0, cb = 0, tt = 0, dl = 0, wsv = 0;
                 if (c.valid) {
                     cr = p.rgbs[3 * s]; cg = p.rgbs[3 * s + 1]; cb = p.rgbs[3 * s + 2];
                     tt = p.ts[s]; dl = p.deltas[s]; wsv = p.ws[s];
                 }
-                const float wi = wr + grp_scan_add<W>(wsv, lane);
-                const float wti = wtr + grp_scan_add<W>(wsv * tt, lane);
-                float we = __shfl_up(wi, 1, W), wte = __shfl_up(wti, 1, W);
+                const float wi = wr + half_incl_scan_add(wsv, lane);
+                const float wti = wtr + half_incl_scan_add(wsv * tt, lane);
+                float we = __shfl_up(wi, 1, 32), wte = __shfl_up(wti, 1, 32);
                 if (lane == 0) { we = wr; wte = wtr; }
                 const float dws = gd != 0.0f ? gd * 2 * ((tt * we - wte) + (wt_sum - wti - tt * (w_sum - wi))) + gd * 2.0f / 3 * wsv * dl
                                              : 0.0f;
-                const float ri = r_run + grp_scan_add<W>(w * cr, lane);
-                const float gi = g_run + grp_scan_add<W>(w * cg, lane);
-                const float bi = b_run + grp_scan_add<W>(w * cb, lane);
-                const float pi = p_run + grp_scan_add<W>(dws * wsv, lane);
+                const float ri = r_run + half_incl_scan_add(w * cr, lane);
+                const float gi = g_run + half_incl_scan_add(w * cg, lane);
+                const float bi = b_run + half_incl_scan_add(w * cb, lane);
+                const float pi = p_run + half_incl_scan_add(dws * wsv, lane);
                 if (c.valid) {
                     const float wa = c.active ? w : 0.0f;
                     p.d_rgbs[3 * s] = gR * wa; p.d_rgbs[3 * s + 1] = gG * wa; p.d_rgbs[3 * s + 2] = gB * wa;
@@ -1059,15 +998,15 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                     }
                 }
                 if (c.first >= 0) break;
-                T2 = __shfl(c.T_after, W - 1, W);
-                r_run = __shfl(ri, W - 1, W); g_run = __shfl(gi, W - 1, W); b_run = __shfl(bi, W - 1, W); p_run = __shfl(pi, W - 1, W);
-                wr = __shfl(wi, W - 1, W); wtr = __shfl(wti, W - 1, W);
+                T2 = __shfl(c.T_after, 31, 32);
+                r_run = __shfl(ri, 31, 32); g_run = __shfl(gi, 31, 32); b_run = __shfl(bi, 31, 32); p_run = __shfl(pi, 31, 32);
+                wr = __shfl(wi, 31, 32); wtr = __shfl(wti, 31, 32);
             }
         }
     }
     // ---------------- loss terms of the block's rays: one set of atomics per block
-    const int hw = threadIdx.x / W;
-    if ((threadIdx.x & (W - 1)) == 0) {
+    const int hw = threadIdx.x / 32;
+    if ((threadIdx.x & 31) == 0) {
         part[0][hw] = s_rgb; part[1][hw] = s_op; part[2][hw] = s_dist; part_n[hw] = n_used;
         if (MASKED) part[3][hw] = s_ms;
         if (SEM) { part[ROW_SEM][hw] = s_ce; part[ROW_SEM + 1][hw] = s_sky; }
@@ -1085,10 +1024,10 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
             t3 *= p.g_ms;
             atomicAdd(p.terms, (t0 + t1 + t2) + t3);
             atomicAdd(p.terms + 4, t3);
-        } else if (MULTI) {
-            // two or three optional terms: each is summed in double into its own term's workspace slot, exactly as in
-            // the single forms below, behind ONE count of finished workgroups (the SEM block's when SEM is built, else
-            // the NRM block's); the last workgroup rounds every term once and adds their float sum to terms[0]
+        } else if (SEM || NRM || DEP) {
+            // the optional terms, one or several: each is summed in double into its own term's workspace slot, behind
+            // ONE count of finished workgroups (that of the first term built: the SEM block's, else the NRM block's, else
+            // the DEP block's tail counter); the last workgroup rounds every term once and adds their float sum to terms[0]
             atomicAdd(p.terms, t0 + t1 + t2);
             double* sem_sums = SEM ? reinterpret_cast<double*>(p.sem_ws + SEM_WS_SUMS) : nullptr;
             double* nrm_sum = NRM ? reinterpret_cast<double*>(p.nrm_ws + NRM_WS_SUM) : nullptr;
@@ -1110,8 +1049,8 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 atomicAdd(dep_sum, d_sum);
             }
             __threadfence();
-            unsigned* cnt = reinterpret_cast<unsigned*>(SEM ? p.sem_ws + SEM_WS_DONE : p.nrm_ws + NRM_WS_DONE);
-            const unsigned done = atomicAdd(cnt, 1u);
+            int* cnt = SEM ? p.sem_ws + SEM_WS_DONE : NRM ? p.nrm_ws + NRM_WS_DONE : p.dep_ws + DEP_WS_TAIL_DONE;
+            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(cnt), 1u);
             if (done == gridDim.x - 1) {   // every workgroup's sums are in: round them once
                 __threadfence();
                 float opt = 0.0f;
@@ -1126,60 +1065,14 @@ __global__ void __launch_bounds__(256) render_loss_fused_kernel(RenderLossArgs p
                 if (NRM) {
                     const float t_nm = (float)(atomicAdd(nrm_sum, 0.0) * (double)p.g_nm);
                     p.terms[p.slot_nm] = t_nm;
-                    opt += t_nm;
+                    opt = SEM ? opt + t_nm : t_nm;
                 }
                 if (DEP) {
                     const float t_dm = (float)(atomicAdd(dep_sum, 0.0) * (double)p.g_dm);
                     p.terms[p.slot_dm] = t_dm;
-                    opt += t_dm;
+                    opt = (SEM || NRM) ? opt + t_dm : t_dm;
                 }
                 atomicAdd(p.terms, opt);
-            }
-        } else if (SEM) {
-            atomicAdd(p.terms, t0 + t1 + t2);
-            double c_sum = 0.0, s_sum = 0.0;
-            for (int q = 0; q < RPB; q++) { c_sum += (double)part[3][q]; s_sum += (double)part[4][q]; }
-            double* sums = reinterpret_cast<double*>(p.sem_ws + SEM_WS_SUMS);
-            atomicAdd(sums, c_sum);
-            atomicAdd(sums + 1, s_sum);
-            __threadfence();
-            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(p.sem_ws + SEM_WS_DONE), 1u);
-            if (done == gridDim.x - 1) {   // every workgroup's sums are in: round them once
-                __threadfence();
-                const double ce_all = atomicAdd(sums, 0.0), sky_all = atomicAdd(sums + 1, 0.0);
-                const float t_ce = n_valid > 0 ? (float)(ce_all * ((double)p.lam_sem / (double)n_valid)) : 0.0f;
-                const float t_sky = (float)(sky_all * (double)p.g_sky);
-                p.terms[4] = t_ce;
-                p.terms[5] = t_sky;
-                atomicAdd(p.terms, t_ce + t_sky);
-            }
-        } else if (NRM) {
-            atomicAdd(p.terms, t0 + t1 + t2);
-            double n_sum = 0.0;
-            for (int q = 0; q < RPB; q++) n_sum += (double)part[3][q];
-            double* sum = reinterpret_cast<double*>(p.nrm_ws + NRM_WS_SUM);
-            atomicAdd(sum, n_sum);
-            __threadfence();
-            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(p.nrm_ws + NRM_WS_DONE), 1u);
-            if (done == gridDim.x - 1) {   // every workgroup's sum is in: round it once
-                __threadfence();
-                const float t_nm = (float)(atomicAdd(sum, 0.0) * (double)p.g_nm);
-                p.terms[p.slot_nm] = t_nm;
-                atomicAdd(p.terms, t_nm);
-            }
-        } else if (DEP) {
-            atomicAdd(p.terms, t0 + t1 + t2);
-            double d_sum = 0.0;
-            for (int q = 0; q < RPB; q++) d_sum += (double)part[3][q];
-            double* sum = reinterpret_cast<double*>(p.dep_ws + DEP_WS_TERM);
-            atomicAdd(sum, d_sum);
-            __threadfence();
-            const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(p.dep_ws + DEP_WS_TAIL_DONE), 1u);
-            if (done == gridDim.x - 1) {   // every workgroup's sum is in: round it once
-                __threadfence();
-                const float t_dm = (float)(atomicAdd(sum, 0.0) * (double)p.g_dm);
-                p.terms[p.slot_dm] = t_dm;
-                atomicAdd(p.terms, t_dm);
             }
         } else
             atomicAdd(p.terms, t0 + t1 + t2);
@@ -1473,8 +1366,9 @@ int ngp_nerf_loss(const float* rgb, const float* target_rgb, const float* opacit
     return ngp_check_launch();
 }
 
-// ---- the fused render + loss tail: six entries on one host path.  Every entry: tail_args plus its own few fields, tail_check
-// with its own extra checks, tail_clear, its pre-kernels (the label count, the depth fit), tail_launch.
+// ---- the fused render + loss tail: seven entries on one host path: tail_args, tail_check with the entry's own extra checks,
+// tail_clear, the pre-kernels (the label count, the depth fit), the entry's few fields, tail_launch.  The four entries with
+// optional terms share one body for all of it (render_loss_fused_terms).
 
 // the one place that fills RenderLossArgs from the arguments every entry shares; every optional field is set to "absent"
 static RenderLossArgs tail_args(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1545,12 +1439,10 @@ static int tail_launch(bool masked, int term_mask, int classes, int n_rays, hipS
 {
     const dim3 grid = seg_grid(n_rays), block(256);
     if (a.d_bg) {
-        hipLaunchKernelGGL((render_loss_fused_kernel<8, 32, false, false, false, false, true>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((render_loss_fused_kernel<8, false, false, false, false, true>), grid, block, 0, st, a);
         return ngp_check_launch();
     }
-    // a 32-lane half-wave per ray (W = 64, a whole wave per ray, was measured: 144 us per launch in the step against 85 —
-    // 83 VGPRs leave 5 waves per SIMD, so 8192 wave-sized rays no longer fit the chip at once)
-#define NGP_TAIL(CM, M, S, N, D) hipLaunchKernelGGL((render_loss_fused_kernel<CM, 32, M, S, N, D>), grid, block, 0, st, a)
+#define NGP_TAIL(CM, M, S, N, D) hipLaunchKernelGGL((render_loss_fused_kernel<CM, M, S, N, D>), grid, block, 0, st, a)
     const bool wide = classes > 8;   // (only with SEM: the entries check it)
     switch (masked ? -1 : term_mask) {
     case -1: NGP_TAIL(8, true, false, false, false); break;
@@ -1634,6 +1526,51 @@ int ngp_render_loss_fused_masked(const float* sigmas, const float* rgbs, const f
         mask, size_delta, dL_dmask, stream);
 }
 
+// The multi workspace, NGP_MULTI_WS_INTS = 30 int32, 8-byte aligned: the three single workspaces back to back
+constexpr int MULTI_WS_NRM = NGP_SEM_WS_INTS, MULTI_WS_DEP = NGP_SEM_WS_INTS + NGP_NRM_WS_INTS;   // (the semantic one: at 0)
+static_assert(MULTI_WS_DEP + NGP_DEP_WS_INTS == NGP_MULTI_WS_INTS && NGP_MULTI_WS_INTS % 2 == 0 && MULTI_WS_NRM % 2 == 0 &&
+              MULTI_WS_DEP % 2 == 0, "the multi workspace is the three single ones, each 8-byte aligned");
+
+// Where an entry with optional terms keeps what the launch accumulates into: terms (n_terms floats), vr_samples vr_at
+// floats and the entry's workspace ws_at floats behind terms (an int64 behind 5 floats sits at float 6), how much of the
+// workspace to clear (ws_clear int32; 0: none, the label count clears the semantic one), where the normal_mono and
+// depth_mono blocks sit in it (the semantic block: at 0) and the slots of the two rounded terms.
+struct TailLayout { size_t n_terms, vr_at, ws_at, ws_clear; int at_nrm, at_dep, slot_nm, slot_dm; };
+constexpr TailLayout LAYOUT_SEM = {6, 6, 0, 0, 0, 0, 4, 4}, LAYOUT_NRM = {5, 6, 8, NGP_NRM_WS_INTS, 0, 0, 4, 4},
+                     LAYOUT_DEP = {5, 6, 8, NGP_DEP_WS_INTS, 0, 0, 4, 4},
+                     LAYOUT_MULTI = {8, 8, 10, NGP_MULTI_WS_INTS, MULTI_WS_NRM, MULTI_WS_DEP, 6, 7};
+
+// shared body of ngp_render_loss_fused_sem / _nrm / _dep / _multi: term_mask names the terms to build, term_ws is the entry's
+// workspace; the inputs and the gradient output of a term that is not built are not looked at (NULL)
+static int render_loss_fused_terms(RenderLossArgs a, int term_mask, const int64_t* labels, float lambda_sem, float lambda_sky,
+                                   const float* normals_gt, float lambda_nm, const float* depth_gt, float lambda_dm,
+                                   float scene_scale, int* term_ws, float* dL_dsem_logits, float* dL_dnormal_head,
+                                   const TailLayout& lay, void* stream)
+{
+    const bool SEM = term_mask & NGP_TERM_SEM, NRM = term_mask & NGP_TERM_NRM, DEP = term_mask & NGP_TERM_DEP;
+    // (the semantic term's instantiations hold 1..16 classes, the others' 0..8)
+    const int rc = tail_check(a, SEM ? 1 : 0, SEM ? 16 : 8, !DEP || scene_scale > 0.0f,
+                              tail_trained_ok(a, term_ws) && (!SEM || (labels && a.sem_logits && dL_dsem_logits)) &&
+                                  (!NRM || (normals_gt && a.np_raw && dL_dnormal_head)) && (!DEP || depth_gt));
+    if (rc != TAIL_GO) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (tail_clear(a.terms, lay.n_terms, lay.vr_at, a.vr_samples, lay.ws_clear ? term_ws : nullptr, lay.ws_at, lay.ws_clear,
+                   st) != NGP_OK) return NGP_ELAUNCH;
+    int *sem_ws = term_ws, *nrm_ws = term_ws + lay.at_nrm, *dep_ws = term_ws + lay.at_dep;
+    // what every seed needs of the whole batch, on the same stream ahead of the tail: n_valid, which depends on the labels
+    // alone (the count also clears the semantic workspace), and the fit's scale and shift, which need every ray's depth
+    if (SEM)
+        hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, a.rays_a, a.n_rays, a.classes, sem_ws);
+    if (DEP)
+        hipLaunchKernelGGL(depth_fit_kernel, seg_grid(a.n_rays), dim3(256), 0, st, a.sigmas, a.deltas, a.ts, a.rays_a, depth_gt,
+                           a.n_rays, a.T_thr, dep_ws);
+    a.slot_nm = lay.slot_nm; a.slot_dm = lay.slot_dm;
+    if (SEM) { a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / a.n_rays; a.d_sem = dL_dsem_logits; }
+    if (NRM) { a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * a.n_rays); a.d_np = dL_dnormal_head; }
+    if (DEP) { a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / a.n_rays; a.dm_scale = scene_scale; }
+    return tail_launch(false, term_mask, a.classes, a.n_rays, st, a);
+}
+
 int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
                               const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
                               const float* dirs, const float* deltas, const float* ts, const int64_t* rays_a,
@@ -1644,20 +1581,12 @@ int ngp_render_loss_fused_sem(const float* sigmas, const float* rgbs, const floa
                               float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* sem_ws,
                               float* dL_dsem_logits, void* stream)
 {
-    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
-                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
-                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
-                                 dL_dsigmas, dL_drgbs);
-    const int rc = tail_check(a, 1, 16, true, tail_trained_ok(a, sem_ws) && labels && sem_logits && dL_dsem_logits);
-    if (rc != TAIL_GO) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // terms (6) with vr_samples right behind them (float 6); the label count below clears the workspace
-    if (tail_clear(terms, 6, 6, vr_samples, nullptr, 0, 0, st) != NGP_OK) return NGP_ELAUNCH;
-    // n_valid depends on the labels alone and every seed needs it: counted (and the workspace cleared) on the same stream
-    // ahead of the tail
-    hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, rays_a, n_rays, classes, sem_ws);
-    a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits;
-    return tail_launch(false, NGP_TERM_SEM, classes, n_rays, st, a);
+    return render_loss_fused_terms(
+        tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts, rays_a,
+                  target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
+                  vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
+        NGP_TERM_SEM, labels, lambda_sem, lambda_sky, nullptr, 0.0f, nullptr, 0.0f, 1.0f, sem_ws, dL_dsem_logits, nullptr,
+        LAYOUT_SEM, stream);
 }
 
 int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1669,17 +1598,12 @@ int ngp_render_loss_fused_nrm(const float* sigmas, const float* rgbs, const floa
                               float* normal_pred, float* sem, float* ws, float* loss_o, float* loss_p, float* terms,
                               float* dL_dsigmas, float* dL_drgbs, int* nrm_ws, float* dL_dnormal_head, void* stream)
 {
-    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
-                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
-                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
-                                 dL_dsigmas, dL_drgbs);
-    const int rc = tail_check(a, 0, 8, true, tail_trained_ok(a, nrm_ws) && normals_gt && normal_head && dL_dnormal_head);
-    if (rc != TAIL_GO) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8
-    if (tail_clear(terms, 5, 6, vr_samples, nrm_ws, 8, NGP_NRM_WS_INTS, st) != NGP_OK) return NGP_ELAUNCH;
-    a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head;
-    return tail_launch(false, NGP_TERM_NRM, classes, n_rays, st, a);
+    return render_loss_fused_terms(
+        tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts, rays_a,
+                  target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
+                  vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
+        NGP_TERM_NRM, nullptr, 0.0f, 0.0f, normals_gt, lambda_nm, nullptr, 0.0f, 1.0f, nrm_ws, nullptr, dL_dnormal_head,
+        LAYOUT_NRM, stream);
 }
 
 int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
@@ -1691,26 +1615,13 @@ int ngp_render_loss_fused_dep(const float* sigmas, const float* rgbs, const floa
                               float* depth, float* rgb, float* normal_pred, float* sem, float* ws, float* loss_o,
                               float* loss_p, float* terms, float* dL_dsigmas, float* dL_drgbs, int* dep_ws, void* stream)
 {
-    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
-                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
-                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
-                                 dL_dsigmas, dL_drgbs);
-    const int rc = tail_check(a, 0, 8, scene_scale > 0.0f, tail_trained_ok(a, dep_ws) && depth_gt);
-    if (rc != TAIL_GO) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // terms (5) with vr_samples behind them at float 6 and the workspace at float 8
-    if (tail_clear(terms, 5, 6, vr_samples, dep_ws, 8, NGP_DEP_WS_INTS, st) != NGP_OK) return NGP_ELAUNCH;
-    // every seed needs the batch's scale and shift, which need every ray's depth: fitted on the same stream ahead of the tail
-    hipLaunchKernelGGL(depth_fit_kernel, seg_grid(n_rays), dim3(256), 0, st, sigmas, deltas, ts, rays_a, depth_gt, n_rays,
-                       T_threshold, dep_ws);
-    a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale;
-    return tail_launch(false, NGP_TERM_DEP, classes, n_rays, st, a);
+    return render_loss_fused_terms(
+        tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts, rays_a,
+                  target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
+                  vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
+        NGP_TERM_DEP, nullptr, 0.0f, 0.0f, nullptr, 0.0f, depth_gt, lambda_dm, scene_scale, dep_ws, nullptr, nullptr,
+        LAYOUT_DEP, stream);
 }
-
-// The multi workspace, NGP_MULTI_WS_INTS = 30 int32, 8-byte aligned: the three single workspaces back to back
-constexpr int MULTI_WS_SEM = 0, MULTI_WS_NRM = NGP_SEM_WS_INTS, MULTI_WS_DEP = NGP_SEM_WS_INTS + NGP_NRM_WS_INTS;
-static_assert(MULTI_WS_DEP + NGP_DEP_WS_INTS == NGP_MULTI_WS_INTS && NGP_MULTI_WS_INTS % 2 == 0 && MULTI_WS_NRM % 2 == 0 &&
-              MULTI_WS_DEP % 2 == 0, "the multi workspace is the three single ones, each 8-byte aligned");
 
 int ngp_render_loss_fused_multi(const float* sigmas, const float* rgbs, const float* dsigma_dx, const float* scale3,
                                 const float* normal_head, int64_t ld_normal, const float* sem_logits, int64_t ld_sem,
@@ -1726,30 +1637,13 @@ int ngp_render_loss_fused_multi(const float* sigmas, const float* rgbs, const fl
     // (a zero mask names nothing to compute: refused with rays to process; an empty batch is valid whatever it names)
     if (term_mask < 0 || (term_mask & ~(NGP_TERM_SEM | NGP_TERM_NRM | NGP_TERM_DEP)) || (term_mask == 0 && n_rays != 0))
         return NGP_EINVAL;
-    const bool SEM = term_mask & NGP_TERM_SEM, NRM = term_mask & NGP_TERM_NRM, DEP = term_mask & NGP_TERM_DEP;
-    RenderLossArgs a = tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts,
-                                 rays_a, target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion,
-                                 total_samples, vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms,
-                                 dL_dsigmas, dL_drgbs);
-    const int rc = tail_check(a, SEM ? 1 : 0, SEM ? 16 : 8, !DEP || scene_scale > 0.0f,
-                              tail_trained_ok(a, multi_ws) && (!SEM || (labels && sem_logits && dL_dsem_logits)) &&
-                                  (!NRM || (normals_gt && normal_head && dL_dnormal_head)) && (!DEP || depth_gt));
-    if (rc != TAIL_GO) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // terms (8) with vr_samples behind them at float 8 and the workspace at float 10
-    if (tail_clear(terms, 8, 8, vr_samples, multi_ws, 10, NGP_MULTI_WS_INTS, st) != NGP_OK) return NGP_ELAUNCH;
-    int *sem_ws = multi_ws + MULTI_WS_SEM, *nrm_ws = multi_ws + MULTI_WS_NRM, *dep_ws = multi_ws + MULTI_WS_DEP;
-    // what every seed needs of the whole batch, on the same stream ahead of the tail: the count of valid labels, the fit
-    if (SEM) hipLaunchKernelGGL(count_valid_labels_kernel, dim3(1), dim3(1024), 0, st, labels, rays_a, n_rays, classes, sem_ws);
-    if (DEP)
-        hipLaunchKernelGGL(depth_fit_kernel, seg_grid(n_rays), dim3(256), 0, st, sigmas, deltas, ts, rays_a, depth_gt, n_rays,
-                           T_threshold, dep_ws);
-    a.slot_nm = 6; a.slot_dm = 7;
-    if (SEM) { a.labels = labels; a.sem_ws = sem_ws; a.lam_sem = lambda_sem; a.g_sky = lambda_sky / n_rays; a.d_sem = dL_dsem_logits; }
-    if (NRM) { a.nrm_gt = normals_gt; a.nrm_ws = nrm_ws; a.g_nm = lambda_nm / (3.0f * n_rays); a.d_np = dL_dnormal_head; }
-    if (DEP) { a.dep_gt = depth_gt; a.dep_ws = dep_ws; a.g_dm = lambda_dm / n_rays; a.dm_scale = scene_scale; }
-    // (one bit alone launches that term's own instantiation)
-    return tail_launch(false, term_mask, classes, n_rays, st, a);
+    // (a term's workspace is its block of multi_ws; one bit alone launches that term's own instantiation)
+    return render_loss_fused_terms(
+        tail_args(sigmas, rgbs, dsigma_dx, scale3, normal_head, ld_normal, sem_logits, ld_sem, dirs, deltas, ts, rays_a,
+                  target_rgb, rgb_bg, T_threshold, classes, n_rays, lambda_opacity, lambda_distortion, total_samples,
+                  vr_samples, opacity, depth, rgb, normal_pred, sem, ws, loss_o, loss_p, terms, dL_dsigmas, dL_drgbs),
+        term_mask, labels, lambda_sem, lambda_sky, normals_gt, lambda_nm, depth_gt, lambda_dm, scene_scale,
+        multi_ws, dL_dsem_logits, dL_dnormal_head, LAYOUT_MULTI, stream);
 }
 
 int ngp_refloss_inputs(const float* normals_raw, const float* normals_pred, const float* dirs, int64_t n,
