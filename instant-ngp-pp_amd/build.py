@@ -24,6 +24,7 @@ SOURCES = [
     ("composite_kernels.hip", []),
     ("grid_kernels.hip", []),
     ("mlp_kernels.hip", []),
+    ("optim_kernels.hip", []),
     ("density_bwd2_kernels.hip", []),
     ("mask_kernels.hip", []),
     ("embed_kernels.hip", []),

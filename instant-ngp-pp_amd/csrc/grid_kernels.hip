@@ -1161,26 +1161,13 @@ int ngp_density_field_fwd(const ngp_grid_desc* desc, const float* table, const f
     if (n == 0) return NGP_OK;
     if (!table || !x || !W1 || !W2 || !feat || !a1 || !sig || !dfeat || !grads) return NGP_EINVAL;
     if ((((uintptr_t)W1 | (uintptr_t)feat | (uintptr_t)a1 | (uintptr_t)dfeat) & 15) != 0) return NGP_EINVAL;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    static bool attr_set = false;
+    const int n_cu = cu_count();
+    if (!n_cu) return NGP_ELAUNCH;
     const size_t lds = (size_t)dens::LDS_FLOATS * sizeof(float);
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&density_field_fwd_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return NGP_ELAUNCH;
-        attr_set = true;
-    }
     const int n_tiles = (int)((n + 31) / 32);
     const int blocks = (n_tiles + dens::NW - 1) / dens::NW < n_cu ? (n_tiles + dens::NW - 1) / dens::NW : n_cu;
-    hipLaunchKernelGGL(density_field_fwd_kernel, dim3(blocks), dim3(64 * dens::NW), lds, (hipStream_t)stream, m, table, x,
-                       n, W1, b1, W2, b2, feat, a1, sig, dfeat, grads, n_tiles);
-    return ngp_check_launch();
+    return launch_big_lds<density_field_fwd_kernel>(dim3(blocks), dim3(64 * dens::NW), lds, (int)lds, (hipStream_t)stream,
+                                                    m, table, x, n, W1, b1, W2, b2, feat, a1, sig, dfeat, grads, n_tiles);
 }
 
 int ngp_grid_bwd_bwd_input(const ngp_grid_desc* desc, const float* table, const float* x, const float* dL_dy,

@@ -1,5 +1,6 @@
-// Small-MLP layers on the f32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains),
-// activation backward, fused Adam, sum of squares.
+// Small-MLP layers on the f32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains): the tiled GEMM, the
+// streaming 2-layer forward / data gradient / weight gradient, the skinny (n_out <= 4) layers, activation backward and
+// column sums.  (The optimizer's kernels are in optim_kernels.hip.)
 //
 // One LDS-tiled GEMM template serves the three products a dense layer needs:
 //   FWD   y  (n, n_out) = act(x (n, n_in) . W^T + b)       A = x  [m][k],  B = W [n][k]
@@ -10,6 +11,7 @@
 // is one conflict-free ds_read_b32 per lane: lane l of the 32x32x2 MFMA holds A[i=l&31][k=l>>5]
 // and B[k=l>>5][j=l&31]; C/D is col=l&31, row=acc_row(r, l>>5) (mlp_tile.h).
 // Layers with n_out <= 4 (the density head, networks.py:57) use VALU kernels instead.
+#include <type_traits>
 #include "common.h"
 #include "mlp_act.h"
 #include "mlp_tile.h"
@@ -1323,211 +1325,6 @@ __global__ void __launch_bounds__(256) mlp_hidden_bwd_kernel(const float* __rest
     }
 }
 
-// ---------------------------------------------------------------- optimizer
-__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, float step_size, float beta1, float beta2,
-                                                   float eps, float bc2_sqrt, float weight_decay,
-                                                   const float* __restrict__ grad_scale, int zero_grad, bool sparse_zero)
-{
-    constexpr int U = 2;   // 16-byte quads per lane and trip
-    const float gs = grad_scale ? *grad_scale : 1.0f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t n4 = n >> 2;
-    float4* p4 = reinterpret_cast<float4*>(p); float4* g4 = reinterpret_cast<float4*>(g);
-    float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
-    auto update = [&](float4& pp, const float4& gg, float4& mm, float4& vv) {
-        float* pa = &pp.x; const float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float gr = ga[j] * gs;
-            if (weight_decay != 0.0f) gr += weight_decay * pa[j];
-            ma[j] = ma[j] + (gr - ma[j]) * (1.0f - beta1);
-            va[j] = va[j] * beta2 + (1.0f - beta2) * gr * gr;
-            const float denom = sqrtf(va[j]) / bc2_sqrt + eps;
-            pa[j] = pa[j] - step_size * (ma[j] / denom);
-        }
-    };
-    const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    auto nz = [](const float4& q) { return q.x != 0.0f || q.y != 0.0f || q.z != 0.0f || q.w != 0.0f; };
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // U independent 16-B quads per lane and trip: the launch is capped well below full occupancy
-    // (other streams' kernels must be able to get wave slots and registers), so the bytes in flight come from
-    // the unroll instead of from more waves
-    for (; i + (U - 1) * stride < n4; i += U * stride) {
-        float4 pa[U], ga[U], ma[U], va[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) { pa[u] = p4[i + u * stride]; ga[u] = g4[i + u * stride]; ma[u] = m4[i + u * stride]; va[u] = v4[i + u * stride]; }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            update(pa[u], ga[u], ma[u], va[u]);
-            p4[i + u * stride] = pa[u]; m4[i + u * stride] = ma[u]; v4[i + u * stride] = va[u];
-            // untouched table rows (no sample near them this step) already hold zeros: do not write them again
-            if (zero_grad && (sparse_zero ? nz(ga[u]) : true)) g4[i + u * stride] = zero4;
-        }
-    }
-    for (; i < n4; i += stride) {
-        float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-        update(pp, gg, mm, vv);
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
-        if (zero_grad && (sparse_zero ? nz(gg) : true)) g4[i] = zero4;
-    }
-    // tail
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float gr = g[i] * gs;
-        if (weight_decay != 0.0f) gr += weight_decay * p[i];
-        const float mn = m[i] + (gr - m[i]) * (1.0f - beta1);
-        const float vn = v[i] * beta2 + (1.0f - beta2) * gr * gr;
-        m[i] = mn; v[i] = vn;
-        p[i] = p[i] - step_size * (mn / (sqrtf(vn) / bc2_sqrt + eps));
-        if (zero_grad) g[i] = 0.0f;
-    }
-}
-
-__global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out,
-                                                    const int32_t* __restrict__ flag)
-{
-    if (flag && *flag == 0) return;   // the clip decision did not need the exact norm
-
-    __shared__ float part[4];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    float a = 0.0f, b = 0.0f;
-    // 16-byte loads, two independent quads per trip (x is 16-byte aligned: checked by the caller)
-    const float4* x4 = reinterpret_cast<const float4*>(x);
-    const int64_t n4 = n >> 2;
-    int64_t i = tid;
-    for (; i + stride < n4; i += 2 * stride) {
-        const float4 p = x4[i], q = x4[i + stride];
-        a = fmaf(p.x, p.x, a); a = fmaf(p.y, p.y, a); a = fmaf(p.z, p.z, a); a = fmaf(p.w, p.w, a);
-        b = fmaf(q.x, q.x, b); b = fmaf(q.y, q.y, b); b = fmaf(q.z, q.z, b); b = fmaf(q.w, q.w, b);
-    }
-    for (; i < n4; i += stride) {
-        const float4 p = x4[i];
-        a = fmaf(p.x, p.x, a); a = fmaf(p.y, p.y, a); a = fmaf(p.z, p.z, a); a = fmaf(p.w, p.w, a);
-    }
-    for (int64_t j = (n4 << 2) + tid; j < n; j += stride) a = fmaf(x[j], x[j], a);
-    a += b;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
-}
-
-__global__ void __launch_bounds__(256) sumsq_scalar_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out,
-                                                           const int32_t* __restrict__ flag)
-{
-    if (flag && *flag == 0) return;
-
-    __shared__ float part[4];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    float a = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) a = fmaf(x[i], x[i], a);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
-}
-
-// coef = extra_scale * min(1, max_norm / (sqrt(sumsq) + 1e-6))   (torch.nn.utils.clip_grad_norm_)
-__global__ void clip_coef_kernel(const float* __restrict__ sumsq, float max_norm, float extra_scale,
-                                 float* __restrict__ coef)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const float norm = sqrtf(*sumsq) * extra_scale;
-        float c = max_norm / (norm + 1e-6f);
-        if (c > 1.0f) c = 1.0f;
-        *coef = c * extra_scale;
-    }
-}
-
-// sum over rows of the Euclidean norm of the first `cols` entries (cols <= 16): one lane per row
-__global__ void __launch_bounds__(256) row_norm_sum_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int cols,
-                                                           float* __restrict__ out)
-{
-    __shared__ float part[4];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    float a = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float q = 0.0f;
-        for (int c = 0; c < cols; c++) { const float v = x[i * ldx + c]; q = fmaf(v, v, q); }
-        a += sqrtf(q);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
-}
-
-// clipping settled from an upper bound of the gradient norm (see ngp_clip_decide in the header)
-__global__ void __launch_bounds__(1024) clip_decide_kernel(const float* __restrict__ sums,
-                                                           const float* __restrict__ w1a, int64_t n1a,
-                                                           const float* __restrict__ w2a, int64_t n2a,
-                                                           const float* __restrict__ w1b, int64_t n1b,
-                                                           const float* __restrict__ w2b, int64_t n2b,
-                                                           const float* __restrict__ sumsq_rest, float max_norm,
-                                                           float extra_scale, float* __restrict__ coef,
-                                                           int32_t* __restrict__ need_exact,
-                                                           const float* __restrict__ rest, int64_t n_rest,
-                                                           float* __restrict__ sumsq_out)
-{
-    __shared__ float ws[5][16];
-    const float* ptr[5] = {w1a, w2a, w1b, w2b, rest};
-    const int64_t cnt[5] = {n1a, n2a, n1b, n2b, rest ? n_rest : 0};
-    for (int k = 0; k < 5; k++) {
-        float q = 0.0f;
-        // 16-byte pieces, several in flight per thread (one block reads ~80 k floats: the loads' latency is the launch's length)
-        const bool vec = (((uintptr_t)ptr[k]) & 15) == 0;
-        const int64_t n4 = vec ? cnt[k] / 4 : 0;
-        const float4* p4 = reinterpret_cast<const float4*>(ptr[k]);
-        float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
-#pragma unroll 4
-        for (int64_t i = threadIdx.x; i < n4; i += 1024) {
-            const float4 v = p4[i];
-            q0 = fmaf(v.x, v.x, q0); q1 = fmaf(v.y, v.y, q1); q2 = fmaf(v.z, v.z, q2); q3 = fmaf(v.w, v.w, q3);
-        }
-        q = (q0 + q1) + (q2 + q3);
-        for (int64_t i = 4 * n4 + threadIdx.x; i < cnt[k]; i += 1024) q = fmaf(ptr[k][i], ptr[k][i], q);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-        if ((threadIdx.x & 63) == 0) ws[k][threadIdx.x >> 6] = q;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float f[4];
-        for (int k = 0; k < 4; k++) {
-            float t = 0.0f;
-            for (int w = 0; w < 16; w++) t += ws[k][w];
-            f[k] = sqrtf(t);
-        }
-        float rest_sq = sumsq_rest ? *sumsq_rest : 0.0f;
-        if (rest) {                       // the exact part summed here (ngp_clip_decide_rest): no launch of its own
-            for (int w = 0; w < 16; w++) rest_sq += ws[4][w];
-            *sumsq_out = rest_sq;         // the conditional exact route (ngp_sumsq_if) continues from it
-        }
-        const float ba = f[0] * f[1] * sums[0], bb = f[2] * f[3] * sums[1];
-        const float bound = sqrtf(ba * ba + bb * bb + rest_sq) * extra_scale;
-        const bool safe = bound * 1.001f + 1e-6f < max_norm;     // false for NaN / inf
-        *need_exact = safe ? 0 : 1;
-        if (safe) *coef = extra_scale;
-    }
-}
-
-__global__ void clip_coef_if_kernel(const float* __restrict__ sumsq, float max_norm, float extra_scale,
-                                    float* __restrict__ coef, const int32_t* __restrict__ flag)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0 && *flag != 0) {
-        const float norm = sqrtf(*sumsq) * extra_scale;
-        float c = max_norm / (norm + 1e-6f);
-        if (c > 1.0f) c = 1.0f;
-        *coef = c * extra_scale;
-    }
-}
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 #define LAUNCH_GEMM(MODE, WM, WN, TM, TN)                                                                   \
     do {                                                                                                   \
         if (XF == 0) hipLaunchKernelGGL((gemm_kernel<MODE, WM, WN, TM, TN>), grid, dim3(256), 0, st, p);      \
@@ -1576,6 +1373,17 @@ void launch_wgrad(GemmArgs p, hipStream_t st)
         dim3 grid(ngp_blocks(p.M, 64), ngp_blocks(p.N, 64), (unsigned)splits);
         LAUNCH_GEMM(MODE_WGRAD, 2, 2, 1, 1);
     }
+}
+
+// Runtime value -> template argument: f(std::integral_constant<int, V>) for the V among Vs that equals v.  The three
+// streaming entry points below choose their kernel instantiation with it; launch_big_lds (common.h) then owns the
+// hipFuncSetAttribute that lets the instantiation have its LDS.
+template <int... Vs, typename F>
+int pick(int v, F&& f)
+{
+    int rc = NGP_EINVAL;
+    (void)((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    return rc;
 }
 
 inline bool xf_args_ok(const float* dz2, int64_t lddz2, const float* W2, int64_t ldw2, const float* hidden,
@@ -1665,44 +1473,18 @@ static int mlp2_fwd_impl(const float* x, int64_t ldx, const float* W1, int64_t l
         const int f2 = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);
         constexpr int nw = 8;   // waves per workgroup
         const size_t lds = (size_t)(H * (n_in + 4) + f2 * H + H + 8 + nw * 1024) * sizeof(float);
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
-            n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        }
+        const int n_cu = cu_count();
+        if (!n_cu) return NGP_ELAUNCH;
         const int max_blocks = n_cu;   // one workgroup per CU (W1 takes half the LDS)
         const int blocks = (n_tiles + nw - 1) / nw < max_blocks ? (n_tiles + nw - 1) / nw : max_blocks;
-#define LAUNCH_STREAM(F2V, KQV, ACTV, TNV)                                                                              \
-    do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_stream_fwd_kernel<F2V, KQV, ACTV, TNV>),         \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)              \
-                return NGP_ELAUNCH;                                                                                     \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((mlp_stream_fwd_kernel<F2V, KQV, ACTV, TNV>), dim3(blocks), dim3(64 * nw), lds, st, p, n_tiles); \
-    } while (0)
-#define LAUNCH_STREAM_A(F2V, KQV, TNV)                                                                                  \
-    do {                                                                                                                \
-        if (act1 == NGP_ACT_RELU) LAUNCH_STREAM(F2V, KQV, NGP_ACT_RELU, TNV);                                           \
-        else LAUNCH_STREAM(F2V, KQV, NGP_ACT_SOFTPLUS, TNV);                                                            \
-    } while (0)
-#define LAUNCH_STREAM_K(F2V)                                                                                            \
-    do {                                                                                                                \
-        if (n_in == 128) LAUNCH_STREAM_A(F2V, 16, 4);                                                                   \
-        else if (n_in == 144) LAUNCH_STREAM_A(F2V, 18, 4);                                                              \
-        else LAUNCH_STREAM_A(F2V, 20, 4);                                                                               \
-    } while (0)
-        if (f2 == 1) LAUNCH_STREAM_K(1);
-        else if (f2 == 4) LAUNCH_STREAM_K(4);
-        else LAUNCH_STREAM_K(8);
-#undef LAUNCH_STREAM_K
-#undef LAUNCH_STREAM_A
-#undef LAUNCH_STREAM
-        return ngp_check_launch();
+        return pick<1, 4, 8>(f2, [&](auto F2) {
+            return pick<128, 144, 160>(n_in, [&](auto K) {
+                return pick<NGP_ACT_RELU, NGP_ACT_SOFTPLUS>(act1, [&](auto ACT) {
+                    return launch_big_lds<mlp_stream_fwd_kernel<F2, K / 8, ACT, 4>>(dim3(blocks), dim3(64 * nw), lds, 128 * 1024,
+                                                                                    st, p, n_tiles);
+                });
+            });
+        });
     }
     if (H > 32) {
         if (n_out == 1) hipLaunchKernelGGL((gemm_fwd2_kernel<2, 2, 2, 2, 1>), grid, dim3(256), 0, st, p);
@@ -1832,40 +1614,18 @@ int ngp_mlp_bwd_input(const float* dz2, int64_t lddz2, const float* W2, int64_t 
         // but the dz2 prefetch reads XF floats per row: stay inside the row
         hipStream_t st = (hipStream_t)stream;
         const int n_tiles = (int)((n + 31) / 32);
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
-            n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        }
+        const int n_cu = cu_count();
+        if (!n_cu) return NGP_ELAUNCH;
         constexpr int nw = 8;   // waves per workgroup, one workgroup per CU
         const int cap_d = n_cu;
         const int blocks = (n_tiles + nw - 1) / nw < cap_d ? (n_tiles + nw - 1) / nw : cap_d;
-#define LAUNCH_SD(XFV, ACTV)                                                                                            \
-    do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        const size_t lds = (size_t)(128 * 132 + XFV * 128 + nw * 1024) * sizeof(float);                                 \
-        if (!attr_set) {                                                                                                \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_stream_dgrad_kernel<XFV, ACTV>),                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)              \
-                return NGP_ELAUNCH;                                                                                     \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((mlp_stream_dgrad_kernel<XFV, ACTV>), dim3(blocks), dim3(64 * nw), lds, st, p, n_tiles);    \
-    } while (0)
-#define LAUNCH_SD_A(XFV)                                                                                                \
-    do {                                                                                                                \
-        if (act1 == NGP_ACT_RELU) LAUNCH_SD(XFV, NGP_ACT_RELU);                                                         \
-        else LAUNCH_SD(XFV, NGP_ACT_SOFTPLUS);                                                                          \
-    } while (0)
-        if (n_out == 1) LAUNCH_SD_A(1);
-        else if (n_out == 2) LAUNCH_SD_A(2);
-        else if (n_out == 3) LAUNCH_SD_A(3);
-        else LAUNCH_SD_A(4);
-#undef LAUNCH_SD_A
-#undef LAUNCH_SD
-        return ngp_check_launch();
+        return pick<1, 2, 3, 4>(n_out, [&](auto XF) {
+            return pick<NGP_ACT_RELU, NGP_ACT_SOFTPLUS>(act1, [&](auto ACT) {
+                const size_t lds = (size_t)(128 * 132 + XF * 128 + nw * 1024) * sizeof(float);
+                return launch_big_lds<mlp_stream_dgrad_kernel<XF, ACT>>(dim3(blocks), dim3(64 * nw), lds, 128 * 1024, st, p,
+                                                                        n_tiles);
+            });
+        });
     }
     if (n_out == 1) launch_dgrad<1>(p, (hipStream_t)stream);
     else if (n_out <= 3) launch_dgrad<3>(p, (hipStream_t)stream);
@@ -1891,13 +1651,8 @@ int ngp_mlp_bwd_weight(const float* dz2, int64_t lddz2, const float* W2, int64_t
     if (H == 128 && (n_in == 128 || n_in == 144 || n_in == 160) && p.vecA && p.vecB &&
         (act1 == NGP_ACT_RELU || act1 == NGP_ACT_SOFTPLUS)) {
         hipStream_t st = (hipStream_t)stream;
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NGP_ELAUNCH;
-            n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        }
+        const int n_cu = cu_count();
+        if (!n_cu) return NGP_ELAUNCH;
         // The kernel takes workgroups of 8 waves (two groups meeting in LDS, half the atomics; alone the faster shape
         // for the 128-column case: 0.236 -> 0.225 ms) or of 4; a group's share of the chunk is a multiple of the 16
         // samples one turn of the prefetch ring covers
@@ -1917,160 +1672,21 @@ int ngp_mlp_bwd_weight(const float* dz2, int64_t lddz2, const float* W2, int64_t
             if (chunk > cap) chunk = cap;
         }
         blocks = (n + chunk - 1) / chunk;
-#define LAUNCH_SW2(XFV, ACTV, TNV, W2GV)                                                                                \
-    do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_stream_wgrad_kernel<XFV, ACTV, TNV, W2GV>),      \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)               \
-                return NGP_ELAUNCH;                                                                                     \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((mlp_stream_wgrad_kernel<XFV, ACTV, TNV, W2GV>), dim3((unsigned)blocks), dim3(threads), lds, st, \
-                           p, chunk);                                                                                   \
-    } while (0)
-#define LAUNCH_SW(XFV, ACTV, TNV)                                                                                       \
-    do {                                                                                                                \
-        if (dW2) LAUNCH_SW2(XFV, ACTV, TNV, true);                                                                      \
-        else LAUNCH_SW2(XFV, ACTV, TNV, false);                                                                         \
-    } while (0)
-#define LAUNCH_SW_T(XFV, ACTV)                                                                                          \
-    do {                                                                                                                \
-        if (n_in == 128) LAUNCH_SW(XFV, ACTV, 4);                                                                       \
-        else LAUNCH_SW(XFV, ACTV, 5);                                                                                   \
-    } while (0)
-#define LAUNCH_SW_A(XFV)                                                                                                \
-    do {                                                                                                                \
-        if (act1 == NGP_ACT_RELU) LAUNCH_SW_T(XFV, NGP_ACT_RELU);                                                       \
-        else LAUNCH_SW_T(XFV, NGP_ACT_SOFTPLUS);                                                                        \
-    } while (0)
-        if (n_out == 1) LAUNCH_SW_A(1);
-        else if (n_out == 2) LAUNCH_SW_A(2);
-        else if (n_out == 3) LAUNCH_SW_A(3);
-        else LAUNCH_SW_A(4);
-#undef LAUNCH_SW_A
-#undef LAUNCH_SW_T
-#undef LAUNCH_SW
-#undef LAUNCH_SW2
-        return ngp_check_launch();
+        return pick<1, 2, 3, 4>(n_out, [&](auto XF) {
+            return pick<NGP_ACT_RELU, NGP_ACT_SOFTPLUS>(act1, [&](auto ACT) {
+                return pick<4, 5>(n_in == 128 ? 4 : 5, [&](auto TN) {
+                    return pick<0, 1>(dW2 ? 1 : 0, [&](auto W2G) {
+                        return launch_big_lds<mlp_stream_wgrad_kernel<XF, ACT, TN, W2G != 0>>(
+                            dim3((unsigned)blocks), dim3(threads), lds, 96 * 1024, st, p, chunk);
+                    });
+                });
+            });
+        });
     }
     if (n_out == 1) launch_wgrad<1>(p, (hipStream_t)stream);
     else if (n_out <= 3) launch_wgrad<3>(p, (hipStream_t)stream);
     else launch_wgrad<XF_OMAX>(p, (hipStream_t)stream);
     return ngp_check_launch();
 }
-
-int ngp_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                  float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, int zero_grad,
-                  void* stream)
-{
-    return ngp_adam_step_width(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                               zero_grad, 0, stream);
-}
-
-int ngp_adam_step_width(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                        float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, int zero_grad,
-                        int workgroups, void* stream)
-{
-    if (n < 0 || step < 1 || workgroups < 0) return NGP_EINVAL;
-    if (n == 0) return NGP_OK;
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return NGP_EINVAL;
-    if (!aligned16(param) || !aligned16(grad) || !aligned16(exp_avg) || !aligned16(exp_avg_sq)) return NGP_EINVAL;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
-    // Default 2 workgroups per CU (a wave per SIMD each, 64 registers): 5.2 TB/s alone (2048 workgroups: 4.5) and the sweep ends
-    // soonest.  ONE workgroup per CU lets the 8-wave MLP workgroups of the next step's density path in beside it (the sweep then
-    // takes 1.5-1.7 instead of 1.1-1.4 ms, the colour chain follows alone).  Which is faster per step depends on the loop and
-    // the box (+-3 %: profiles/r03_occupancy_shaping.txt (1), (9)), so the caller may name the width:
-    // NGPTrainer times both in its own loop and keeps the faster one.
-    const int64_t cap = workgroups > 0 ? workgroups : 512;
-    int64_t blocks = ((n >> 2) + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                       exp_avg_sq, n, step_size, beta1, beta2, eps, bc2_sqrt, weight_decay, grad_scale, zero_grad, true);
-    return ngp_check_launch();
-}
-
-int ngp_sumsq(const float* x, int64_t n, float* out, void* stream)
-{
-    return ngp_sumsq_if(x, n, out, nullptr, stream);
-}
-
-int ngp_sumsq_if(const float* x, int64_t n, float* out, const int32_t* flag, void* stream)
-{
-    if (n < 0 || !out) return NGP_EINVAL;
-    if (n == 0) return NGP_OK;
-    if (!x) return NGP_EINVAL;
-    if (aligned16(x)) {
-        int64_t blocks = ((n >> 2) + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, out, flag);
-    } else {
-        int64_t blocks = (n + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(sumsq_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, out, flag);
-    }
-    return ngp_check_launch();
-}
-
-int ngp_clip_coef(const float* sumsq, float max_norm, float extra_scale, float* coef, void* stream)
-{
-    if (!sumsq || !coef) return NGP_EINVAL;
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, max_norm, extra_scale, coef);
-    return ngp_check_launch();
-}
-
-int ngp_row_norm_sum(const float* x, int64_t ldx, int64_t n, int cols, float* out, void* stream)
-{
-    if (n < 0 || cols < 1 || cols > 16 || ldx < cols || !out) return NGP_EINVAL;
-    if (n == 0) return NGP_OK;
-    if (!x) return NGP_EINVAL;
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(row_norm_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, n, cols, out);
-    return ngp_check_launch();
-}
-
-int ngp_clip_decide(const float* row_norm_sums, const float* w1_a, int64_t n1_a, const float* w2_a, int64_t n2_a,
-                    const float* w1_b, int64_t n1_b, const float* w2_b, int64_t n2_b, const float* sumsq_rest,
-                    float max_norm, float extra_scale, float* coef, int32_t* need_exact, void* stream)
-{
-    if (!row_norm_sums || !w1_a || !w2_a || !w1_b || !w2_b || n1_a < 1 || n2_a < 1 || n1_b < 1 || n2_b < 1 || !coef ||
-        !need_exact)
-        return NGP_EINVAL;
-    hipLaunchKernelGGL(clip_decide_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_norm_sums, w1_a, n1_a, w2_a,
-                       n2_a, w1_b, n1_b, w2_b, n2_b, sumsq_rest, max_norm, extra_scale, coef, need_exact,
-                       (const float*)nullptr, (int64_t)0, (float*)nullptr);
-    return ngp_check_launch();
-}
-
-int ngp_clip_decide_rest(const float* row_norm_sums, const float* w1_a, int64_t n1_a, const float* w2_a, int64_t n2_a,
-                         const float* w1_b, int64_t n1_b, const float* w2_b, int64_t n2_b, const float* rest,
-                         int64_t n_rest, float* sumsq, float max_norm, float extra_scale, float* coef,
-                         int32_t* need_exact, void* stream)
-{
-    if (!row_norm_sums || !w1_a || !w2_a || !w1_b || !w2_b || n1_a < 1 || n2_a < 1 || n1_b < 1 || n2_b < 1 || !coef ||
-        !need_exact || !rest || n_rest < 0 || !sumsq)
-        return NGP_EINVAL;
-    hipLaunchKernelGGL(clip_decide_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_norm_sums, w1_a, n1_a, w2_a,
-                       n2_a, w1_b, n1_b, w2_b, n2_b, (const float*)sumsq, max_norm, extra_scale, coef, need_exact, rest,
-                       n_rest, sumsq);
-    return ngp_check_launch();
-}
-
-int ngp_clip_coef_if(const float* sumsq, float max_norm, float extra_scale, float* coef, const int32_t* flag,
-                     void* stream)
-{
-    if (!sumsq || !coef || !flag) return NGP_EINVAL;
-    hipLaunchKernelGGL(clip_coef_if_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, max_norm, extra_scale,
-                       coef, flag);
-    return ngp_check_launch();
-}
-
-const char* ngp_version(void) { return "ngp_hip 0.2 gfx950"; }
 
 } // extern "C"

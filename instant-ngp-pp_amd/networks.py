@@ -18,6 +18,8 @@ Differences, all deliberate:
     order then runs on ngp_grid_bwd_bwd_input, ngp_density_head_bwd2 and four existing products (what
     NGPTrainer(normal_ref=True) trains through).
 """
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -93,86 +95,112 @@ def _stream(role, dev, own=None):
     return _STREAMS[key] if own is None else own
 
 
+class _Mlp2(NamedTuple):
+    """A 2-layer MLP as the kernels see it: hidden (H) = act1(x W1^T + b1), out (n_out) = act2(hidden W2^T + b2).  W1 is
+    (H, n_in) with leading dimension ldw1, W2 (>= n_out, H) with leading dimension H; either may be a flat slice."""
+    W1: torch.Tensor
+    ldw1: int
+    b1: Optional[torch.Tensor]
+    W2: torch.Tensor
+    b2: Optional[torch.Tensor]
+    n_in: int
+    H: int
+    n_out: int
+    act1: int
+    act2: int
+
+    @classmethod
+    def tcnn(cls, params, n_in, H, n_out, act2):
+        """a bias-free tinycudann.Network with one ReLU hidden layer: params = [W1 (H, n_in) | W2 (padded n_out, H)]"""
+        return cls(params, n_in, None, params[H * n_in:], None, n_in, H, n_out, _RELU, act2)
+
+    def grad_slices(self, flat):
+        """(dW1, dW2, db1, db2) inside `flat`, the gradient of a tcnn() net's params"""
+        return flat, flat[self.H * self.n_in:], None, None
+
+    def forward(self, x, ldx, n, hidden, out, dact=None):
+        """both layers in one launch, the second in the MFMA epilogue; dact (n, n_out): the launch also leaves act2'(z2)"""
+        args = (x, ldx, self.W1, self.ldw1, self.b1, self.act1, self.W2, self.H, self.b2, self.act2, n, self.n_in, self.H,
+                self.n_out, hidden, self.H, out, self.n_out)
+        if dact is None:
+            call("mlp2_fwd", *args)
+        else:
+            call("mlp2_fwd_dact", *args, dact)
+
+
 class _Mlp2Bwd:
     """Backward of a 2-layer MLP (x_in -> H hidden with act1 -> n_out with act2) on the library, in three stages
     the caller can interleave with other work: the constructor runs the elementwise stage (dz2, on the plain route
     also dz1), input_product() the data gradient dz1 . W1[:, cols], weight_products() dW1 / dW2 / db1 / db2.
     On the fused route dz1 = act1'(hidden) * (dz2 . W2) is formed inside the two first-layer products."""
 
-    def __init__(self, d_out, out, ld_out, act2, W2, hidden, H, act1, n_out, x_in, ld_in, n_in, W1, ldw1, dW1, dW2,
-                 db1, db2, norm_acc=None):
-        """norm_acc: device scalar that takes sum_s ||dz2[s]|| (the trainer's norm-bound sums), accumulated by the pass
+    def __init__(self, mlp, grads, acts, norm_acc=None):
+        """mlp: the _Mlp2; grads = (dW1, dW2, db1, db2), the destinations the weight products add to; acts = (d_out, out,
+        hidden, x_in, ld_in), the loss gradient and what the forward left, x_in with its leading dimension
+        norm_acc: device scalar that takes sum_s ||dz2[s]|| (the trainer's norm-bound sums), accumulated by the pass
         that forms dz2 when that pass is the elementwise one (self.norm_noted says whether it was)"""
-        self.a = (d_out, out, ld_out, act2, W2, hidden, H, act1, n_out, x_in, ld_in, n_in, W1, ldw1, dW1, dW2, db1, db2)
+        self.mlp = mlp
+        self.dW1, self.dW2, self.db1, self.db2 = grads
+        d_out, out, self.hidden, self.x_in, self.ld_in = acts
+        H, n_out = mlp.H, mlp.n_out
         self.norm_noted = False
-        n = hidden.shape[0]
-        dev = hidden.device
-        self.n = n
+        n = self.n = self.hidden.shape[0]
+        dev = self.hidden.device
+        ld_out = out.stride(0)
         self.fused = bool(n_out <= _FUSED_BWD_MAX_OUT and d_out.stride(0) == n_out and ld_out == n_out)
         self.dz1 = None
         self.dw2_done = False
         if self.fused:
             self.dz2 = torch.empty(n, n_out, dtype=_f32, device=dev)
             if norm_acc is not None and n_out <= 4:
-                call("act_bwd_rows", d_out, out, n, n_out, act2, self.dz2, norm_acc)
+                call("act_bwd_rows", d_out, out, n, n_out, mlp.act2, self.dz2, norm_acc)
                 self.norm_noted = True
             else:
-                call("act_bwd", d_out, out, n * n_out, act2, self.dz2)
+                call("act_bwd", d_out, out, n * n_out, mlp.act2, self.dz2)
             return
         self.dz2 = torch.empty(n, 16 if n_out > 4 else 4, dtype=_f32, device=dev)
         self.dz1 = torch.empty(n, H, dtype=_f32, device=dev)
         if n_out <= 4:   # dW2 / db2 come out of the same pass over the hidden activations
-            call("mlp_hidden_bwd", d_out, d_out.stride(0), out, ld_out, act2, W2, H, hidden, H, act1, n, H, n_out,
-                 None, 0, self.dz1, H, dW2, H, db2)
+            call("mlp_hidden_bwd", d_out, d_out.stride(0), out, ld_out, mlp.act2, mlp.W2, H, self.hidden, H, mlp.act1, n, H,
+                 n_out, None, 0, self.dz1, H, self.dW2, H, self.db2)
             self.dw2_done = True
         else:
-            call("mlp_hidden_bwd", d_out, d_out.stride(0), out, ld_out, act2, W2, H, hidden, H, act1, n, H, n_out,
-                 self.dz2, self.dz2.shape[1], self.dz1, H, None, 0, None)
+            call("mlp_hidden_bwd", d_out, d_out.stride(0), out, ld_out, mlp.act2, mlp.W2, H, self.hidden, H, mlp.act1, n, H,
+                 n_out, self.dz2, self.dz2.shape[1], self.dz1, H, None, 0, None)
 
     def input_product(self, dx, ld_dx, dx_cols, w1_col0, accumulate):
         """dx (+)= dz1 . W1[:, w1_col0 : w1_col0 + dx_cols] (the input columns that need a gradient)"""
-        (d_out, out, ld_out, act2, W2, hidden, H, act1, n_out, x_in, ld_in, n_in, W1, ldw1, dW1, dW2, db1, db2) = self.a
-        w1_dx = W1[w1_col0:] if W1.dim() == 1 else W1
+        mlp = self.mlp
+        w1_dx = mlp.W1[w1_col0:] if mlp.W1.dim() == 1 else mlp.W1
         if self.fused:
-            call("mlp_bwd_input", self.dz2, n_out, W2, H, hidden, H, act1, w1_dx, ldw1, self.n, dx_cols, H, n_out, dx, ld_dx,
-                 1 if accumulate else 0)
+            call("mlp_bwd_input", self.dz2, mlp.n_out, mlp.W2, mlp.H, self.hidden, mlp.H, mlp.act1, w1_dx, mlp.ldw1, self.n,
+                 dx_cols, mlp.H, mlp.n_out, dx, ld_dx, 1 if accumulate else 0)
         else:
-            call("linear_bwd_input", self.dz1, H, w1_dx, ldw1, self.n, dx_cols, H, dx, ld_dx, 1 if accumulate else 0)
+            call("linear_bwd_input", self.dz1, mlp.H, w1_dx, mlp.ldw1, self.n, dx_cols, mlp.H, dx, ld_dx,
+                 1 if accumulate else 0)
 
     def weight_products(self):
-        (d_out, out, ld_out, act2, W2, hidden, H, act1, n_out, x_in, ld_in, n_in, W1, ldw1, dW1, dW2, db1, db2) = self.a
-        n = self.n
-        wide = n_in > 128 and n_in % 128 <= 32
-        # 128 + remainder columns: a second launch with 128x32 tiles instead of a mostly empty 128x128
-        # tile (rgb_net's first layer is 128 x 144/160)
-        rem = n_in - 128
-        x_rem = x_in[:, 128:] if x_in.dim() == 2 else x_in
-        dW1_rem = dW1[128:] if dW1.dim() == 1 else dW1[:, 128:]
+        # One launch per product whatever n_in: rgb_net's 144 / 160 columns go through the streaming kernel in one pass,
+        # and every other first layer is at most 128 columns wide.
+        mlp, n = self.mlp, self.n
+        H, n_out = mlp.H, mlp.n_out
         if self.fused:
-            dz2 = self.dz2
             # the first-layer weight product streams dz2 and hidden anyway: it also leaves dW2 / db2
-            if wide and H == 128 and n_in in (144, 160) and act1 in (_RELU, _SOFTPLUS):
-                # the streaming kernel takes all 144 / 160 input columns (and dW2 / db2) in one pass
-                call("mlp_bwd_weight", dz2, n_out, W2, H, hidden, H, act1, x_in, ld_in, n, n_in, H, n_out, dW1, ldw1, db1,
-                     dW2, H, db2)
-            elif wide:
-                # dW2 / db2 ride with the narrow remainder launch (16 accumulator registers per lane; in the
-                # 128x128 one the extra partial sums would spill at 3 workgroups per CU)
-                call("mlp_bwd_weight", dz2, n_out, W2, H, hidden, H, act1, x_in, ld_in, n, 128, H, n_out, dW1, ldw1, db1,
-                     None, 0, None)
-                call("mlp_bwd_weight", dz2, n_out, W2, H, hidden, H, act1, x_rem, ld_in, n, rem, H, n_out, dW1_rem, ldw1,
-                     None, dW2, H, db2)
-            else:
-                call("mlp_bwd_weight", dz2, n_out, W2, H, hidden, H, act1, x_in, ld_in, n, n_in, H, n_out, dW1, ldw1, db1,
-                     dW2, H, db2)
+            call("mlp_bwd_weight", self.dz2, n_out, mlp.W2, H, self.hidden, H, mlp.act1, self.x_in, self.ld_in, n, mlp.n_in, H,
+                 n_out, self.dW1, mlp.ldw1, self.db1, self.dW2, H, self.db2)
             return
         if not self.dw2_done:
-            call("linear_bwd_weight", self.dz2, self.dz2.shape[1], hidden, H, n, H, n_out, dW2, H, db2)
-        if wide:
-            call("linear_bwd_weight", self.dz1, H, x_in, ld_in, n, 128, H, dW1, ldw1, db1)
-            call("linear_bwd_weight", self.dz1, H, x_rem, ld_in, n, rem, H, dW1_rem, ldw1, None)
-        else:
-            call("linear_bwd_weight", self.dz1, H, x_in, ld_in, n, n_in, H, dW1, ldw1, db1)
+            call("linear_bwd_weight", self.dz2, self.dz2.shape[1], self.hidden, H, n, H, n_out, self.dW2, H, self.db2)
+        call("linear_bwd_weight", self.dz1, H, self.x_in, self.ld_in, n, mlp.n_in, H, self.dW1, mlp.ldw1, self.db1)
+
+
+def _field_mlps(model, W1, b1, W2, b2, rgb_p, nrm_p, sem_p):
+    """the four MLPs of the field node -> (density head, rgb_net, normal head, semantic head)"""
+    net = model.rgb_net
+    return (_Mlp2(W1, 128, b1, W2, b2, 128, 128, 1, _SOFTPLUS, _SOFTPLUS),
+            _Mlp2.tcnn(rgb_p, net.padded_in, 128, 3, net.output_activation),
+            _Mlp2.tcnn(nrm_p, 128, 32, 3, _NONE),
+            _Mlp2.tcnn(sem_p, 128, 32, model.semantic_header.n_output_dims, _NONE))
 
 
 class _NegNormalize(Function):
@@ -260,7 +288,7 @@ class _FieldFn(Function):
         a_r = torch.empty(n, 128, dtype=_f32, device=dev)
         a_n = torch.empty(n, 32, dtype=_f32, device=dev)
         a_s = torch.empty(n, 32, dtype=_f32, device=dev)
-        net = model.rgb_net
+        density_mlp, rgb_mlp, nrm_mlp, sem_mlp = _field_mlps(model, W1, b1, W2, b2, rgb_p, nrm_p, sem_p)
 
         def colour_branch():
             # [SH(16) | rgb grid features (128) | appearance code (E) | ones-padding] -> rgb_net, the two heads
@@ -293,41 +321,31 @@ class _FieldFn(Function):
                     rgb_in[:, 144:K] = embed_a
                 if Kp > K:
                     rgb_in[:, K:] = 1.0
-            if C <= 8 and x.is_cuda:
+            if C <= 8:
                 # the two 32-wide heads read the same rows as rgb_net: on a stream of their own their 256-thread
                 # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU (-0.03 ms/step)
                 cur = torch.cuda.current_stream()
                 heads = _stream("heads", dev, link.heads_stream)
                 heads.wait_stream(cur)
                 with torch.cuda.stream(heads):
-                    call("mlp2_fwd", feat_rgb, Kp, nrm_p, 128, None, _RELU, nrm_p[32 * 128:], 32, None, _NONE,
-                         n, 128, 32, 3, a_n, 32, np_o, 3)
-                    call("mlp2_fwd", feat_rgb, Kp, sem_p, 128, None, _RELU, sem_p[32 * 128:], 32, None, _NONE,
-                         n, 128, 32, C, a_s, 32, sem_o, C)
-                call("mlp2_fwd", rgb_in, Kp, rgb_p, Kp, None, _RELU, rgb_p[128 * Kp:], 128, None, net.output_activation,
-                     n, Kp, 128, 3, a_r, 128, rgb_o, 3)
+                    nrm_mlp.forward(feat_rgb, Kp, n, a_n, np_o)
+                    sem_mlp.forward(feat_rgb, Kp, n, a_s, sem_o)
+                rgb_mlp.forward(rgb_in, Kp, n, a_r, rgb_o)
                 cur.wait_stream(heads)
-            else:
-                call("mlp2_fwd", rgb_in, Kp, rgb_p, Kp, None, _RELU, rgb_p[128 * Kp:], 128, None, net.output_activation,
-                     n, Kp, 128, 3, a_r, 128, rgb_o, 3)
-                call("mlp2_fwd", feat_rgb, Kp, nrm_p, 128, None, _RELU, nrm_p[32 * 128:], 32, None, _NONE,
-                     n, 128, 32, 3, a_n, 32, np_o, 3)
-                if C <= 8:
-                    call("mlp2_fwd", feat_rgb, Kp, sem_p, 128, None, _RELU, sem_p[32 * 128:], 32, None, _NONE,
-                         n, 128, 32, C, a_s, 32, sem_o, C)
-                else:   # (the fused forward's epilogue takes at most 8 outputs)
-                    call("linear_fwd", feat_rgb, Kp, sem_p, 128, None, n, 128, 32, _RELU, a_s, 32, None)
-                    call("linear_fwd", a_s, 32, sem_p[32 * 128:], 32, None, n, 32, C, _NONE, sem_o, C, None)
+            else:   # (the fused forward's epilogue takes at most 8 outputs)
+                rgb_mlp.forward(rgb_in, Kp, n, a_r, rgb_o)
+                nrm_mlp.forward(feat_rgb, Kp, n, a_n, np_o)
+                call("linear_fwd", feat_rgb, Kp, sem_mlp.W1, 128, None, n, 128, 32, _RELU, a_s, 32, None)
+                call("linear_fwd", a_s, 32, sem_mlp.W2, 32, None, n, 32, C, _NONE, sem_o, C, None)
 
         # The colour branch needs the positions and the colour table, nothing of the density path: it runs on a
         # stream of its own from the moment the colour table's Adam piece is done, beside the rest of the density
         # path and the analytic normals (which are stretched beyond that piece's end on one stream).
         main = torch.cuda.current_stream()
-        side = _stream("colour", dev) if x.is_cuda else None
-        if side is not None:
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                colour_branch()
+        side = _stream("colour", dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            colour_branch()
 
         # density head
         if ev_p is not None:
@@ -341,18 +359,14 @@ class _FieldFn(Function):
             call("grid_fwd", xe.desc, xyz_table, xn, n, feat, 128)
             # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
             # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
-            call("mlp2_fwd_dact", feat, 128, W1, 128, b1, _SOFTPLUS, W2, 128, b2, _SOFTPLUS, n, 128, 128, 1, a1, 128, sig,
-                 1, dz2)
+            density_mlp.forward(feat, 128, n, a1, sig, dact=dz2)
             # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
             call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
             call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, grads)
         # dfeat = d(sigma)/d(features) is kept: the density head has ONE output, so the gradient the backward
         # sends into the density encoder is d_sigma[s] * dfeat[s] — no second data-gradient product there
 
-        if side is not None:
-            main.wait_stream(side)
-        else:
-            colour_branch()
+        main.wait_stream(side)
 
         ctx.model = model
         ctx.E, ctx.K, ctx.Kp, ctx.C = E, K, Kp, C
@@ -385,6 +399,7 @@ class _FieldFn(Function):
         # launch) registers the MLP gradients as sinks: the weight products accumulate straight into
         # them and autograd gets None — no zeros_like fill, no AccumulateGrad add per parameter.
         sinks = link.grad_sinks
+        density_mlp, rgb_mlp, nrm_mlp, sem_mlp = _field_mlps(model, W1, None, W2, None, rgb_p, nrm_p, sem_p)
 
         def grad_buffer(name, like):
             t = sinks.get(name)
@@ -455,8 +470,7 @@ class _FieldFn(Function):
             acc_rgbp, g_rgbp = grad_buffer("rgb_p", rgb_p)
             dfeat_rgb = torch.empty(n, W_cols, dtype=_f32, device=dev)
             nb_acc = link.norm_acc
-            st = _Mlp2Bwd(d_rgb.contiguous(), rgb_o, 3, model.rgb_net.output_activation, rgb_p[128 * Kp:], a_r, 128,
-                          _RELU, 3, rgb_in, Kp, Kp, rgb_p, Kp, acc_rgbp, acc_rgbp[128 * Kp:], None, None,
+            st = _Mlp2Bwd(rgb_mlp, rgb_mlp.grad_slices(acc_rgbp), (d_rgb.contiguous(), rgb_o, a_r, rgb_in, Kp),
                           norm_acc=None if nb_acc is None else nb_acc[0:1])
             st.input_product(dfeat_rgb, W_cols, W_cols, 16, False)
             stages.append(st)
@@ -467,7 +481,8 @@ class _FieldFn(Function):
                 st.input_product(d_sh, 16, 16, 0, False)
                 g_d = torch.empty(n, 3, dtype=_f32, device=dev)
                 call("sh_bwd_dirs", ctx.saved_tensors[19], d_sh, 16, n, g_d)
-        for d_o, p, a_h, out, n_out, slot in ((d_np, nrm_p, a_n, np_o, 3, "nrm"), (d_sem, sem_p, a_s, sem_o, C, "sem")):
+        for d_o, p, mlp, a_h, out, slot in ((d_np, nrm_p, nrm_mlp, a_n, np_o, "nrm"),
+                                            (d_sem, sem_p, sem_mlp, a_s, sem_o, "sem")):
             if d_o is None:
                 continue
             link.bound_spoiled()    # a head adds to the colour features' gradient: outside the norm bound
@@ -475,8 +490,7 @@ class _FieldFn(Function):
             first = dfeat_rgb is None
             if first:
                 dfeat_rgb = torch.zeros(n, W_cols, dtype=_f32, device=dev) if E else torch.empty(n, W_cols, dtype=_f32, device=dev)
-            st = _Mlp2Bwd(d_o.contiguous(), out, n_out, _NONE, p[32 * 128:], a_h, 32, _RELU, n_out,
-                          rgb_in[:, 16:], Kp, 128, p, 128, acc_p, acc_p[32 * 128:], None, None)
+            st = _Mlp2Bwd(mlp, mlp.grad_slices(acc_p), (d_o.contiguous(), out, a_h, rgb_in[:, 16:], Kp))
             st.input_product(dfeat_rgb, W_cols, 128, 0, not first)
             stages.append(st)
             if slot == "nrm":
@@ -531,7 +545,7 @@ class _FieldFn(Function):
             call("linear_fwd", u, 128, W1, 128, None, n, 128, 128, _NONE, r, 128, None)
             m = torch.empty(n, 128, dtype=_f32, device=dev)
             call("density_head_bwd2", a1, sig, r, W2, None if d_sig is None else d_sig.contiguous(), n, m, r, acc_W2, acc_b2,
-                 _head2_workspace(dev))
+                 _workspace("density_head_bwd2", dev))
             call("linear_bwd_weight", m, 128, u, 128, n, 128, 128, acc_W1, 128, None)
             call("linear_bwd_weight", r, 128, feat, 128, n, 128, 128, acc_W1, 128, acc_b1)      # (r holds e1 now)
             if buf is not None:
@@ -542,8 +556,7 @@ class _FieldFn(Function):
             (acc_W1, g_W1), (acc_W2, g_W2) = grad_buffer("W1", W1), grad_buffer("W2", W2)
             (acc_b1, g_b1), (acc_b2, g_b2) = grad_buffer("b1", (128,)), grad_buffer("b2", (1,))
             nb_acc = link.norm_acc
-            st = _Mlp2Bwd(d_sig.contiguous().view(n, 1), sig, 1, _SOFTPLUS, W2, a1, 128, _SOFTPLUS, 1,
-                          feat, 128, 128, W1, 128, acc_W1, acc_W2, acc_b1, acc_b2,
+            st = _Mlp2Bwd(density_mlp, (acc_W1, acc_W2, acc_b1, acc_b2), (d_sig.contiguous().view(n, 1), sig, a1, feat, 128),
                           norm_acc=None if nb_acc is None else nb_acc[1:2])
             if not reuse:
                 dfeat = torch.empty(n, 128, dtype=_f32, device=dev)
@@ -570,29 +583,18 @@ class _FieldFn(Function):
         return (None, g_x, g_d, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None, None)
 
 
-_HEAD2_WS = {}
+_WORKSPACES = {}
 
 
-def _head2_workspace(dev):
-    """ngp_density_head_bwd2's scratch (the workgroups' partial sums: at most 1024 x 129 doubles), one per device AND
-    stream, as _tone_workspace is and for its reason"""
-    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _HEAD2_WS:
-        _HEAD2_WS[key] = torch.empty(call_host("density_head_bwd2_workspace", 1 << 40), dtype=_f32, device=dev)
-    return _HEAD2_WS[key]
-
-
-_TONE_WS = {}
-
-
-def _tone_workspace(dev):
-    """ngp_tonemap_bwd's scratch (the workgroups' partial sums: at most 512 x 576 doubles), one per device AND stream: two
-    backwards on one stream run one behind the other (a step's render and its unit-exposure term do), backwards on two
-    streams may overlap and must not share their partial sums"""
-    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _TONE_WS:
-        _TONE_WS[key] = torch.empty(call_host("tonemap_bwd_workspace", 1 << 40), dtype=_f32, device=dev)
-    return _TONE_WS[key]
+def _workspace(entry, dev):
+    """scratch of a backward entry point that sums in two passes (the workgroups' partial sums, as doubles), sized for any
+    n by the host call `entry`_workspace.  One per entry, device AND stream: two backwards on one stream run one behind
+    the other (a step's render and its unit-exposure term do), backwards on two streams may overlap and must not share
+    their partial sums.  entry: density_head_bwd2 (at most 1024 x 129 doubles), tonemap_bwd (512 x 576), skybox_bwd (256 x 416)"""
+    key = (entry, torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
+    if key not in _WORKSPACES:
+        _WORKSPACES[key] = torch.empty(call_host(entry + "_workspace", 1 << 40), dtype=_f32, device=dev)
+    return _WORKSPACES[key]
 
 
 class _ToneMapFn(Function):
@@ -625,22 +627,10 @@ class _ToneMapFn(Function):
             out = [torch.zeros_like(p) for p in (p0, p1, p2)]
         dx = torch.empty_like(log_radiance) if need_x else None
         call("tonemap_bwd", p0, p1, p2, log_radiance, exposure, ctx.stride, g.contiguous(), log_radiance.shape[0], dx,
-             *out, _tone_workspace(g.device))
+             *out, _workspace("tonemap_bwd", g.device))
         if to_sinks or not need_p:
             return (dx,) + (None,) * 5
         return (dx, None) + tuple(t if need else None for t, need in zip(out, ctx.needs_input_grad[2:5])) + (None,)
-
-
-_SKY_WS = {}
-
-
-def _sky_workspace(dev):
-    """ngp_skybox_bwd's scratch (the workgroups' partial sums: at most 256 x 416 doubles), one per device AND stream, as
-    _tone_workspace is and for its reason"""
-    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _SKY_WS:
-        _SKY_WS[key] = torch.empty(call_host("skybox_bwd_workspace", 1 << 40), dtype=_f32, device=dev)
-    return _SKY_WS[key]
 
 
 class _SkyFn(Function):
@@ -664,7 +654,7 @@ class _SkyFn(Function):
             return None, None, None
         sink = ctx.owner.link.grad_sinks.get("sky")
         out = sink if sink is not None else torch.zeros_like(params)
-        call("skybox_bwd", params, rays_d, g.contiguous(), rays_d.shape[0], out, _sky_workspace(g.device))
+        call("skybox_bwd", params, rays_d, g.contiguous(), rays_d.shape[0], out, _workspace("skybox_bwd", g.device))
         return None, (None if sink is not None else out), None
 
 
@@ -796,8 +786,6 @@ class NGP(nn.Module):
                 if embed_a.weight.shape[1] != self.rgb_net.n_input_dims - 144:
                     raise ValueError(f"codes of length {embed_a.weight.shape[1]} for a model built with embed_a_len="
                                      f"{self.rgb_net.n_input_dims - 144}")
-                if not x.is_cuda:
-                    raise RuntimeError("RayCodes needs CUDA tensors")
                 ray_codes = (embed_a.img_idxs, embed_a.rays_a.contiguous())
                 if getattr(embed_a.rays_a, "_ngp_full_cover", False):
                     ray_codes[1]._ngp_full_cover = True
@@ -817,6 +805,8 @@ class NGP(nn.Module):
             if x.requires_grad:
                 raise RuntimeError("second_order_normals with sample positions that require a gradient (pose refinement): "
                                    "the field's second order has no dL/dx")
+        if not x.is_cuda:   # (every launch of the node takes device pointers)
+            raise RuntimeError("x must be a CUDA tensor")
         return _FieldFn.apply(self, x.contiguous(), d.contiguous(), embed_a,
                               self.xyz_encoder.params, lin1.weight, lin1.bias, lin2.weight, lin2.bias,
                               self.rgb_encoder.params, self.rgb_net.params, self.norm_pred_header.params,

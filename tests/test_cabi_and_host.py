@@ -91,6 +91,20 @@ def test_no_cpu_fallback(ngp):
     assert "CDLL" in src
 
 
+def test_field_node_refuses_cpu_tensors_without_a_launch(ngp, monkeypatch):
+    """every launch of the field's autograd node takes device pointers: a CPU model given CPU tensors is refused by
+    NGP._field with a RuntimeError before anything is launched"""
+    def no_launch(name, *args):
+        pytest.fail(f"ngp_{name} launched for CPU tensors")
+    monkeypatch.setattr(ngp.networks, "call", no_launch)
+    model = ngp.networks.NGP(scale=0.5)
+    x, d = torch.zeros(4, 3), torch.ones(4, 3)
+    with pytest.raises(RuntimeError, match="x must be a CUDA tensor"):
+        model._field(x, d, {})
+    with pytest.raises(RuntimeError, match="x must be a CUDA tensor"), torch.no_grad():
+        model._field(x, d, {})
+
+
 def test_grid_layout_matches_oracle_and_reference_counts(ngp):
     """Level geometry of the two encoders of models/networks.py:36-76 at scale 0.5."""
     b = float(np.exp(np.log(2048 * 0.5 / 16) / 15))
