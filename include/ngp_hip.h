@@ -843,6 +843,50 @@ int ngp_mesh_compact_faces(const int32_t* faces, int n_faces, int n_verts, const
                            int32_t* faces_out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * M3  mesh simplification: uniform vertex clustering (Rossignac-Borrel) with one quadric solve per cell (Lindstrom)
+ * verts (n_verts, 3) f32, faces (n_faces, 3) int32 with every index in [0, n_verts) (the caller checks it);
+ * n_verts, n_faces <= 2^28.  The cell key of a vertex is floorf((v_a - origin3[a]) * inv_cell) per axis in f32
+ * without contraction (inv_cell = 1.f / cell, formed by the caller); vertices with equal keys form a cluster, and
+ * clusters are numbered in ascending order of their smallest member.  A face with two corners in one cluster is
+ * degenerate; of the faces with the same unordered cluster triple only the one with the smallest index is kept.
+ * ngp_mesh_simplify_count (the count-only path: nothing is summed or emitted) leaves on the device totals[0] =
+ * clusters, totals[1] = kept faces, totals[2] = degenerate faces, totals[3] = error bits (1: a non-finite coordinate
+ * or a key outside [0, 2^21); 2: a hash table had no room; the other totals mean nothing then), and in workspace
+ * (ngp_mesh_simplify_workspace(n_verts, n_faces) int32 elements, 8-byte aligned; host-only query, NGP_EINVAL for a
+ * size that is negative or above 2^28) what the calls below need.  Its tables are open-addressing, at least twice
+ * the element count, filled with integer atomicCAS / atomicMin; every probe loop is bounded by the capacity, and no
+ * launch reads what another workgroup stored in that launch except through an atomic's return value.
+ * ngp_mesh_simplify_groups writes vert_cluster (n_verts) and corner_cluster (3 n_faces, index 3 * face + corner).
+ * The caller sorts each once, stably, into sorted_* (the cluster numbers, ascending) and order_* (the vertex, or
+ * 3 * face + corner, of each entry), int32.  ngp_mesh_simplify_place then writes one vertex per cluster
+ * (n_clusters = totals[0]): all sums in double over the f32 inputs in that order, no floating-point atomics (the same
+ * bytes from run to run).  m = the members' mean.  quadric == 0: x = m.  Otherwise every corner of every input face
+ * adds n n^T to A and (n . p0) n to b of its cluster, n = (p1 - p0) x (p2 - p0); t = trace A; t zero or not finite:
+ * x = m; else lambda = regularization * t / 3 and (A + lambda I) x = b + lambda m by Cholesky, x clamped per axis to
+ * [origin + key * cell, origin + (key + 1) * cell] in double; rounded to f32.  normals / colors (n_verts, 3) f32 /
+ * uint8 or NULL: normals_out = the members' mean, normalised ((0,0,0) where it vanishes), colors_out = floor(mean +
+ * 0.5) in integers.  ngp_mesh_simplify_faces writes the kept faces (totals[1], 3) as cluster numbers in their
+ * original order and winding and adds to used[c] (n_clusters, zeroed by the caller) the kept corners at cluster c:
+ * with labels[c] = c and keep[c] = 1 that is the face_counts ngp_mesh_compact_* (M2) takes to drop unused clusters.
+ * origin3 is a HOST array of 3 floats.  n_verts == 0 returns NGP_OK before any pointer is looked at (n_faces == 0
+ * too where only faces are written); every pointer is checked (NGP_EINVAL) before any launch.
+ * ---------------------------------------------------------------------- */
+int64_t ngp_mesh_simplify_workspace(int n_verts, int n_faces);
+int ngp_mesh_simplify_count(const float* verts, int n_verts, const int32_t* faces, int n_faces,
+                            const float* origin3 /* host */, float inv_cell, int32_t* workspace, int32_t* totals,
+                            void* stream);
+int ngp_mesh_simplify_groups(const int32_t* faces, int n_faces, int n_verts, const int32_t* workspace,
+                             int32_t* vert_cluster, int32_t* corner_cluster, void* stream);
+int ngp_mesh_simplify_place(const float* verts, int n_verts, const int32_t* faces, int n_faces,
+                            const float* origin3 /* host */, float cell, float inv_cell, double regularization,
+                            int quadric, int n_clusters, const int32_t* sorted_v, const int32_t* order_v,
+                            const int32_t* sorted_c, const int32_t* order_c, const float* normals,
+                            const uint8_t* colors, float* verts_out, float* normals_out, uint8_t* colors_out,
+                            void* stream);
+int ngp_mesh_simplify_faces(const int32_t* faces, int n_faces, int n_verts, const int32_t* workspace,
+                            int32_t* faces_out, int32_t* used, void* stream);
+
+/* ------------------------------------------------------------------------
  * I1  SSIM of rendered images (replaces torchmetrics' StructuralSimilarityIndexMeasure(data_range=1) of the
  *     reference's validation step, train.py:93,353-386; no conv2d / MIOpen on the way)
  * pred, gt: `count` images of H*W rows of 3 floats, row-major, channel-last (what render() returns and the loaders

@@ -33,6 +33,7 @@ SOURCES = [
     ("pose_kernels.hip", ["-ffp-contract=off"]),    # at dR = dT = 0 the rays are bit-identical to get_rays' products
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),
+    ("mesh_simplify_kernels.hip", ["-ffp-contract=off"]),   # cell keys are bit-identical to their numpy restatement
     ("image_kernels.hip", ["-ffp-contract=off"]),   # frame packing is bit-identical to its numpy restatement
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

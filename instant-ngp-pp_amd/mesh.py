@@ -4,8 +4,10 @@ own.
 
   marching_cubes(volume, level, spacing, origin) -> verts (V,3) f32, faces (F,3) i32 on the volume's device
   extract_mesh(model, ...)                        -> the same for NGP.density sampled on a dense lattice
+                                                     (MC -> clean_mesh -> simplify_mesh -> normals -> colours)
   mesh_components(faces, n_verts)                 -> per-vertex component labels and faces per component (M2)
   clean_mesh(verts, faces, keep_largest=, min_faces=) -> the mesh without its small disconnected pieces (M2)
+  simplify_mesh(verts, faces, cell= | target_faces=)  -> a smaller mesh: vertex clustering, quadric placement (M3)
   vertex_colors(model, verts, normals, offset)    -> (V,3) uint8 colours rendered by the test-time marcher
   write_ply(path, verts, faces, normals, colors) / read_ply(path, colors=False)
 
@@ -14,6 +16,7 @@ are resolved by one face-local rule (inside corners are separated), so closed su
 the triangle order and the ambiguity choices are not skimage's (Lewiner) ones.
 """
 import ctypes as C
+import time
 
 import numpy as np
 import torch
@@ -106,7 +109,8 @@ def vertex_normals(model, verts, chunk=128 ** 3):
 
 
 def extract_mesh(model, xyz_min=None, xyz_max=None, resolution=512, level=10.0, chunk=128 ** 3, normals=False,
-                 reference_spacing=False, keep_largest=None, min_faces=None, colors=False, color_offset=None):
+                 reference_spacing=False, keep_largest=None, min_faces=None, colors=False, color_offset=None,
+                 simplify_cell=None, target_faces=None, placement='quadric', stats=None):
     """Mesh of the level set {sigma = level} of `model` (an NGP) -> verts (V,3), faces (F,3) [, normals (V,3)].
 
     The lattice spans [xyz_min, xyz_max] (default: the model's own box) with `resolution` (an int or (nx, ny, nz))
@@ -122,7 +126,14 @@ def extract_mesh(model, xyz_min=None, xyz_max=None, resolution=512, level=10.0, 
 
     keep_largest / min_faces remove small disconnected pieces (clean_mesh) before normals and colours are computed.
     colors=True adds per-vertex uint8 RGB (vertex_colors) rendered from color_offset (default: twice the largest
-    lattice spacing) outside each vertex.  The result is (verts, faces[, normals][, colors])."""
+    lattice spacing) outside each vertex.
+
+    simplify_cell=X or target_faces=N (one of them) simplifies the cleaned mesh (simplify_mesh, cells from the
+    lattice's xyz_min, `placement`) before normals and colours, which are then evaluated on the field at the new
+    vertices (nothing is averaged); a dict passed as `stats` receives simplify_mesh's stats.
+    The result is (verts, faces[, normals][, colors])."""
+    if simplify_cell is not None and target_faces is not None:
+        raise ValueError("give at most one of simplify_cell and target_faces")
     lo = _vec3(model.xyz_min if xyz_min is None else xyz_min)
     hi = _vec3(model.xyz_max if xyz_max is None else xyz_max)
     vol = density_volume(model, lo, hi, resolution, chunk)
@@ -131,6 +142,9 @@ def extract_mesh(model, xyz_min=None, xyz_max=None, resolution=512, level=10.0, 
     del vol
     if keep_largest is not None or min_faces is not None:
         verts, faces = clean_mesh(verts, faces, keep_largest=keep_largest, min_faces=min_faces)
+    if simplify_cell is not None or target_faces is not None:
+        verts, faces = simplify_mesh(verts, faces, cell=simplify_cell, target_faces=target_faces, origin=lo,
+                                     placement=placement, stats=stats)
     out = [verts, faces]
     nrm = vertex_normals(model, verts, chunk) if normals or colors else None
     if normals:
@@ -236,24 +250,203 @@ def clean_mesh(verts, faces, *, normals=None, colors=None, keep_largest=None, mi
     if n_verts:
         call("mesh_face_counts", faces, n_faces, n_verts, labels, counts)
     keep = select_components(counts, keep_largest, min_faces)
-    ws = torch.empty(call_host("mesh_clean_workspace", n_verts, n_faces), dtype=torch.int32, device=verts.device)
-    totals = torch.zeros(2, dtype=torch.int32, device=verts.device)
+    out, f_out = _compact([verts] + attrs, faces, labels, counts, keep)
+    if stats is not None:
+        stats.update(rounds=rounds, components=int((counts > 0).sum()), components_kept=int(keep.sum()),
+                     V_removed=n_verts - out[0].shape[0], F_removed=n_faces - f_out.shape[0])
+    return (out[0], f_out, *out[1:])
+
+
+def _compact(rows, faces, labels, counts, keep):
+    """ngp_mesh_compact_*: the faces whose label is kept and the vertices those use (keep[label] and counts[label] >
+    0), in their original order; rows is a list of (V, ...) per-vertex arrays -> (their kept rows, faces renumbered)"""
+    n_verts, n_faces = labels.shape[0], faces.shape[0]
+    dev = faces.device
+    ws = torch.empty(call_host("mesh_clean_workspace", n_verts, n_faces), dtype=torch.int32, device=dev)
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
     if n_verts:
         call("mesh_compact_count", faces, n_faces, n_verts, labels, counts, keep, ws, totals)
     n_v, n_f = totals.tolist()
-    out = [torch.empty(n_v, 3, dtype=_f32, device=verts.device)]
-    out += [torch.empty((n_v,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device) for a in attrs]
-    for src, dst in zip([verts] + attrs, out):
+    out = [torch.empty((n_v,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device) for a in rows]
+    for src, dst in zip(rows, out):
         if n_v:
             row_bytes = src[0].numel() * src.element_size()
             call("mesh_compact_rows", src, row_bytes, n_verts, n_faces, ws, dst)
-    f_out = torch.empty(n_f, 3, dtype=torch.int32, device=faces.device)
+    f_out = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
     if n_f:
         call("mesh_compact_faces", faces, n_faces, n_verts, ws, f_out)
-    if stats is not None:
-        stats.update(rounds=rounds, components=int((counts > 0).sum()), components_kept=int(keep.sum()),
-                     V_removed=n_verts - n_v, F_removed=n_faces - n_f)
-    return (out[0], f_out, *out[1:])
+    return out, f_out
+
+
+# ------------------------------------------------------------------------------------------- simplification (M3)
+MAX_CELLS = 1 << 20   # the most cells along the longest axis that target_faces tries
+
+
+def _check_mesh(verts, faces, normals, colors):
+    check_input(verts, "verts")
+    if verts.dtype != _f32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts must be a (V, 3) float32 tensor, got {tuple(verts.shape)} {verts.dtype}")
+    _check_faces(faces, verts.shape[0])
+    for name, a, dtype in (("normals", normals, _f32), ("colors", colors, torch.uint8)):
+        if a is not None:
+            check_input(a, name)
+            if a.dtype != dtype or tuple(a.shape) != (verts.shape[0], 3):
+                raise ValueError(f"{name} must be a ({verts.shape[0]}, 3) {dtype} tensor, got {tuple(a.shape)} "
+                                 f"{a.dtype}")
+
+
+class _Clustering:
+    """the count-only path of ngp_mesh_simplify_*: one workspace, one call and one read-back per cell size"""
+
+    def __init__(self, verts, faces, origin):
+        self.verts, self.faces = verts, faces
+        self.n_verts, self.n_faces = verts.shape[0], faces.shape[0]
+        self.origin = (C.c_float * 3)(*origin)
+        n_ws = call_host("mesh_simplify_workspace", self.n_verts, self.n_faces)
+        if n_ws < 0:
+            raise ValueError(f"unsupported mesh size: {self.n_verts} vertices, {self.n_faces} faces")
+        self.ws = torch.empty(n_ws, dtype=torch.int32, device=verts.device)
+        self.totals = torch.zeros(4, dtype=torch.int32, device=verts.device)
+        self.cell = None
+
+    def count(self, cell):
+        """-> (clusters, kept faces, degenerate faces) for cells of size float32(cell) from the origin"""
+        cell = np.float32(cell)
+        with np.errstate(all="ignore"):
+            inv = np.float32(1) / cell
+        if not (cell > 0 and np.isfinite(cell) and np.isfinite(inv)):
+            raise ValueError(f"cell must be a positive float32 with a finite inverse, got {cell}")
+        self.cell, self.inv = float(cell), float(inv)
+        call("mesh_simplify_count", self.verts, self.n_verts, self.faces, self.n_faces, self.origin, self.inv, self.ws,
+             self.totals)
+        clusters, kept, degenerate, err = self.totals.tolist()
+        if err & 1:
+            raise ValueError(f"a vertex is not finite, or its cell lies outside [0, 2^21) per axis (cell {cell}, "
+                             f"origin {list(self.origin)})")
+        if err:
+            raise RuntimeError("ngp_mesh_simplify_count: a hash table had no room")
+        return clusters, kept, degenerate
+
+
+def _search_cells(clustering, extent, target_faces):
+    """the number of cells k along the longest axis (cell = float32(extent / k)) for target_faces: k doubles from 1
+    until more than target_faces faces are kept (or nothing merges any more, or k = MAX_CELLS), then a bisection
+    finds a k that keeps <= target_faces faces while k + 1 keeps more -> (k, probes); k = 0 when even k = 1 keeps too
+    many (vertices exactly on the upper faces of the bounding box open a second layer of cells)"""
+    probes, k, lo, hi = 0, 1, 0, None
+    while True:
+        clusters, kept, _ = clustering.count(extent / k)
+        probes += 1
+        if kept > target_faces:
+            hi = k
+            break
+        lo = k
+        if clusters == clustering.n_verts or k >= MAX_CELLS:
+            break
+        k *= 2
+    while hi is not None and hi - lo > 1:
+        mid = (lo + hi) // 2
+        kept = clustering.count(extent / mid)[1]
+        probes += 1
+        lo, hi = (mid, hi) if kept <= target_faces else (lo, mid)
+    return lo, probes
+
+
+def simplify_mesh(verts, faces, *, cell=None, target_faces=None, origin=None, placement='quadric', regularization=1e-3,
+                  normals=None, colors=None, stats=None):
+    """Uniform vertex clustering with quadric placement (M3) -> (verts, faces[, normals][, colors]).
+
+    Vertices whose key floorf((v - origin) * (1/cell)) (float32, per axis) agrees form a cluster; clusters are numbered
+    by their smallest member.  Each cluster becomes one vertex: placement='mean' puts it at the members' mean;
+    'quadric' at the minimiser of the squared distances to the planes of the faces at its members, weighted by squared
+    face area and regularised toward the mean (lambda = regularization * trace / 3), clamped to the cell, so creases
+    and corners stay where a mean rounds them off.  Faces are renumbered; a face with two corners in one cluster is
+    dropped (`degenerate`), as is every face but the first of each unordered corner triple (`duplicate`); kept faces
+    keep order and winding, and clusters no kept face uses are dropped.  Every vertex moves by at most the cell's
+    diagonal.  The mesh need not stay manifold.  normals (V,3) f32 / colors (V,3) uint8 are averaged per cluster
+    (normalised / rounded).  All sums run in double in a fixed order: the result is the same from run to run.
+
+    Exactly one of cell (> 0) and target_faces (>= 0).  target_faces=N picks cell = float32(longest bounding-box
+    extent / k) by the search of _search_cells (count-only passes) so that at most N faces are kept; a mesh that has
+    no more than N faces comes back unchanged.  origin defaults to verts.amin(0); keys must lie in [0, 2^21).
+    A dict passed as `stats` receives cell, k and probes (None / 0 without target_faces), clusters, V_in, V_out, F_in,
+    F_out, degenerate, duplicate, and probe_ms / emit_ms (host clocks around device synchronisation)."""
+    _check_mesh(verts, faces, normals, colors)
+    if (cell is None) == (target_faces is None):
+        raise ValueError("give exactly one of cell and target_faces")
+    if placement not in ('quadric', 'mean'):
+        raise ValueError(f"placement must be 'quadric' or 'mean', got {placement!r}")
+    if not (regularization > 0 and np.isfinite(regularization)):
+        raise ValueError(f"regularization must be positive, got {regularization}")
+    if cell is not None and not (float(cell) > 0 and np.isfinite(float(cell))):
+        raise ValueError(f"cell must be positive, got {cell}")
+    if target_faces is not None and int(target_faces) < 0:
+        raise ValueError(f"target_faces must be >= 0, got {target_faces}")
+    n_verts, n_faces = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    attrs = [a for a in (normals, colors) if a is not None]
+    info = dict(cell=None, k=None, probes=0, clusters=n_verts, V_in=n_verts, V_out=n_verts, F_in=n_faces,
+                F_out=n_faces, degenerate=0, duplicate=0, probe_ms=0.0, emit_ms=0.0)
+
+    def done(out_v, out_f, out_attrs):
+        info.update(V_out=out_v.shape[0], F_out=out_f.shape[0])
+        if stats is not None:
+            stats.update(info)
+        return (out_v, out_f, *out_attrs)
+
+    def nothing():
+        return done(verts[:0].clone(), faces[:0].clone(), [a[:0].clone() for a in attrs])
+
+    if n_verts == 0:
+        return nothing()
+    if target_faces is not None and n_faces <= int(target_faces):
+        return done(verts, faces, attrs)
+    lo, hi = torch.aminmax(verts, dim=0)
+    if not bool(torch.isfinite(lo).all() and torch.isfinite(hi).all()):
+        raise ValueError("verts holds a value that is not finite")
+    origin = _vec3(lo if origin is None else origin)
+    clustering = _Clustering(verts, faces, origin)
+    t0 = time.perf_counter()
+    if target_faces is not None:
+        extent = float((hi - lo).max())
+        if not np.isfinite(extent):
+            raise ValueError("the bounding box of verts is not finite")
+        extent = extent if extent > 0 else 1.0     # one point: every cell size merges everything
+        k, probes = _search_cells(clustering, extent, int(target_faces))
+        info.update(k=k, probes=probes)
+        if k == 0:
+            return nothing()
+        cell = extent / k
+    info["probe_ms"] = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    # the workspace holds the last probe's tables: count once more at the chosen cell, then emit from it
+    clusters, kept, degenerate = clustering.count(cell)
+    info.update(cell=clustering.cell, clusters=clusters, degenerate=degenerate, duplicate=n_faces - degenerate - kept)
+    if kept == 0:
+        return nothing()
+    vert_cluster = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    corner_cluster = torch.empty(3 * n_faces, dtype=torch.int32, device=dev)
+    call("mesh_simplify_groups", faces, n_faces, n_verts, clustering.ws, vert_cluster, corner_cluster)
+    # members of a cluster side by side, in ascending index order: one stable sort per array
+    sorted_v, order_v = torch.sort(vert_cluster, stable=True)
+    sorted_c, order_c = torch.sort(corner_cluster, stable=True)
+    order_v, order_c = order_v.to(torch.int32), order_c.to(torch.int32)
+    rows = [torch.empty(clusters, 3, dtype=_f32, device=dev)]
+    rows += [torch.empty(clusters, 3, dtype=a.dtype, device=dev) for a in attrs]
+    call("mesh_simplify_place", verts, n_verts, faces, n_faces, clustering.origin, clustering.cell, clustering.inv,
+         float(regularization), int(placement == 'quadric'), clusters, sorted_v, order_v, sorted_c, order_c,
+         normals, colors, rows[0], rows[1] if normals is not None else None,
+         rows[-1] if colors is not None else None)
+    kept_faces = torch.empty(kept, 3, dtype=torch.int32, device=dev)
+    used = torch.zeros(clusters, dtype=torch.int32, device=dev)
+    call("mesh_simplify_faces", faces, n_faces, n_verts, clustering.ws, kept_faces, used)
+    # clusters that no kept face uses go, as in clean_mesh without a criterion: every cluster is its own label
+    labels = torch.empty(clusters, dtype=torch.int32, device=dev)
+    call("mesh_labels_init", labels, clusters)
+    out, f_out = _compact(rows, kept_faces, labels, used, torch.ones(clusters, dtype=torch.uint8, device=dev))
+    torch.cuda.synchronize(dev)
+    info["emit_ms"] = 1e3 * (time.perf_counter() - t0)
+    return done(out[0], f_out, out[1:])
 
 
 # ------------------------------------------------------------------------------------------------- vertex colours

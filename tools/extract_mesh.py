@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Extracts a triangle mesh from a trained checkpoint and writes it as binary PLY (the reference's extract_mesh.py:
 density on a dense lattice, marching cubes, PLY).  GPU only.  Prints one JSON line: V, F and the milliseconds of the
-density pass, marching cubes, the cleaning, the normals, the colours, the device->host copy and the PLY write (each
-timed around a device synchronise), and what the cleaning found and removed.
+density pass, marching cubes, the cleaning, the simplification, the normals, the colours, the device->host copy and
+the PLY write (each timed around a device synchronise), what the cleaning found and removed, and what the
+simplification did (cell, k, probes, clusters, V_in, V_out, F_in, F_out, degenerate, duplicate, probe_ms, emit_ms).
 
   python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --resolution 256 --normals
   python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --keep_largest 1 --colors
+  python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --keep_largest 1 --target_faces 100000
 """
 import argparse
 import json
@@ -43,6 +45,13 @@ def main(argv=None):
     ap.add_argument("--keep_largest", type=int, metavar="K",
                     help="keep only the K connected pieces with the most faces (floater removal)")
     ap.add_argument("--min_faces", type=int, metavar="M", help="keep only the connected pieces with at least M faces")
+    simplify = ap.add_mutually_exclusive_group()
+    simplify.add_argument("--simplify_cell", type=float, metavar="X",
+                          help="merge the vertices of each cubic cell of edge X (from the lattice's corner) into one")
+    simplify.add_argument("--target_faces", type=int, metavar="N",
+                          help="simplify with the smallest cell found that leaves at most N faces")
+    ap.add_argument("--placement", choices=("quadric", "mean"), default="quadric",
+                    help="where a merged vertex goes: the quadric minimiser of its faces' planes, or the mean")
     ap.add_argument("--colors", action="store_true",
                     help="per-vertex RGB rendered from the trained appearance field (PLY red green blue)")
     ap.add_argument("--embed_a", action="store_true",
@@ -55,6 +64,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes 1 or 3 values")
+    if args.simplify_cell is not None and not args.simplify_cell > 0:
+        ap.error("--simplify_cell must be positive")
+    if args.target_faces is not None and args.target_faces < 0:
+        ap.error("--target_faces must be >= 0")
     res = args.resolution[0] if len(args.resolution) == 1 else tuple(args.resolution)
 
     dev = torch.device("cuda", 0)
@@ -84,6 +97,12 @@ def main(argv=None):
                                        stats=stats)
     torch.cuda.synchronize()
     t_c = time.perf_counter()
+    simplified = {}
+    if args.simplify_cell is not None or args.target_faces is not None:
+        verts, faces = mesh.simplify_mesh(verts, faces, cell=args.simplify_cell, target_faces=args.target_faces,
+                                          origin=lo, placement=args.placement, stats=simplified)
+    torch.cuda.synchronize()
+    t_s = time.perf_counter()
     nrm = mesh.vertex_normals(model, verts, args.chunk) if args.normals or args.colors else None
     torch.cuda.synchronize()
     t_n = time.perf_counter()
@@ -97,12 +116,14 @@ def main(argv=None):
     t3 = time.perf_counter()
     mesh.write_ply(args.out, v, f, nrm, rgb)
     t4 = time.perf_counter()
-    times = {"density_ms": 1e3 * (t1 - t0), "mc_ms": 1e3 * (t2 - t1), "normals_ms": 1e3 * (t_n - t_c),
+    times = {"density_ms": 1e3 * (t1 - t0), "mc_ms": 1e3 * (t2 - t1), "normals_ms": 1e3 * (t_n - t_s),
              "d2h_ms": 1e3 * (t3 - t_k), "ply_ms": 1e3 * (t4 - t3), "clean_ms": 1e3 * (t_c - t2),
-             "colors_ms": 1e3 * (t_k - t_n)}
+             "colors_ms": 1e3 * (t_k - t_n), "simplify_ms": 1e3 * (t_s - t_c)}
     print(json.dumps({"V": int(v.shape[0]), "F": int(f.shape[0]), "lattice": list(vol.shape),
                       **{k: round(x, 3) for k, x in times.items()},
-                      **{k: stats[k] for k in ("components", "V_removed", "F_removed")}}))
+                      **{k: stats[k] for k in ("components", "V_removed", "F_removed")},
+                      **{k: round(x, 3) if isinstance(x, float) and k.endswith("_ms") else x
+                         for k, x in simplified.items()}}))
 
 
 if __name__ == "__main__":
