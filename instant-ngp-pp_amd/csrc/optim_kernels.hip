@@ -5,6 +5,21 @@
 
 namespace {
 
+// One element's Adam update.  The three multiply-adds are fused by name and nothing else may be: left to the compiler, the
+// quad loops and the tail of adam_kernel fused v * beta2 + (1 - beta2) g g each its own way, and the last bit of exp_avg_sq
+// depended on which loop an element fell into, that is on n and on the launch width.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float gs, float step_size, float beta1,
+                                            float beta2, float eps, float bc2_sqrt, float weight_decay)
+{
+#pragma clang fp contract(off)
+    float gr = g * gs;
+    if (weight_decay != 0.0f) gr = fmaf(weight_decay, p, gr);
+    m = fmaf(gr - m, 1.0f - beta1, m);
+    v = fmaf(v, beta2, (1.0f - beta2) * gr * gr);
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = fmaf(-step_size, m / denom, p);
+}
+
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, float step_size, float beta1, float beta2,
                                                    float eps, float bc2_sqrt, float weight_decay,
@@ -19,14 +34,8 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float*
     auto update = [&](float4& pp, const float4& gg, float4& mm, float4& vv) {
         float* pa = &pp.x; const float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float gr = ga[j] * gs;
-            if (weight_decay != 0.0f) gr += weight_decay * pa[j];
-            ma[j] = ma[j] + (gr - ma[j]) * (1.0f - beta1);
-            va[j] = va[j] * beta2 + (1.0f - beta2) * gr * gr;
-            const float denom = sqrtf(va[j]) / bc2_sqrt + eps;
-            pa[j] = pa[j] - step_size * (ma[j] / denom);
-        }
+        for (int j = 0; j < 4; j++)
+            adam_update(pa[j], ga[j], ma[j], va[j], gs, step_size, beta1, beta2, eps, bc2_sqrt, weight_decay);
     };
     const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     auto nz = [](const float4& q) { return q.x != 0.0f || q.y != 0.0f || q.z != 0.0f || q.w != 0.0f; };
@@ -54,12 +63,9 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float*
     }
     // tail
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float gr = g[i] * gs;
-        if (weight_decay != 0.0f) gr += weight_decay * p[i];
-        const float mn = m[i] + (gr - m[i]) * (1.0f - beta1);
-        const float vn = v[i] * beta2 + (1.0f - beta2) * gr * gr;
-        m[i] = mn; v[i] = vn;
-        p[i] = p[i] - step_size * (mn / (sqrtf(vn) / bc2_sqrt + eps));
+        float pp = p[i], mm = m[i], vv = v[i];
+        adam_update(pp, g[i], mm, vv, gs, step_size, beta1, beta2, eps, bc2_sqrt, weight_decay);
+        m[i] = mm; v[i] = vv; p[i] = pp;
         if (zero_grad) g[i] = 0.0f;
     }
 }
