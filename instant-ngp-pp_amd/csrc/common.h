@@ -18,6 +18,13 @@ static inline unsigned ngp_blocks(int64_t work, int per_block)
     return (unsigned)(b < 1 ? 1 : b);
 }
 
+// workgroups of a grid-stride launch over n items: one per tile of `tile` items, at most max_blocks
+static inline int64_t ngp_capped_tiles(int64_t n, int tile, int max_blocks)
+{
+    const int64_t n_tiles = (n + tile - 1) / tile;
+    return n_tiles < max_blocks ? n_tiles : max_blocks;
+}
+
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // ---- host state that belongs to a device, not to the process ------------------------------
@@ -67,7 +74,8 @@ int launch_big_lds(dim3 grid, dim3 block, size_t lds, int max_lds, hipStream_t s
 
 // ---- cross-lane helpers over a 32-lane half-wave (one ray segment per half) ----------
 // __shfl_* with width=32 never crosses the half-wave boundary.
-__device__ __forceinline__ float half_sum(float v)
+template <typename T>   // float or double
+__device__ __forceinline__ T half_sum(T v)
 {
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
@@ -99,4 +107,83 @@ __device__ __forceinline__ int half_first(unsigned long long ballot, int lane64)
 {
     unsigned m = (unsigned)(ballot >> (lane64 & 32));
     return m ? (__ffs((int)m) - 1) : -1;
+}
+
+// ---- cross-lane helpers over the whole 64-lane wave -------------------------------------------
+// Sum of the wave on every lane (int, float or double).  The xor butterfly runs 32 -> 1: that order is part of every
+// float and double result built on it.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ int wave_incl_scan(int v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < NGP_WAVE; o <<= 1) {
+        const int u = __shfl_up(v, o, NGP_WAVE);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// ---- scans over a workgroup -------------------------------------------------------------------
+// Exclusive scan of v over a workgroup of THREADS lanes (every lane calls it); *total, if asked for, is the workgroup's
+// sum on every lane.  The wave totals pass through LDS that the function owns, behind ONE barrier: lanes may still be
+// reading it when the function returns, so a second call in the same kernel needs a __syncthreads() between the two
+// (block_carry_scan ends every tile with one).
+template <int THREADS>
+__device__ __forceinline__ int block_excl_scan(int v, int* total = nullptr)
+{
+    static_assert(THREADS % NGP_WAVE == 0, "whole waves");
+    __shared__ int wsum[THREADS / NGP_WAVE];
+    const int lane = threadIdx.x & (NGP_WAVE - 1), wave = threadIdx.x / NGP_WAVE;
+    const int inc = wave_incl_scan(v, lane);
+    if (lane == NGP_WAVE - 1) wsum[wave] = inc;
+    __syncthreads();
+    int off = inc - v;
+    for (int w = 0; w < wave; w++) off += wsum[w];
+    if (total) {
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < THREADS / NGP_WAVE; w++) tot += wsum[w];
+        *total = tot;
+    }
+    return off;
+}
+
+// ONE workgroup of THREADS lanes scans n values tile by tile: store(i, sum of load(0) .. load(i - 1)) for every i < n,
+// and the sum of all n comes back on every lane.  A tile's values and their sum are int32; the running carry is a
+// Carry, int64_t where the total may pass 2^31.
+template <int THREADS, typename Carry, typename Load, typename Store>
+__device__ __forceinline__ Carry block_carry_scan(int n, Load load, Store store)
+{
+    Carry carry = 0;
+    for (int base = 0; base < n; base += THREADS) {
+        const int i = base + threadIdx.x;
+        int tot;
+        const int off = block_excl_scan<THREADS>(i < n ? load(i) : 0, &tot);
+        if (i < n) store(i, carry + off);
+        carry += tot;
+        __syncthreads();   // the next tile reuses block_excl_scan's LDS
+    }
+    return carry;
+}
+
+// Sum of element e of n_blocks rows of `stride` doubles (the per-workgroup partial sums of a backward), in row order:
+// two accumulators over the even and the odd rows, rounded ONCE, where the sum meets its float32 sink.  No atomics: the
+// same bits on every run.
+__device__ __forceinline__ float ordered_partial_sum(const double* __restrict__ partials, int n_blocks, int stride, int e)
+{
+    double s0 = 0.0, s1 = 0.0;
+    int b = 0;
+    for (; b + 1 < n_blocks; b += 2) {
+        s0 += partials[(size_t)b * stride + e];
+        s1 += partials[(size_t)(b + 1) * stride + e];
+    }
+    if (b < n_blocks) s0 += partials[(size_t)b * stride + e];
+    return (float)(s0 + s1);
 }

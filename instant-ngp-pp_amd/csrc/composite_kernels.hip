@@ -473,7 +473,7 @@ __global__ void __launch_bounds__(256) nerf_loss_kernel(const float* __restrict_
         d_opacity[r] = g_op * (-lg - 1.0f);
         if (dist) s2 = dist[r];
     }
-#pragma unroll
+#pragma unroll   // wave_sum of the three, interleaved: the text the kernel's compiled shape was measured with
     for (int o = 32; o > 0; o >>= 1) {
         s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64);
     }
@@ -564,8 +564,7 @@ __global__ void __launch_bounds__(1024) count_valid_labels_kernel(const int64_t*
         const int64_t y = labels[rays_a[3 * (size_t)row]];
         c += (y >= 0 && y < classes) ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {

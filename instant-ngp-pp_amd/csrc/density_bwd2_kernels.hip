@@ -26,13 +26,6 @@ constexpr int DH_ROWS = NGP_DENSITY_BWD2_ROWS;     // rows per tile: one per hal
 constexpr int DH_THREADS = 32 * DH_ROWS;
 constexpr int DH_SUMS = DH_H + 1;                  // dW2 (128) | db2
 
-__device__ __forceinline__ double half_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-    return v;
-}
-
 // e1 may be r itself: a lane reads its four values of r before it writes its four of e1, and no other lane touches them
 __global__ void __launch_bounds__(DH_THREADS) density_head_bwd2_kernel(const float* __restrict__ a1, const float* __restrict__ sig,
                                                                        const float* r, const float* __restrict__ W2,
@@ -65,7 +58,7 @@ __global__ void __launch_bounds__(DH_THREADS) density_head_bwd2_kernel(const flo
             ws1[k] = (double)w[k] * s1[k];
             qp = fma((double)rr[k], ws1[k], qp);
         }
-        const double q = half_sum_f64(qp);
+        const double q = half_sum(qp);
         const double s2 = (double)-expm1f(-sg), o2 = (double)expf(-sg);
         const double e2 = q * (s2 * o2) + (double)gs * s2;
         if (live) {
@@ -100,22 +93,9 @@ __global__ void __launch_bounds__(DH_THREADS) density_head_bwd2_sum_kernel(const
 {
     const int e = threadIdx.x;
     if (e >= DH_SUMS) return;
-    double s0 = 0.0, s1 = 0.0;
-    int b = 0;
-    for (; b + 1 < n_blocks; b += 2) {
-        s0 += partials[(size_t)b * DH_SUMS + e];
-        s1 += partials[(size_t)(b + 1) * DH_SUMS + e];
-    }
-    if (b < n_blocks) s0 += partials[(size_t)b * DH_SUMS + e];
-    const float s = (float)(s0 + s1);
+    const float s = ordered_partial_sum(partials, n_blocks, DH_SUMS, e);
     if (e < DH_H) dW2[e] += s;
     else db2[0] += s;
-}
-
-inline int64_t dh_blocks(int64_t n)
-{
-    const int64_t n_tiles = (n + DH_ROWS - 1) / DH_ROWS;
-    return n_tiles < NGP_DENSITY_BWD2_MAX_BLOCKS ? n_tiles : NGP_DENSITY_BWD2_MAX_BLOCKS;
 }
 
 } // namespace
@@ -125,7 +105,7 @@ extern "C" {
 int64_t ngp_density_head_bwd2_workspace(int64_t n)
 {
     if (n < 0) return NGP_EINVAL;
-    return dh_blocks(n) * DH_SUMS * 2;   // doubles, counted in floats
+    return ngp_capped_tiles(n, DH_ROWS, NGP_DENSITY_BWD2_MAX_BLOCKS) * DH_SUMS * 2;   // doubles, counted in floats
 }
 
 int ngp_density_head_bwd2(const float* a1, const float* sig, const float* r, const float* W2, const float* d_sig, int64_t n,
@@ -138,7 +118,7 @@ int ngp_density_head_bwd2(const float* a1, const float* sig, const float* r, con
         (((uintptr_t)sig | (uintptr_t)W2 | (uintptr_t)d_sig | (uintptr_t)dW2 | (uintptr_t)db2) & 3))
         return NGP_EINVAL;
     const int64_t n_tiles = (n + DH_ROWS - 1) / DH_ROWS;
-    const int blocks = (int)dh_blocks(n);
+    const int blocks = (int)ngp_capped_tiles(n, DH_ROWS, NGP_DENSITY_BWD2_MAX_BLOCKS);
     hipLaunchKernelGGL(density_head_bwd2_kernel, dim3((unsigned)blocks), dim3(DH_THREADS), 0, (hipStream_t)stream, a1, sig, r, W2,
                        d_sig, n, n_tiles, m, e1, reinterpret_cast<double*>(workspace));
     if (ngp_check_launch() != NGP_OK) return NGP_ELAUNCH;

@@ -126,8 +126,7 @@ int ngp_embed_a_fwd(const float* weight, int64_t n_imgs, int E, const int64_t* i
     if (n_rays == 0) return NGP_OK;
     if (!weight || !img_idxs || !rays_a || !out || n_imgs <= 0 || E < 1 || E > EB_MAX_E || n_cols < E || n_cols > 64 ||
         ld < n_cols) return NGP_EINVAL;
-    const int64_t blocks = (n_rays + EB_WAVES - 1) / EB_WAVES;
-    const dim3 grid((unsigned)(blocks < EB_MAX_BLOCKS ? blocks : EB_MAX_BLOCKS));
+    const dim3 grid((unsigned)ngp_capped_tiles(n_rays, EB_WAVES, EB_MAX_BLOCKS));
     const bool vec = ((uintptr_t)out % 16 == 0) && ld % 4 == 0 && n_cols % 4 == 0 && 64 % (n_cols / 4) == 0;
     if (vec)
         hipLaunchKernelGGL(embed_a_fwd_kernel<true>, grid, dim3(64 * EB_WAVES), 0, (hipStream_t)stream, weight, n_imgs, E,

@@ -232,7 +232,7 @@ int ngp_mask_field_bwd(const ngp_grid_desc* desc, const float* table, const floa
     if (!mask_meta(desc, m) || !table || !W1 || !b1 || !W2 || !uvi || !mask || !dL_dmask || !dtable || !dW1 || !db1 ||
         !dW2 || !db2) return NGP_EINVAL;
     const int64_t n_tiles = (n + MK_ROWS - 1) / MK_ROWS;
-    const unsigned blocks = (unsigned)(n_tiles < MK_MAX_BLOCKS ? n_tiles : MK_MAX_BLOCKS);
+    const unsigned blocks = (unsigned)ngp_capped_tiles(n, MK_ROWS, MK_MAX_BLOCKS);
     hipLaunchKernelGGL(mask_field_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, m, table, W1, b1, W2, uvi,
                        mask, dL_dmask, n, n_tiles, dtable, dW1, db1, dW2, db2);
     return ngp_check_launch();

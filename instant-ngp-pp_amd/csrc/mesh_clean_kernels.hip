@@ -98,29 +98,6 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_face_count_kernel(const int32_t* 
     }
 }
 
-// exclusive scan over the workgroup (CC_BLOCK threads); *total = the workgroup's sum
-__device__ __forceinline__ int cc_block_scan(int v, int* total)
-{
-    __shared__ int wsum[CC_BLOCK / NGP_WAVE];
-    const int lane = threadIdx.x & (NGP_WAVE - 1), wave = threadIdx.x / NGP_WAVE;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < NGP_WAVE; o <<= 1) {
-        const int u = __shfl_up(inc, o, NGP_WAVE);
-        if (lane >= o) inc += u;
-    }
-    if (lane == NGP_WAVE - 1) wsum[wave] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < CC_BLOCK / NGP_WAVE; w++) {
-        off += w < wave ? wsum[w] : 0;
-        tot += wsum[w];
-    }
-    *total = tot;
-    return off + inc - v;
-}
-
 struct CcLayout {   // workspace of the compaction: int32 words
     int32_t* word_v;      // (n_verts)  local offset << 1 | kept
     int32_t* word_f;      // (n_faces)
@@ -159,7 +136,7 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_flag_kernel(const int32_t* __rest
         flag = keep[labels[faces[3 * (int64_t)i]]] != 0;
     }
     int tot;
-    const int off = cc_block_scan(flag, &tot);
+    const int off = block_excl_scan<CC_BLOCK>(flag, &tot);
     if (is_v && i < n_verts) L.word_v[i] = off << 1 | flag;
     if (!is_v && i < n_faces) L.word_f[i] = off << 1 | flag;
     if (threadIdx.x == 0) L.sums[blockIdx.x] = tot;
@@ -168,35 +145,13 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_flag_kernel(const int32_t* __rest
 // exclusive scans of the vertex and face workgroup sums; totals[0] = kept vertices, totals[1] = kept faces
 __global__ void __launch_bounds__(CC_SCAN_THREADS) cc_scan_blocks_kernel(CcLayout L, int32_t* __restrict__ totals)
 {
-    __shared__ int ws[CC_SCAN_THREADS / NGP_WAVE];
-    const int lane = threadIdx.x & (NGP_WAVE - 1), wave = threadIdx.x / NGP_WAVE;
     for (int part = 0; part < 2; part++) {
-        const int nb = part ? L.nb_f : L.nb_v;
         const int32_t* sums = L.sums + (part ? L.nb_v : 0);
         int32_t* offs = L.offs + (part ? L.nb_v : 0);
-        int carry = 0;   // at most n_verts or n_faces < 2^31
-        for (int base = 0; base < nb; base += CC_SCAN_THREADS) {
-            const int b = base + threadIdx.x;
-            const int s = b < nb ? sums[b] : 0;
-            int inc = s;
-#pragma unroll
-            for (int o = 1; o < NGP_WAVE; o <<= 1) {
-                const int u = __shfl_up(inc, o, NGP_WAVE);
-                if (lane >= o) inc += u;
-            }
-            if (lane == NGP_WAVE - 1) ws[wave] = inc;
-            __syncthreads();
-            int off = 0, tot = 0;
-#pragma unroll
-            for (int w = 0; w < CC_SCAN_THREADS / NGP_WAVE; w++) {
-                off += w < wave ? ws[w] : 0;
-                tot += ws[w];
-            }
-            __syncthreads();
-            if (b < nb) offs[b] = carry + off + inc - s;
-            carry += tot;
-        }
-        if (threadIdx.x == 0) totals[part] = carry;
+        // the carry is at most n_verts or n_faces < 2^31
+        const int tot = block_carry_scan<CC_SCAN_THREADS, int>(
+            part ? L.nb_f : L.nb_v, [&](int b) { return sums[b]; }, [&](int b, int excl) { offs[b] = excl; });
+        if (threadIdx.x == 0) totals[part] = tot;
     }
 }
 

@@ -141,31 +141,6 @@ static_assert(kMcTables.ntri[0x69] == 4 && kMcTables.ntri[0x96] == 4, "checkerbo
 
 __constant__ McTables c_mc = kMcTables;
 
-// exclusive scan over the workgroup (MC_BLOCK threads); *total = the workgroup's sum.  Ends with a barrier, so the
-// next call may reuse the LDS.
-__device__ __forceinline__ int mc_block_scan(int v, int* total)
-{
-    __shared__ int wsum[MC_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < MC_BLOCK / 64; w++) {
-        off += w < wave ? wsum[w] : 0;
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return off + inc - v;
-}
-
 struct McLattice {
     int nx, ny, nz, n;   // n = nx*ny*nz < 2^31
     float level;
@@ -205,7 +180,7 @@ __global__ void __launch_bounds__(MC_BLOCK) mc_count_kernel(const float* __restr
     const int nv = __popc(mask), nt = cs >= 0 ? c_mc.ntri[cs] : 0;
     // vertex counts in the low 16 bits, triangle counts in the high ones (per workgroup at most 768 and 1280)
     int tot;
-    const int off = mc_block_scan(nv | nt << 16, &tot);
+    const int off = block_excl_scan<MC_BLOCK>(nv | nt << 16, &tot);
     if (p < L.n) word[p] = (off & 0xffff) << 3 | mask;
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
@@ -218,44 +193,12 @@ __global__ void __launch_bounds__(MC_SCAN_THREADS) mc_scan_blocks_kernel(const i
                                                                          int32_t* __restrict__ status,
                                                                          int32_t* __restrict__ totals)
 {
-    __shared__ int wv[MC_SCAN_THREADS / 64], wt[MC_SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t carry_v = 0, carry_t = 0;
-    for (int base = 0; base < nb; base += MC_SCAN_THREADS) {
-        const int b = base + threadIdx.x;
-        const int s = b < nb ? block_sums[b] : 0;
-        const int v = s & 0xffff, t = s >> 16;
-        int iv = v, it = t;    // a tile sums to at most 1024 * 1280: int32
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int uv = __shfl_up(iv, o, 64), ut = __shfl_up(it, o, 64);
-            if (lane >= o) {
-                iv += uv;
-                it += ut;
-            }
-        }
-        if (lane == 63) {
-            wv[wave] = iv;
-            wt[wave] = it;
-        }
-        __syncthreads();
-        int ov = 0, ot = 0, sv = 0, st = 0;
-#pragma unroll
-        for (int w = 0; w < MC_SCAN_THREADS / 64; w++) {
-            ov += w < wave ? wv[w] : 0;
-            ot += w < wave ? wt[w] : 0;
-            sv += wv[w];
-            st += wt[w];
-        }
-        __syncthreads();
-        if (b < nb) {
-            const int64_t ev = carry_v + ov + iv - v, et = carry_t + ot + it - t;
-            off_v[b] = (int32_t)(ev < INT32_MAX ? ev : INT32_MAX);
-            off_t[b] = (int32_t)(et < INT32_MAX ? et : INT32_MAX);
-        }
-        carry_v += sv;
-        carry_t += st;
-    }
+    // the two halves of the packed sums, one after the other (a tile sums to at most 1024 * 1280: int32)
+    const auto clamped = [](int64_t e) { return (int32_t)(e < INT32_MAX ? e : INT32_MAX); };
+    const int64_t carry_v = block_carry_scan<MC_SCAN_THREADS, int64_t>(
+        nb, [&](int b) { return block_sums[b] & 0xffff; }, [&](int b, int64_t excl) { off_v[b] = clamped(excl); });
+    const int64_t carry_t = block_carry_scan<MC_SCAN_THREADS, int64_t>(
+        nb, [&](int b) { return block_sums[b] >> 16; }, [&](int b, int64_t excl) { off_t[b] = clamped(excl); });
     if (threadIdx.x == 0) {
         const bool over = carry_v > INT32_MAX || carry_t > INT32_MAX;
         status[0] = over ? 1 : 0;
@@ -287,8 +230,7 @@ __global__ void __launch_bounds__(MC_BLOCK) mc_emit_kernel(const float* __restri
     int mask = 0, cs = -1;
     if (p < L.n) mc_classify(vol, L, p, mask, cs);
     const int nt = cs >= 0 ? c_mc.ntri[cs] : 0;
-    int tot;
-    const int toff = mc_block_scan(nt, &tot) + off_t[blockIdx.x];
+    const int toff = block_excl_scan<MC_BLOCK>(nt) + off_t[blockIdx.x];
     if (p >= L.n) return;
 
     const int k = p % L.nz, r = p / L.nz, j = r % L.ny, i = r / L.ny;

@@ -180,29 +180,6 @@ __global__ void __launch_bounds__(SM_BLOCK) sm_insert_verts_kernel(const float* 
     sm_raise(totals, err);
 }
 
-// exclusive scan over the workgroup (SM_BLOCK threads); *total = the workgroup's sum
-__device__ __forceinline__ int sm_block_scan(int v, int* total)
-{
-    __shared__ int wsum[SM_BLOCK / NGP_WAVE];
-    const int lane = threadIdx.x & (NGP_WAVE - 1), wave = threadIdx.x / NGP_WAVE;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < NGP_WAVE; o <<= 1) {
-        const int u = __shfl_up(inc, o, NGP_WAVE);
-        if (lane >= o) inc += u;
-    }
-    if (lane == NGP_WAVE - 1) wsum[wave] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SM_BLOCK / NGP_WAVE; w++) {
-        off += w < wave ? wsum[w] : 0;
-        tot += wsum[w];
-    }
-    *total = tot;
-    return off + inc - v;
-}
-
 // the smallest member of v's cluster (v itself where it has no slot: the call is an error then, and stays in bounds)
 __device__ __forceinline__ int sm_smallest(const SmLayout& L, int v)
 {
@@ -215,7 +192,7 @@ __global__ void __launch_bounds__(SM_BLOCK) sm_flag_verts_kernel(int n_verts, Sm
     const int v = blockIdx.x * SM_BLOCK + threadIdx.x;
     const int flag = v < n_verts && sm_smallest(L, v) == v;
     int tot;
-    const int off = sm_block_scan(flag, &tot);
+    const int off = block_excl_scan<SM_BLOCK>(flag, &tot);
     if (v < n_verts) L.word_v[v] = off << 1 | flag;
     if (threadIdx.x == 0) L.sums_v[blockIdx.x] = tot;
 }
@@ -225,31 +202,10 @@ __global__ void __launch_bounds__(SM_SCAN_THREADS) sm_scan_blocks_kernel(const i
                                                                          int32_t* __restrict__ offs, int nb,
                                                                          int32_t* __restrict__ total)
 {
-    __shared__ int ws[SM_SCAN_THREADS / NGP_WAVE];
-    const int lane = threadIdx.x & (NGP_WAVE - 1), wave = threadIdx.x / NGP_WAVE;
-    int carry = 0;   // at most n_verts or n_faces
-    for (int base = 0; base < nb; base += SM_SCAN_THREADS) {
-        const int b = base + threadIdx.x;
-        const int s = b < nb ? sums[b] : 0;
-        int inc = s;
-#pragma unroll
-        for (int o = 1; o < NGP_WAVE; o <<= 1) {
-            const int u = __shfl_up(inc, o, NGP_WAVE);
-            if (lane >= o) inc += u;
-        }
-        if (lane == NGP_WAVE - 1) ws[wave] = inc;
-        __syncthreads();
-        int off = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < SM_SCAN_THREADS / NGP_WAVE; w++) {
-            off += w < wave ? ws[w] : 0;
-            tot += ws[w];
-        }
-        __syncthreads();
-        if (b < nb) offs[b] = carry + off + inc - s;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
+    // the carry is at most n_verts or n_faces
+    const int tot = block_carry_scan<SM_SCAN_THREADS, int>(
+        nb, [&](int b) { return sums[b]; }, [&](int b, int excl) { offs[b] = excl; });
+    if (threadIdx.x == 0) *total = tot;
 }
 
 __global__ void __launch_bounds__(SM_BLOCK) sm_number_kernel(int n_verts, SmLayout L)
@@ -324,7 +280,7 @@ __global__ void __launch_bounds__(SM_BLOCK) sm_flag_faces_kernel(int n_faces, Sm
         flag = s >= 0 && (int)L.fmin[s] == f;
     }
     int tot;
-    const int off = sm_block_scan(flag, &tot);
+    const int off = block_excl_scan<SM_BLOCK>(flag, &tot);
     if (f < n_faces) L.word_f[f] = off << 1 | flag;
     if (threadIdx.x == 0) L.sums_f[blockIdx.x] = tot;
 }

@@ -1212,8 +1212,7 @@ __global__ void __launch_bounds__(256) act_bwd_rows_kernel(const float* __restri
         }
         acc += sqrtf(q);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(norm_acc, part[0] + part[1] + part[2] + part[3]);

@@ -94,8 +94,7 @@ __global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ x,
     }
     for (int64_t j = (n4 << 2) + tid; j < n; j += stride) a = fmaf(x[j], x[j], a);
     a += b;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
@@ -110,8 +109,7 @@ __global__ void __launch_bounds__(256) sumsq_scalar_kernel(const float* __restri
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     float a = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) a = fmaf(x[i], x[i], a);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
@@ -141,8 +139,7 @@ __global__ void __launch_bounds__(256) row_norm_sum_kernel(const float* __restri
         for (int c = 0; c < cols; c++) { const float v = x[i * ldx + c]; q = fmaf(v, v, q); }
         a += sqrtf(q);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
@@ -178,7 +175,7 @@ __global__ void __launch_bounds__(1024) clip_decide_kernel(const float* __restri
         }
         q = (q0 + q1) + (q2 + q3);
         for (int64_t i = 4 * n4 + threadIdx.x; i < cnt[k]; i += 1024) q = fmaf(ptr[k][i], ptr[k][i], q);
-#pragma unroll
+#pragma unroll   // wave_sum(q): the text the kernel's compiled shape was measured with
         for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
         if ((threadIdx.x & 63) == 0) ws[k][threadIdx.x >> 6] = q;
     }

@@ -168,9 +168,7 @@ __global__ void __launch_bounds__(64 * PB_WAVES) pose_rays_bwd_kernel(
             a[3] += e0; a[4] += e1; a[5] += e2;
         }
 #pragma unroll
-        for (int k = 0; k < 6; k++)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+        for (int k = 0; k < 6; k++) a[k] = wave_sum(a[k]);
         if (img != run_img) {
             if (run_img >= 0) pose_flush(dR, run_img, M, gT, lane, g_dR, g_dT);
             run_img = img;

@@ -186,9 +186,7 @@ __global__ void __launch_bounds__(256) occ_count_kernel(const float* __restrict_
 {
     __shared__ int part[4];
     const int base = blockIdx.x * OCC_BLOCK + threadIdx.x * 4;
-    int c = __popc(occ_mask4(grid, g3, base, thr));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    const int c = wave_sum(__popc(occ_mask4(grid, g3, base, thr)));
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) block_counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
@@ -200,19 +198,14 @@ __global__ void __launch_bounds__(1024) scan_counts_kernel(const int32_t* __rest
                                                            int32_t* __restrict__ offsets, int32_t* __restrict__ total,
                                                            int32_t* __restrict__ clear, int clear_n)
 {
-    __shared__ int wsum[16];
     const int per = (n + 1023) / 1024;
     const int lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
     int s = 0;
     for (int i = lo; i < hi; i++) s += counts[i];
-    // exclusive scan of the 1024 thread sums: inside each wave by shuffles, across the 16 waves through LDS
+    // block_excl_scan<1024> of the thread sums, spelled out: the text the kernel's compiled shape was measured with
+    __shared__ int wsum[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
+    const int inc = wave_incl_scan(s, lane);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     int woff = 0;
@@ -227,17 +220,13 @@ __global__ void __launch_bounds__(256) occ_compact_kernel(const float* __restric
                                                           const int32_t* __restrict__ block_offsets,
                                                           int32_t* __restrict__ occ_list)
 {
+    // block_excl_scan<256> of the lanes' counts, spelled out: the text the kernel's compiled shape was measured with
     __shared__ int wsum[4];
     const int base = blockIdx.x * OCC_BLOCK + threadIdx.x * 4;
     const int m = occ_mask4(grid, g3, base, thr);
     const int c = __popc(m);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
+    const int inc = wave_incl_scan(c, lane);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     int pos = block_offsets[blockIdx.x] + inc - c;
@@ -320,29 +309,18 @@ __global__ void __launch_bounds__(1024) bucket_sort_points_kernel(const int32_t*
                                                                   int32_t* __restrict__ out_idx, float* __restrict__ out_xyz)
 {
     __shared__ int bins[SAMPLE_SUB];
-    __shared__ int wsum[16];
     const int b = blockIdx.x;
     const int lo = bucket_offsets[b], hi = b + 1 < SAMPLE_TOP ? bucket_offsets[b + 1] : n;
     for (int i = threadIdx.x; i < SAMPLE_SUB; i += 1024) bins[i] = 0;
     __syncthreads();
     for (int i = lo + threadIdx.x; i < hi; i += 1024) atomicAdd(&bins[((uint32_t)keys_b[i] >> sub_shift) & (SAMPLE_SUB - 1)], 1);
     __syncthreads();
-    // exclusive scan of the bins: 8 per thread, wave scan, 16 wave totals
+    // exclusive scan of the bins: 8 per thread, then the 1024 thread sums
     constexpr int PER = SAMPLE_SUB / 1024;
     int loc[PER], sum = 0;
 #pragma unroll
     for (int k = 0; k < PER; k++) { loc[k] = bins[threadIdx.x * PER + k]; sum += loc[k]; }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int run = lo + inc - sum;
-    for (int w = 0; w < wave; w++) run += wsum[w];
+    int run = lo + block_excl_scan<1024>(sum);
 #pragma unroll
     for (int k = 0; k < PER; k++) { bins[threadIdx.x * PER + k] = run; run += loc[k]; }
     __syncthreads();
@@ -386,7 +364,7 @@ __global__ void __launch_bounds__(256) grid_ema_stats_kernel(float* __restrict__
         if (!(g < 0)) { g = fmaxf(g * decay, tmp[i]); grid[i] = g; }
         if (g > 0) { sum += g; cnt += 1.0f; }
     }
-#pragma unroll
+#pragma unroll   // wave_sum of both, interleaved: the text the kernel's compiled shape was measured with
     for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
     if ((threadIdx.x & 63) == 0) { ps[threadIdx.x >> 6] = sum; pc[threadIdx.x >> 6] = cnt; }
     __syncthreads();
@@ -403,7 +381,7 @@ __global__ void __launch_bounds__(256) grid_threshold_kernel(const float* __rest
     __shared__ double ps[4], pc[4];
     double sum = 0.0, cnt = 0.0;
     for (int i = threadIdx.x; i < n_blocks; i += 256) { sum += partials[2 * i]; cnt += partials[2 * i + 1]; }
-#pragma unroll
+#pragma unroll   // wave_sum of both, interleaved: the text the kernel's compiled shape was measured with
     for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
     if ((threadIdx.x & 63) == 0) { ps[threadIdx.x >> 6] = sum; pc[threadIdx.x >> 6] = cnt; }
     __syncthreads();
@@ -599,6 +577,7 @@ __global__ void __launch_bounds__(256) march_wave_kernel(const float* __restrict
 __global__ void __launch_bounds__(1024) march_scan_kernel(const int32_t* __restrict__ counts, int n_rays,
                                                           int64_t* __restrict__ rays_a, int32_t* __restrict__ counter)
 {
+    // block_carry_scan<1024, int64_t> with the carry in LDS, spelled out: the text the kernel's compiled shape was measured with
     __shared__ int32_t wave_tot[16];
     __shared__ int64_t carry_s;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -607,12 +586,7 @@ __global__ void __launch_bounds__(1024) march_scan_kernel(const int32_t* __restr
     for (int base = 0; base < n_rays; base += 1024) {
         const int r = base + tid;
         const int32_t c = r < n_rays ? counts[r] : 0;
-        int32_t v = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
+        const int32_t v = wave_incl_scan(c, lane);
         if (lane == 63) wave_tot[wid] = v;
         __syncthreads();
         int32_t woff = 0;

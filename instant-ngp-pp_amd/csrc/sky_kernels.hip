@@ -203,14 +203,7 @@ __global__ void __launch_bounds__(SKY_H) skybox_bwd_sum_kernel(const double* __r
                                                                float* __restrict__ dprm)
 {
     const int e = blockIdx.x * SKY_H + threadIdx.x;   // 0 .. 415
-    double s0 = 0.0, s1 = 0.0;
-    int b = 0;
-    for (; b + 1 < n_blocks; b += 2) {
-        s0 += partials[(size_t)b * SKY_SUMS + e];
-        s1 += partials[(size_t)(b + 1) * SKY_SUMS + e];
-    }
-    if (b < n_blocks) s0 += partials[(size_t)b * SKY_SUMS + e];
-    const float s = (float)(s0 + s1);   // rounded once, where it meets the float32 sink
+    const float s = ordered_partial_sum(partials, n_blocks, SKY_SUMS, e);
     if (e < 3 * SKY_H) {
         dprm[SKY_W2_AT + e] += s;
     } else if (e < 3 * SKY_H + SKY_H * SKY_Y) {
@@ -223,12 +216,6 @@ __global__ void __launch_bounds__(SKY_H) skybox_bwd_sum_kernel(const double* __r
     }
 }
 
-inline int64_t bwd_blocks(int64_t n)
-{
-    const int64_t n_tiles = (n + SKY_TILE - 1) / SKY_TILE;
-    return n_tiles < NGP_SKYBOX_BWD_MAX_BLOCKS ? n_tiles : NGP_SKYBOX_BWD_MAX_BLOCKS;
-}
-
 } // namespace
 
 extern "C" {
@@ -239,7 +226,7 @@ int ngp_skybox_fwd(const float* params, const float* rays_d, int64_t n_rays, flo
     if (n_rays == 0) return NGP_OK;
     if (!params || !rays_d || !rgb_bg) return NGP_EINVAL;
     const int64_t n_tiles = (n_rays + SKY_TILE - 1) / SKY_TILE;
-    const unsigned blocks = (unsigned)(n_tiles < SKY_FWD_MAX_BLOCKS ? n_tiles : SKY_FWD_MAX_BLOCKS);
+    const unsigned blocks = (unsigned)ngp_capped_tiles(n_rays, SKY_TILE, SKY_FWD_MAX_BLOCKS);
     hipLaunchKernelGGL(skybox_fwd_kernel, dim3(blocks), dim3(SKY_TILE), 0, (hipStream_t)stream, params, rays_d, n_rays, n_tiles,
                        rgb_bg);
     return ngp_check_launch();
@@ -248,7 +235,7 @@ int ngp_skybox_fwd(const float* params, const float* rays_d, int64_t n_rays, flo
 int64_t ngp_skybox_bwd_workspace(int64_t n)
 {
     if (n < 0) return NGP_EINVAL;
-    return bwd_blocks(n) * SKY_SUMS * 2;   // doubles, counted in floats
+    return ngp_capped_tiles(n, SKY_TILE, NGP_SKYBOX_BWD_MAX_BLOCKS) * SKY_SUMS * 2;   // doubles, counted in floats
 }
 
 int ngp_skybox_bwd(const float* params, const float* rays_d, const float* dL_drgb_bg, int64_t n_rays, float* dparams,
@@ -258,7 +245,7 @@ int ngp_skybox_bwd(const float* params, const float* rays_d, const float* dL_drg
     if (n_rays == 0) return NGP_OK;
     if (!params || !rays_d || !dL_drgb_bg || !dparams || !workspace || ((uintptr_t)workspace & 7)) return NGP_EINVAL;
     const int64_t n_tiles = (n_rays + SKY_TILE - 1) / SKY_TILE;
-    const int blocks = (int)bwd_blocks(n_rays);
+    const int blocks = (int)ngp_capped_tiles(n_rays, SKY_TILE, NGP_SKYBOX_BWD_MAX_BLOCKS);
     hipLaunchKernelGGL(skybox_bwd_kernel, dim3((unsigned)blocks), dim3(SKY_TILE), 0, (hipStream_t)stream, params, rays_d,
                        dL_drgb_bg, n_rays, n_tiles, reinterpret_cast<double*>(workspace));
     if (ngp_check_launch() != NGP_OK) return NGP_ELAUNCH;

@@ -180,14 +180,7 @@ __global__ void __launch_bounds__(TM_H) tonemap_bwd_sum_kernel(const double* __r
 {
     const int e = blockIdx.x * TM_H + threadIdx.x;   // 0 .. 575
     const int q = e / TM_UNITS, c = (e % TM_UNITS) / TM_H, j = e % TM_H;
-    double s0 = 0.0, s1 = 0.0;
-    int b = 0;
-    for (; b + 1 < n_blocks; b += 2) {
-        s0 += partials[(size_t)b * (3 * TM_UNITS) + e];
-        s1 += partials[(size_t)(b + 1) * (3 * TM_UNITS) + e];
-    }
-    if (b < n_blocks) s0 += partials[(size_t)b * (3 * TM_UNITS) + e];
-    const float s = (float)(s0 + s1);   // rounded once, where it meets the float32 sink
+    const float s = ordered_partial_sum(partials, n_blocks, 3 * TM_UNITS, e);
     float* d = dprm.p[c];
     if (q == 0) {
         d[TM_W2_AT + j] += s;
@@ -204,12 +197,6 @@ inline bool aligned16(const void* a, const void* b, const void* c)
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
-inline int64_t bwd_blocks(int64_t n)
-{
-    const int64_t n_tiles = (n + TM_TILE - 1) / TM_TILE;
-    return n_tiles < NGP_TONEMAP_BWD_MAX_BLOCKS ? n_tiles : NGP_TONEMAP_BWD_MAX_BLOCKS;
-}
-
 } // namespace
 
 extern "C" {
@@ -221,7 +208,7 @@ int ngp_tonemap_fwd(const float* params0, const float* params1, const float* par
     if (n == 0) return NGP_OK;
     if (!params0 || !params1 || !params2 || !log_radiance || !rgb || !aligned16(params0, params1, params2)) return NGP_EINVAL;
     const int64_t n_tiles = (n + TM_TILE - 1) / TM_TILE;
-    const unsigned blocks = (unsigned)(n_tiles < TM_FWD_MAX_BLOCKS ? n_tiles : TM_FWD_MAX_BLOCKS);
+    const unsigned blocks = (unsigned)ngp_capped_tiles(n, TM_TILE, TM_FWD_MAX_BLOCKS);
     const TmParams prm = {{params0, params1, params2}};
     hipLaunchKernelGGL(tonemap_fwd_kernel, dim3(blocks), dim3(TM_TILE), 0, (hipStream_t)stream, prm, log_radiance, exposure,
                        exposure_stride, n, n_tiles, rgb);
@@ -231,7 +218,7 @@ int ngp_tonemap_fwd(const float* params0, const float* params1, const float* par
 int64_t ngp_tonemap_bwd_workspace(int64_t n)
 {
     if (n < 0) return NGP_EINVAL;
-    return bwd_blocks(n) * (3 * TM_UNITS) * 2;   // doubles, counted in floats
+    return ngp_capped_tiles(n, TM_TILE, NGP_TONEMAP_BWD_MAX_BLOCKS) * (3 * TM_UNITS) * 2;   // doubles, counted in floats
 }
 
 int ngp_tonemap_bwd(const float* params0, const float* params1, const float* params2, const float* log_radiance,
@@ -244,7 +231,7 @@ int ngp_tonemap_bwd(const float* params0, const float* params1, const float* par
         !aligned16(params0, params1, params2) || ((uintptr_t)workspace & 7))
         return NGP_EINVAL;
     const int64_t n_tiles = (n + TM_TILE - 1) / TM_TILE;
-    const int blocks = (int)bwd_blocks(n);
+    const int blocks = (int)ngp_capped_tiles(n, TM_TILE, NGP_TONEMAP_BWD_MAX_BLOCKS);
     const TmParams prm = {{params0, params1, params2}};
     const TmSinks dprm = {{dparams0, dparams1, dparams2}};
     hipLaunchKernelGGL(tonemap_bwd_kernel, dim3((unsigned)blocks), dim3(TM_TILE), 0, (hipStream_t)stream, prm, log_radiance,

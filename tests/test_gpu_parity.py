@@ -90,6 +90,7 @@ def test_packbits_bit_exact(ngp):
 MARCH_CASES = [
     # cascades, scale, exp_step_factor, fill, n_rays, max_samples
     (1, 0.5, 0.0, 0.05, 2048, 1024),
+    (1, 0.5, 0.0, 0.05, 1025, 1024),    # one ray past a tile of the 1024-thread scan of the counts
     (1, 0.5, 0.0, 1.00, 257, 1024),     # warm-up: everything occupied, rays hit the 1024 cap region
     (5, 8.0, 1 / 256, 0.03, 1500, 1024),
     (6, 16.0, 1 / 256, 0.02, 700, 256),

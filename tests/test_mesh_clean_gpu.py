@@ -103,6 +103,36 @@ def test_random_face_lists_match_restatement(ngp, seed):
                                [(None, None), (1, None), (10, 2), (None, 3)], f"random {seed}")
 
 
+SCAN_TILE = 1024 * 256    # items whose workgroup sums fill one tile of the 1024-thread scan (256-thread workgroups)
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("n_verts,n_faces", [(SCAN_TILE + 1, 20_000), (60_000, SCAN_TILE + 1)], ids=["verts", "faces"])
+def test_second_tile_of_the_workgroup_sums(ngp, n_verts, n_faces):
+    """one vertex, or one face, more than 1024 workgroups cover: its offset is the first entry of the scan's second tile
+    and is made of the first tile's carry alone.  The last vertex is put into the component with the most faces (it
+    trades places with that component's largest vertex: no label changes) and the last face is one of that component's,
+    so both criteria keep them."""
+    criteria = [(None, None), (1, None)]
+    g = np.random.default_rng(60 + n_verts % 7)
+    faces = ref.random_faces(g, n_verts, n_faces, n_isolated=n_verts // 10, degenerate=0.15)
+    lab = ref.labels(faces, n_verts)
+    big = np.argmax(ref.face_counts(faces, lab))                   # label of the component with the most faces
+    of_big = np.nonzero(lab[faces[:, 0]] == big)[0]
+    faces[[of_big[-1], n_faces - 1]] = faces[[n_faces - 1, of_big[-1]]]
+    w, last = faces[lab[faces[:, 0]] == big].max(), n_verts - 1
+    swap = np.arange(n_verts, dtype=np.int32)
+    swap[[w, last]] = last, w
+    faces = swap[faces]
+    lab = ref.labels(faces, n_verts)
+    counts = ref.face_counts(faces, lab)
+    for k, m in criteria:
+        kept = ref.select(counts, k, m)[lab[faces[:, 0]]] != 0
+        assert (faces[kept] >= SCAN_TILE).any() if n_verts > SCAN_TILE else kept[SCAN_TILE:].any(), (k, m)
+    verts = torch.from_numpy(g.standard_normal((n_verts, 3)).astype(np.float32)).to(DEV)
+    _check_against_restatement(ngp, verts, torch.from_numpy(faces).to(DEV), criteria, f"second tile V {n_verts} F {n_faces}")
+
+
 @pytest.mark.timeout(300)
 def test_long_chain_stays_within_the_round_bound(ngp):
     """faces (i, i+1, i+2) over 10^5 vertices: one component whose label has to travel the whole chain"""

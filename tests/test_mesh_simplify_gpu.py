@@ -102,6 +102,26 @@ def test_random_soups_match_restatement(ngp, seed):
     assert want["stats"]["degenerate"] > 0 and want["stats"]["duplicate"] > 0
 
 
+SCAN_TILE = 1024 * 256    # items whose workgroup sums fill one tile of the 1024-thread scan (256-thread workgroups)
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("n_verts,n_faces", [(SCAN_TILE + 1, 20_000), (60_000, SCAN_TILE + 1)], ids=["verts", "faces"])
+def test_second_tile_of_the_workgroup_sums(ngp, n_verts, n_faces):
+    """one vertex, or one face, more than 1024 workgroups cover: its offset is the first entry of the scan's second tile
+    and is made of the first tile's carry alone.  A thousand cells along the longest side leave most vertices alone in
+    their cell: the last vertex is its cluster's representative, the last face is kept."""
+    v, f = ref.soup(7, n_verts, n_faces)
+    cell = float(np.float32((v.max(0) - v.min(0)).max() / 1000))
+    cluster, _ = ref.clusters(ref.cell_keys(v, v.min(0), cell))
+    if n_verts > SCAN_TILE:
+        assert np.nonzero(cluster == cluster[-1])[0].min() >= SCAN_TILE
+    else:
+        assert ref.face_pass(f, cluster)[1][SCAN_TILE:].any()
+    _check_against_restatement(ngp, torch.from_numpy(v).to(DEV), torch.from_numpy(f).to(DEV), cell, None,
+                               f"second tile V {n_verts} F {n_faces}")
+
+
 @pytest.mark.timeout(120)
 def test_edges_and_errors(ngp):
     simplify = ngp.mesh.simplify_mesh

@@ -5,7 +5,7 @@ Bars.  (a), (b), (c) are held to the project's own second-order bar (tests/test_
 max-normalised against the float64 reference and must lie within second_order_reference.FACTOR (8) x floor, the floor being
 the same expressions evaluated in float32 on the same case, clamped at 2^-23; every row is compared.
   (a) ngp_density_head_bwd2 against normal_ref_reference.head_closed (which test_normal_ref_host.py holds to autograd):
-      n in {1, 31, 32, 33, 257}, two full tiles plus a ragged row, a second trip of the grid-stride loop with a ragged tile,
+      n in {1, 31, 32, 33, 257}, one and two full tiles plus a ragged row, a second trip of the grid-stride loop with a ragged tile,
       and two full trips plus one row (all from NGP_DENSITY_BWD2_ROWS / _MAX_BLOCKS); d_sig NULL and present; prefilled
       sinks; a one-signed case; rows saturated at 1e-6 and at 30; e1 written over r; guard bands; bit-identical sums.
   (b) ngp_normal_ref_tail against torch float64 autograd of lambda_rp mean(Rp) + lambda_ro mean(Ro) on one batch with empty,
@@ -112,7 +112,8 @@ def _head_compare(tag, got, case, prefill=None):
 
 def _head_counts():
     rows, blocks = _launch_shape()
-    counts = [1, 31, 32, 33, 257, 2 * rows + 1, rows * blocks + rows + 1, 2 * rows * blocks + 1]
+    # (1, rows + 1 and 2 * rows + 1 rows are 1, 2 and 3 workgroups: the ordered sum's single row, its pair and its odd tail)
+    counts = [1, 31, 32, 33, 257, rows + 1, 2 * rows + 1, rows * blocks + rows + 1, 2 * rows * blocks + 1]
     assert max(counts) <= 40000
     return counts
 

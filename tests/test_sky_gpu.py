@@ -34,7 +34,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE, FWD_BLOCKS, BWD_BLOCKS = 256, 1024, 256          # rays per tile, workgroups of the two persistent grids at most
 # 2049 tiles: every workgroup of the forward's grid walks 2 or 3 tiles, of the backward's 8 or 9; the last tile has 77 rays
 MANY = 2 * FWD_BLOCKS * TILE + 77
-COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, MANY)
+# 256, 257 and 513 rays are 1, 2 and 3 workgroups of the backward: the ordered sum's single row, its pair and its odd tail
+COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, 513, MANY)
 ULP2 = 2 * 2.0 ** -23
 
 

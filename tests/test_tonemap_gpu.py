@@ -20,8 +20,9 @@ DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TILE, MAX_BLOCKS = 256, 512                 # samples per tile, NGP_TONEMAP_BWD_MAX_BLOCKS
-# 300 001 samples = 1172 tiles on 512 workgroups: every workgroup walks more than one tile, the last tile is ragged
-COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, 300001)
+# 300 001 samples = 1172 tiles on 512 workgroups: every workgroup walks more than one tile, the last tile is ragged;
+# 256, 257 and 513 samples are 1, 2 and 3 workgroups: the ordered sum's single row, its pair and its odd tail
+COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, 513, 300001)
 TIMES = (0.125, 0.5, 2.0, 8.0, 32.0)        # the exposure table of the synthetic scenes
 EPS = 2.0 ** -23
 
