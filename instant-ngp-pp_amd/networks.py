@@ -194,10 +194,15 @@ class _Mlp2Bwd:
         call("linear_bwd_weight", self.dz1, H, self.x_in, self.ld_in, n, mlp.n_in, H, self.dW1, mlp.ldw1, self.db1)
 
 
+def _density_mlp(W1, b1, W2, b2):
+    """the density head 128 -> 128 -> 1, Softplus on both layers, with nn.Linear parameters"""
+    return _Mlp2(W1, 128, b1, W2, b2, 128, 128, 1, _SOFTPLUS, _SOFTPLUS)
+
+
 def _field_mlps(model, W1, b1, W2, b2, rgb_p, nrm_p, sem_p):
     """the four MLPs of the field node -> (density head, rgb_net, normal head, semantic head)"""
     net = model.rgb_net
-    return (_Mlp2(W1, 128, b1, W2, b2, 128, 128, 1, _SOFTPLUS, _SOFTPLUS),
+    return (_density_mlp(W1, b1, W2, b2),
             _Mlp2.tcnn(rgb_p, net.padded_in, 128, 3, net.output_activation),
             _Mlp2.tcnn(nrm_p, 128, 32, 3, _NONE),
             _Mlp2.tcnn(sem_p, 128, 32, model.semantic_header.n_output_dims, _NONE))
@@ -242,13 +247,299 @@ def _density_fused_ok(enc, W1, b1, W2, b2):
             and (b2 is None or b2.numel() == 1))
 
 
+# The inputs of _FieldFn.forward (and so of NGP._field's apply), in order: backward looks up which of them need a gradient
+# and hands its gradients back under these names.
+_FIELD_INPUTS = ("model", "x", "d", "embed_a", "xyz_table", "W1", "b1", "W2", "b2", "rgb_table", "rgb_p", "nrm_p", "sem_p",
+                 "ray_codes", "second_order")
+
+
+class _Saved(NamedTuple):
+    """What _FieldFn.forward keeps for backward, in save_for_backward's order."""
+    xn: torch.Tensor            # (n, 3) normalised positions
+    feat: torch.Tensor          # density path: grid features (n, 128), hidden layer a1 (n, 128), sigma (n, 1) and
+    a1: torch.Tensor            # dsig_dfeat = d(sigma)/d(features) (n, 128)
+    sig: torch.Tensor
+    dsig_dfeat: torch.Tensor
+    rgb_o: torch.Tensor         # colour branch: the three outputs (n, 3) (n, 3) (n, C), rgb_net's input matrix (n, Kp) and
+    np_o: torch.Tensor          # the three hidden layers (n, 128) (n, 32) (n, 32)
+    sem_o: torch.Tensor
+    rgb_in: torch.Tensor
+    a_r: torch.Tensor
+    a_n: torch.Tensor
+    a_s: torch.Tensor
+    xyz_table: torch.Tensor
+    W1: torch.Tensor
+    W2: torch.Tensor
+    rgb_table: torch.Tensor
+    rgb_p: torch.Tensor
+    nrm_p: torch.Tensor
+    sem_p: torch.Tensor
+    d: Optional[torch.Tensor]   # the view directions, kept only when they need a gradient (pose refinement: its kernel
+                                # reads them again)
+
+
+def _forward_buffers(n, C, Kp, dev):
+    """Every buffer of one forward -> (d(sigma)/dxn (n, 3), the eleven of _Saved from feat to a_s).  They come from the
+    caller's stream (the allocator then knows them as that stream's; the colour stream only launches into them and is
+    joined before anything is returned)."""
+    feat = torch.empty(n, 128, dtype=_f32, device=dev)
+    a1 = torch.empty(n, 128, dtype=_f32, device=dev)
+    sig = torch.empty(n, 1, dtype=_f32, device=dev)
+    dfeat = torch.empty(n, 128, dtype=_f32, device=dev)
+    grads = torch.empty(n, 3, dtype=_f32, device=dev)   # d sigma / d xn (normalised coordinates)
+    rgb_o = torch.empty(n, 3, dtype=_f32, device=dev)
+    np_o = torch.empty(n, 3, dtype=_f32, device=dev)
+    sem_o = torch.empty(n, C, dtype=_f32, device=dev)
+    rgb_in = torch.empty(n, Kp, dtype=_f32, device=dev)
+    a_r = torch.empty(n, 128, dtype=_f32, device=dev)
+    a_n = torch.empty(n, 32, dtype=_f32, device=dev)
+    a_s = torch.empty(n, 32, dtype=_f32, device=dev)
+    return grads, (feat, a1, sig, dfeat, rgb_o, np_o, sem_o, rgb_in, a_r, a_n, a_s)
+
+
+class _FieldCall:
+    """One forward or one backward of the field node: what its stages share, and the stages.  _FieldFn.forward and
+    _FieldFn.backward hold the schedule (which stage runs when, on which stream); a stage launches on the current stream."""
+
+    def __init__(self, model, saved, E, side, b1=None, b2=None, need=None):
+        """saved: the _Saved; E: length of the appearance codes; side: the stream fork() launches on; need: name of
+        _FIELD_INPUTS -> whether it needs a gradient (backward)"""
+        s = self.s = saved
+        self.model, self.link = model, model.link
+        self.xe, self.re = model.xyz_encoder, model.rgb_encoder
+        self.n, self.dev = s.xn.shape[0], s.xn.device
+        self.E, self.K, self.Kp, self.C = E, 144 + E, s.rgb_in.shape[1], s.sem_o.shape[1]
+        self.W_cols = 128 + E       # [grid features | appearance code]: the columns of dfeat_rgb
+        self.density_mlp, self.rgb_mlp, self.nrm_mlp, self.sem_mlp = _field_mlps(model, s.W1, b1, s.W2, b2, s.rgb_p, s.nrm_p,
+                                                                                 s.sem_p)
+        self.main, self.side, self.forked = torch.cuda.current_stream(), side, False
+        self.need, self.grads = need, {}        # grads: name of _FIELD_INPUTS -> what autograd gets (absent: None)
+        self.dfeat_rgb = None                   # backward: dL/d[grid features | appearance code] (n, W_cols)
+
+    def fork(self, stage, *args):
+        """stage(*args) on the side stream, behind everything the main stream holds so far"""
+        self.side.wait_stream(self.main)
+        with torch.cuda.stream(self.side):
+            stage(*args)
+        self.forked = True
+
+    def join(self):
+        if self.forked:
+            self.main.wait_stream(self.side)
+
+    def sink(self, name, like, acc):
+        """Where the gradient of input `name` accumulates.  `acc`: the storage a trainer owns for it (NGPTrainer: views of
+        one flat buffer, zeroed by its Adam launch), which the launches add straight into while autograd gets None — no
+        zeros_like fill, no AccumulateGrad add per parameter.  Without one: a fresh zero buffer shaped as `like` (a tensor
+        or a shape), which is also what autograd gets."""
+        if acc is None:
+            acc = self.grads[name] = (torch.zeros(like, dtype=_f32, device=self.dev) if isinstance(like, tuple)
+                                      else torch.zeros_like(like))
+        return acc
+
+    def density_head_sinks(self):
+        """-> (dW1, dW2, db1, db2) of the density head, for either of its backwards"""
+        s, sinks = self.s, self.link.grad_sinks
+        return tuple(self.sink(k, like, sinks.get(k)) for k, like in (("W1", s.W1), ("W2", s.W2), ("b1", (128,)), ("b2", (1,))))
+
+    # ---- forward stages
+    def colour_forward(self, d, embed_a, ray_codes, second_order, ev_p, ev_c):
+        """[SH(16) | rgb grid features (128) | appearance code (E) | ones-padding] -> rgb_net and the two heads (the heads on
+        their own stream when the fused kernel takes them), for the forward's colour stream"""
+        s, n, E, K, Kp, C = self.s, self.n, self.E, self.K, self.Kp, self.C
+        rgb_in = s.rgb_in
+        feat_rgb = rgb_in[:, 16:144]
+        if second_order:
+            # The module route's own direction encoding, op for op (F.normalize, the [0,1] remap, ngp_sh_fwd), so that
+            # both normal_ref routes hand rgb_net the same bits.  ngp_sh_fwd_dirs multiplies by a rounded reciprocal
+            # and fuses the remap's add: 14 % of its basis values differ from these by up to 4e-7, which is enough to
+            # move a ReLU pre-activation that lies within 1e-8 of zero across it and with it one sample's whole term of
+            # dW1 (the reference's normal_ref step, G10, has such a sample: 5.5e-5 of rgb_net's gradient)
+            dn = F.normalize(d, p=2, dim=-1, eps=1e-6)
+            call("sh_fwd", ((dn + 1) / 2).contiguous(), n, 4, rgb_in, Kp)
+        else:
+            call("sh_fwd_dirs", d, n, 4, rgb_in, Kp)
+        if ev_c is not None:
+            ev_c.wait()   # the colour table's piece (the stream this runs on waits for it)
+        call("grid_fwd", self.re.desc, s.rgb_table, s.xn, n, rgb_in[:, 16:], Kp)
+        if ev_p is not None:
+            ev_p.wait()   # the MLPs' piece
+        if ray_codes is not None:
+            img_idxs, rays_a = ray_codes
+            if not getattr(rays_a, "_ngp_full_cover", False):   # rows outside every segment: finite inputs
+                rgb_in[:, 144:K] = 0.0
+                rgb_in[:, K:] = 1.0
+            # codes and ones-padding of every sample in one launch
+            call("embed_a_fwd", embed_a, embed_a.shape[0], E, img_idxs, rays_a, rays_a.shape[0], rgb_in[:, 144:], Kp,
+                 Kp - 144)
+        else:
+            if E:
+                rgb_in[:, 144:K] = embed_a
+            if Kp > K:
+                rgb_in[:, K:] = 1.0
+        if C <= 8:
+            # the two 32-wide heads read the same rows as rgb_net: on a stream of their own their 256-thread
+            # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU (-0.03 ms/step)
+            cur = torch.cuda.current_stream()
+            heads = _stream("heads", self.dev, self.link.heads_stream)
+            heads.wait_stream(cur)
+            with torch.cuda.stream(heads):
+                self.nrm_mlp.forward(feat_rgb, Kp, n, s.a_n, s.np_o)
+                self.sem_mlp.forward(feat_rgb, Kp, n, s.a_s, s.sem_o)
+            self.rgb_mlp.forward(rgb_in, Kp, n, s.a_r, s.rgb_o)
+            cur.wait_stream(heads)
+        else:   # (the fused forward's epilogue takes at most 8 outputs)
+            self.rgb_mlp.forward(rgb_in, Kp, n, s.a_r, s.rgb_o)
+            self.nrm_mlp.forward(feat_rgb, Kp, n, s.a_n, s.np_o)
+            call("linear_fwd", feat_rgb, Kp, self.sem_mlp.W1, 128, None, n, 128, 32, _RELU, s.a_s, 32, None)
+            call("linear_fwd", s.a_s, 32, self.sem_mlp.W2, 32, None, n, 32, C, _NONE, s.sem_o, C, None)
+
+    def density_forward(self, grads):
+        """encoder, density head, d(sigma)/d(features) and d(sigma)/dxn (into grads), for the forward's main stream"""
+        s, n, xe, mlp = self.s, self.n, self.xe, self.density_mlp
+        if _density_fused_ok(xe, mlp.W1, mlp.b1, mlp.W2, mlp.b2):
+            # encoder, both layers, d(sigma)/d(features) and d(sigma)/dx in one launch: feat, a1, sig and dfeat bitwise
+            # those of the four launches below, grads within 128 ulps of the row's largest component
+            call("density_field_fwd", xe.desc, s.xyz_table, s.xn, n, mlp.W1, mlp.b1, mlp.W2, mlp.b2, s.feat, s.a1, s.sig,
+                 s.dsig_dfeat, grads)
+        else:
+            dz2 = torch.empty(n, 1, dtype=_f32, device=self.dev)
+            call("grid_fwd", xe.desc, s.xyz_table, s.xn, n, s.feat, 128)
+            # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
+            # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
+            mlp.forward(s.feat, 128, n, s.a1, s.sig, dact=dz2)
+            # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
+            call("mlp_bwd_input", dz2, 1, mlp.W2, 128, s.a1, 128, _SOFTPLUS, mlp.W1, 128, n, 128, 128, 1, s.dsig_dfeat, 128, 0)
+            call("grid_bwd_input", xe.desc, s.xyz_table, s.xn, s.dsig_dfeat, 128, n, grads)
+        # dsig_dfeat = d(sigma)/d(features) is kept: the density head has ONE output, so the gradient the backward
+        # sends into the density encoder is d_sigma[s] * dsig_dfeat[s] — no second data-gradient product there
+
+    # ---- backward stages
+    def density_scatter(self, d_sig_c, buf):
+        """the density table's scatter of d_sig[s] * d(sigma)/d(features)[s] into buf, for the backward's scatter stream"""
+        call("grid_bwd_param_scaled", self.xe.desc, self.s.xn, self.s.dsig_dfeat, 128, d_sig_c, self.n, buf)
+        self.xe.grad_ready()
+
+    def rgb_net_data_grad(self, d_rgb):
+        """rgb_net's elementwise stage and its data gradient w.r.t. [grid features | appearance code], which creates
+        dfeat_rgb; for pose refinement also w.r.t. the 16 SH columns and on to dL/dd -> rgb_net's _Mlp2Bwd"""
+        s, n, dev, W_cols = self.s, self.n, self.dev, self.W_cols
+        acc = self.sink("rgb_p", s.rgb_p, self.link.grad_sinks.get("rgb_p"))
+        self.dfeat_rgb = torch.empty(n, W_cols, dtype=_f32, device=dev)
+        nb_acc = self.link.norm_acc
+        st = _Mlp2Bwd(self.rgb_mlp, self.rgb_mlp.grad_slices(acc), (d_rgb.contiguous(), s.rgb_o, s.a_r, s.rgb_in, self.Kp),
+                      norm_acc=None if nb_acc is None else nb_acc[0:1])
+        st.input_product(self.dfeat_rgb, W_cols, W_cols, 16, False)
+        if self.need["d"]:
+            # dL/dd: rgb_net's data gradient for the 16 SH columns, then the adjoint of the direction encoding
+            d_sh = torch.empty(n, 16, dtype=_f32, device=dev)
+            st.input_product(d_sh, 16, 16, 0, False)
+            g_d = self.grads["d"] = torch.empty(n, 3, dtype=_f32, device=dev)
+            call("sh_bwd_dirs", s.d, d_sh, 16, n, g_d)
+        return st
+
+    def head_data_grads(self, d_np, d_sem):
+        """the elementwise stages of the seeded 32-wide heads and their data gradients, added to dfeat_rgb (the first
+        creates it when rgb_net has not) -> their _Mlp2Bwds"""
+        s, n, dev, W_cols = self.s, self.n, self.dev, self.W_cols
+        stages = []
+        for d_o, name, mlp, a_h, out in ((d_np, "nrm_p", self.nrm_mlp, s.a_n, s.np_o),
+                                         (d_sem, "sem_p", self.sem_mlp, s.a_s, s.sem_o)):
+            if d_o is None:
+                continue
+            self.link.bound_spoiled()    # a head adds to the colour features' gradient: outside the norm bound
+            acc = self.sink(name, getattr(s, name), self.link.grad_sinks.get(name))
+            first = self.dfeat_rgb is None
+            if first:
+                self.dfeat_rgb = (torch.zeros(n, W_cols, dtype=_f32, device=dev) if self.E
+                                  else torch.empty(n, W_cols, dtype=_f32, device=dev))
+            st = _Mlp2Bwd(mlp, mlp.grad_slices(acc), (d_o.contiguous(), out, a_h, s.rgb_in[:, 16:], self.Kp))
+            st.input_product(self.dfeat_rgb, W_cols, 128, 0, not first)
+            stages.append(st)
+        return stages
+
+    def colour_scatter(self, buf):
+        """the colour table's scatter of dfeat_rgb into buf, for the scatter stream (the main one without a density scatter)"""
+        call("grid_bwd_param", self.re.desc, self.s.xn, self.dfeat_rgb, self.W_cols, self.n, buf)
+        self.re.grad_ready()
+
+    def code_and_position_grads(self, ray_codes, codes_shape):
+        """what dfeat_rgb gives the node's inputs: the appearance codes' gradient (RayCodes: summed per image) and the
+        colour table's share of dL/dx, for the backward's main stream"""
+        n, E, W_cols, need = self.n, self.E, self.W_cols, self.need
+        if E and need["embed_a"] and ray_codes is not None:
+            # per-image sums of the code columns, one launch: into the trainer's sink when its shape is the table's
+            img_idxs, rays_a = ray_codes
+            acc = self.link.grad_sinks.get("embedding_a")
+            acc = self.sink("embed_a", codes_shape, acc if acc is not None and tuple(acc.shape) == codes_shape else None)
+            call("embed_a_bwd", self.dfeat_rgb[:, 128:], W_cols, E, img_idxs, rays_a, rays_a.shape[0], codes_shape[0], acc)
+        elif E and need["embed_a"]:
+            self.grads["embed_a"] = self.dfeat_rgb[:, 128:]
+        if need["x"]:
+            g_x = self.grads["x"] = torch.empty(n, 3, dtype=_f32, device=self.dev)
+            call("grid_bwd_input", self.re.desc, self.s.rgb_table, self.s.xn, self.dfeat_rgb, W_cols, n, g_x)
+
+    def colour_weight_products(self, stages):
+        """dW1 / dW2 of rgb_net and the seeded heads into their sinks, for the main stream beside the scatters"""
+        for st in stages:
+            st.weight_products()
+
+    def density_head(self, d_sig, reuse):
+        """the density head's first-order backward into its sinks, for the main stream; reuse: the density table's share
+        went out with density_scatter (or is not asked for), else the data gradient, its scatter and dL/dx run here"""
+        s, n, xe = self.s, self.n, self.xe
+        sinks = self.density_head_sinks()
+        nb_acc = self.link.norm_acc
+        st = _Mlp2Bwd(self.density_mlp, sinks, (d_sig.contiguous().view(n, 1), s.sig, s.a1, s.feat, 128),
+                      norm_acc=None if nb_acc is None else nb_acc[1:2])
+        if not reuse:
+            dfeat = torch.empty(n, 128, dtype=_f32, device=self.dev)
+            st.input_product(dfeat, 128, 128, 0, False)
+        st.weight_products()
+        self.link.bound_note(st, 1, 1, n)
+        if not reuse:
+            if self.need["xyz_table"]:
+                buf = self.sink("xyz_table", s.xyz_table, xe.grad_buffer)
+                call("grid_bwd_param", xe.desc, s.xn, dfeat, 128, n, buf)
+                xe.grad_ready()
+            if self.need["x"]:
+                gx2 = torch.empty(n, 3, dtype=_f32, device=self.dev)
+                call("grid_bwd_input", xe.desc, s.xyz_table, s.xn, dfeat, 128, n, gx2)
+                self.grads["x"] = gx2 if "x" not in self.grads else self.grads["x"] + gx2
+
+    def density_head_second_order(self, d_sig, v):
+        """Both orders of the density path in one pass, for the main stream (include/ngp_hip.h, D2): v becomes
+        u = dL/d(dfeat) and the table's second-order share in the grid's double backward, r = u W1^T, and
+        ngp_density_head_bwd2 leaves m (dW1 += m^T u), e1 = dL/dz1 with the first-order share of d_sig inside it
+        (dW1 += e1^T feat, db1, dL/dfeat = e1 W1) and dW2 / db2.  The d_sig-scaled scatter and the first-order weight
+        products are not run: each share lands once."""
+        s, n, dev, xe = self.s, self.n, self.dev, self.xe
+        self.link.bound_spoiled()    # the norm bound is not shown to hold for these contributions
+        acc_W1, acc_W2, acc_b1, acc_b2 = self.density_head_sinks()
+        buf = self.sink("xyz_table", s.xyz_table, xe.grad_buffer) if self.need["xyz_table"] else None
+        u = torch.empty(n, 128, dtype=_f32, device=dev)
+        call("grid_bwd_bwd_input", xe.desc, s.xyz_table, s.xn, s.dsig_dfeat, 128, v.contiguous(), n, buf, u)
+        r = torch.empty(n, 128, dtype=_f32, device=dev)
+        call("linear_fwd", u, 128, s.W1, 128, None, n, 128, 128, _NONE, r, 128, None)
+        m = torch.empty(n, 128, dtype=_f32, device=dev)
+        call("density_head_bwd2", s.a1, s.sig, r, s.W2, None if d_sig is None else d_sig.contiguous(), n, m, r, acc_W2, acc_b2,
+             _workspace("density_head_bwd2", dev))
+        call("linear_bwd_weight", m, 128, u, 128, n, 128, 128, acc_W1, 128, None)
+        call("linear_bwd_weight", r, 128, s.feat, 128, n, 128, 128, acc_W1, 128, acc_b1)      # (r holds e1 now)
+        if buf is not None:
+            call("linear_bwd_input", r, 128, s.W1, 128, n, 128, 128, m, 128, 0)               # (m is free: dL/dfeat)
+            call("grid_bwd_param", xe.desc, s.xn, m, 128, n, buf)
+            xe.grad_ready()
+
+
 class _FieldFn(Function):
     """The whole NGP field (networks.py:198-240) as one autograd node: explicit kernel launches on
     preallocated buffers, no concat (both encoders write straight into rgb_net's input matrix),
     analytic d(sigma)/dx, and a backward that runs only the branches whose outputs received a
-    gradient (normal / semantic heads are skipped when the loss does not use them).
+    gradient (normal / semantic heads are skipped when the loss does not use them).  forward and backward hold the
+    schedule; the stages they order are _FieldCall's methods.
 
-    inputs : x (N,3) world, d (N,3), embed_a (N,E) or None, then the 9 parameter tensors
+    inputs : _FIELD_INPUTS: x (N,3) world, d (N,3), embed_a (N,E) or None, then the 9 parameter tensors
     outputs: sigma (N), rgb (N,3) [after rgb_net's output activation], dsigma/dxn (N,3) w.r.t. the
              normalised position (no grad; divide by xyz_max-xyz_min for world units),
              normal head (N,3) raw, semantic logits (N,C)
@@ -261,326 +552,99 @@ class _FieldFn(Function):
         # density table and xyz_net through ngp_grid_bwd_bwd_input and ngp_density_head_bwd2 in backward
         # ray_codes = (img_idxs (n_rays) i64, rays_a (n_rays, 3) i64) of appearance.RayCodes: embed_a is then the
         # (n_imgs, E) embedding TABLE, broadcast per sample by ngp_embed_a_fwd and summed back by ngp_embed_a_bwd
-        n = x.shape[0]
-        dev = x.device
-        xe, re = model.xyz_encoder, model.rgb_encoder
-        C = model.semantic_header.n_output_dims
-        E = 0 if embed_a is None else embed_a.shape[1]
-        K = 144 + E
-        Kp = model.rgb_net.padded_in
-        span = model._span()
-        xn = (x - model.xyz_min).div_(span)   # (before the waits below: it reads no parameter and runs under the Adam sweep)
-        # the two pieces of the trainer's Adam sweep (or of the sharded optimizer's all-gather): every stream below waits
-        # for a piece where it first reads that piece's parameters
-        link = model.link
-        ev_p, ev_c = link.take_param_events()
-        # every buffer comes from the caller's stream (the allocator then knows them as that stream's; the colour
-        # stream below only launches into them and is joined before anything is returned)
-        feat = torch.empty(n, 128, dtype=_f32, device=dev)
-        a1 = torch.empty(n, 128, dtype=_f32, device=dev)
-        sig = torch.empty(n, 1, dtype=_f32, device=dev)
-        dfeat = torch.empty(n, 128, dtype=_f32, device=dev)
-        grads = torch.empty(n, 3, dtype=_f32, device=dev)   # d sigma / d xn (normalised coordinates)
-        rgb_o = torch.empty(n, 3, dtype=_f32, device=dev)
-        np_o = torch.empty(n, 3, dtype=_f32, device=dev)
-        sem_o = torch.empty(n, C, dtype=_f32, device=dev)
-        rgb_in = torch.empty(n, Kp, dtype=_f32, device=dev)
-        a_r = torch.empty(n, 128, dtype=_f32, device=dev)
-        a_n = torch.empty(n, 32, dtype=_f32, device=dev)
-        a_s = torch.empty(n, 32, dtype=_f32, device=dev)
-        density_mlp, rgb_mlp, nrm_mlp, sem_mlp = _field_mlps(model, W1, b1, W2, b2, rgb_p, nrm_p, sem_p)
-
-        def colour_branch():
-            # [SH(16) | rgb grid features (128) | appearance code (E) | ones-padding] -> rgb_net, the two heads
-            feat_rgb = rgb_in[:, 16:144]
-            if second_order:
-                # The module route's own direction encoding, op for op (F.normalize, the [0,1] remap, ngp_sh_fwd), so that
-                # both normal_ref routes hand rgb_net the same bits.  ngp_sh_fwd_dirs multiplies by a rounded reciprocal
-                # and fuses the remap's add: 14 % of its basis values differ from these by up to 4e-7, which is enough to
-                # move a ReLU pre-activation that lies within 1e-8 of zero across it and with it one sample's whole term of
-                # dW1 (the reference's normal_ref step, G10, has such a sample: 5.5e-5 of rgb_net's gradient)
-                dn = F.normalize(d, p=2, dim=-1, eps=1e-6)
-                call("sh_fwd", ((dn + 1) / 2).contiguous(), n, 4, rgb_in, Kp)
-            else:
-                call("sh_fwd_dirs", d, n, 4, rgb_in, Kp)
-            if ev_c is not None:
-                ev_c.wait()   # the colour table's piece (the stream this runs on waits for it)
-            call("grid_fwd", re.desc, rgb_table, xn, n, rgb_in[:, 16:], Kp)
-            if ev_p is not None:
-                ev_p.wait()   # the MLPs' piece
-            if ray_codes is not None:
-                img_idxs, rays_a = ray_codes
-                if not getattr(rays_a, "_ngp_full_cover", False):   # rows outside every segment: finite inputs
-                    rgb_in[:, 144:K] = 0.0
-                    rgb_in[:, K:] = 1.0
-                # codes and ones-padding of every sample in one launch
-                call("embed_a_fwd", embed_a, embed_a.shape[0], E, img_idxs, rays_a, rays_a.shape[0], rgb_in[:, 144:], Kp,
-                     Kp - 144)
-            else:
-                if E:
-                    rgb_in[:, 144:K] = embed_a
-                if Kp > K:
-                    rgb_in[:, K:] = 1.0
-            if C <= 8:
-                # the two 32-wide heads read the same rows as rgb_net: on a stream of their own their 256-thread
-                # workgroups (72 registers) fit beside the 8-wave rgb_net workgroup on every CU (-0.03 ms/step)
-                cur = torch.cuda.current_stream()
-                heads = _stream("heads", dev, link.heads_stream)
-                heads.wait_stream(cur)
-                with torch.cuda.stream(heads):
-                    nrm_mlp.forward(feat_rgb, Kp, n, a_n, np_o)
-                    sem_mlp.forward(feat_rgb, Kp, n, a_s, sem_o)
-                rgb_mlp.forward(rgb_in, Kp, n, a_r, rgb_o)
-                cur.wait_stream(heads)
-            else:   # (the fused forward's epilogue takes at most 8 outputs)
-                rgb_mlp.forward(rgb_in, Kp, n, a_r, rgb_o)
-                nrm_mlp.forward(feat_rgb, Kp, n, a_n, np_o)
-                call("linear_fwd", feat_rgb, Kp, sem_mlp.W1, 128, None, n, 128, 32, _RELU, a_s, 32, None)
-                call("linear_fwd", a_s, 32, sem_mlp.W2, 32, None, n, 32, C, _NONE, sem_o, C, None)
-
-        # The colour branch needs the positions and the colour table, nothing of the density path: it runs on a
+        #
+        # Schedule.  The colour branch needs the positions and the colour table, nothing of the density path: it runs on a
         # stream of its own from the moment the colour table's Adam piece is done, beside the rest of the density
         # path and the analytic normals (which are stretched beyond that piece's end on one stream).
-        main = torch.cuda.current_stream()
-        side = _stream("colour", dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            colour_branch()
-
-        # density head
+        #   main  : xn, buffers -> (fork) -> wait MLP piece -> density path ------------------------------------> join
+        #   colour:                 SH -> wait colour piece -> colour gather -> wait MLP piece -> codes -> rgb_net -> join
+        #   heads :                                                     (C <= 8, forked behind the codes)  two heads -^
+        # ev_p, ev_c: the two pieces of the trainer's Adam sweep (or of the sharded optimizer's all-gather): every stream
+        # waits for a piece where it first reads that piece's parameters
+        E = 0 if embed_a is None else embed_a.shape[1]
+        xn = (x - model.xyz_min).div_(model._span())   # (before the waits: it reads no parameter and runs under the Adam sweep)
+        ev_p, ev_c = model.link.take_param_events()
+        keep_d = ctx.needs_input_grad[_FIELD_INPUTS.index("d")]
+        grads, buffers = _forward_buffers(x.shape[0], model.semantic_header.n_output_dims, model.rgb_net.padded_in, x.device)
+        saved = _Saved(xn, *buffers, xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, d if keep_d else None)
+        c = _FieldCall(model, saved, E, _stream("colour", x.device), b1, b2)
+        c.fork(c.colour_forward, d, embed_a, ray_codes, second_order, ev_p, ev_c)
         if ev_p is not None:
             ev_p.wait()
-        if _density_fused_ok(xe, W1, b1, W2, b2):
-            # encoder, both layers, d(sigma)/d(features) and d(sigma)/dx in one launch: feat, a1, sig and dfeat bitwise
-            # those of the four launches below, grads within 128 ulps of the row's largest component
-            call("density_field_fwd", xe.desc, xyz_table, xn, n, W1, b1, W2, b2, feat, a1, sig, dfeat, grads)
-        else:
-            dz2 = torch.empty(n, 1, dtype=_f32, device=dev)
-            call("grid_fwd", xe.desc, xyz_table, xn, n, feat, 128)
-            # both layers in one launch, the 1-wide second layer in the MFMA epilogue, which also leaves
-            # dz2 = softplus'(z2) = 1 - exp(-sigma): the start of the d(sigma)/dx pass below (no act_bwd launch)
-            density_mlp.forward(feat, 128, n, a1, sig, dact=dz2)
-            # analytic d(sigma)/dx: back-substitute ones through the head, then the grid input gradient
-            call("mlp_bwd_input", dz2, 1, W2, 128, a1, 128, _SOFTPLUS, W1, 128, n, 128, 128, 1, dfeat, 128, 0)
-            call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, grads)
-        # dfeat = d(sigma)/d(features) is kept: the density head has ONE output, so the gradient the backward
-        # sends into the density encoder is d_sigma[s] * dfeat[s] — no second data-gradient product there
+        c.density_forward(grads)
+        c.join()
 
-        main.wait_stream(side)
-
-        ctx.model = model
-        ctx.E, ctx.K, ctx.Kp, ctx.C = E, K, Kp, C
+        ctx.model, ctx.E = model, E
         ctx.ray_codes = ray_codes
         ctx.codes_shape = None if ray_codes is None else tuple(embed_a.shape)
-        # (pose refinement: the view directions need a gradient, and its kernel reads them again)
-        ctx.save_for_backward(xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
-                              xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dfeat,
-                              *((d,) if ctx.needs_input_grad[2] else ()))
+        ctx.save_for_backward(*saved)
         if not second_order:
             ctx.mark_non_differentiable(grads)
         ctx.set_materialize_grads(False)
-        return sig[:, 0], rgb_o, grads, np_o, sem_o
+        return saved.sig[:, 0], saved.rgb_o, grads, saved.np_o, saved.sem_o
 
     @staticmethod
     def backward(ctx, d_sig, d_rgb, v, d_np, d_sem):
         # v = dL/d(d sigma/dxn) (n,3): only a node built with second_order=True can receive one
-        (xn, feat, a1, sig, rgb_in, a_r, rgb_o, a_n, np_o, a_s, sem_o,
-         xyz_table, W1, W2, rgb_table, rgb_p, nrm_p, sem_p, dsig_dfeat) = ctx.saved_tensors[:19]
-        model = ctx.model
-        link = model.link
-        E, K, Kp, C = ctx.E, ctx.K, ctx.Kp, ctx.C
-        n = xn.shape[0]
-        dev = xn.device
-        xe, re = model.xyz_encoder, model.rgb_encoder
-        need = ctx.needs_input_grad  # (model, x, d, embed_a, xyz_table, W1, b1, W2, b2, rgb_table, rgb_p, nrm_p, sem_p)
-        g_x = g_d = g_emb = g_xyz = g_W1 = g_b1 = g_W2 = g_b2 = g_rgbt = g_rgbp = g_nrm = g_sem = None
-        span = model._span()
-        # A trainer that owns the gradient storage (NGPTrainer: one flat buffer, zeroed by its Adam
-        # launch) registers the MLP gradients as sinks: the weight products accumulate straight into
-        # them and autograd gets None — no zeros_like fill, no AccumulateGrad add per parameter.
-        sinks = link.grad_sinks
-        density_mlp, rgb_mlp, nrm_mlp, sem_mlp = _field_mlps(model, W1, None, W2, None, rgb_p, nrm_p, sem_p)
-
-        def grad_buffer(name, like):
-            t = sinks.get(name)
-            if t is not None:
-                return t, None          # (accumulate here, return nothing to autograd)
-            z = torch.zeros(like, dtype=_f32, device=dev) if isinstance(like, tuple) else torch.zeros_like(like)
-            return z, z
-
+        #
         # Schedule.  The two table scatters are bound by memory-side atomic requests, the MLP products by the
         # matrix pipe: the scatters go to a side stream, one behind the other, and the products run beside them.
         #   side: [density scatter] -> [colour scatter (+ its share of the gradient norm / its reduce-scatter)]
-        #   main: colour data gradients -> (fork) -> colour weight gradients -> density weight gradients -> join
+        #   main: colour data gradients -> (fork) -> codes, dL/dx -> colour weight gradients -> density head -> join
         # The density scatter can start at once: its input is d_sigma[s] * d(sigma)/d(features)[s], and the second
-        # factor was computed (and kept) by the forward pass for the analytic normals.
-        main = torch.cuda.current_stream()
-        side = _stream("scatter", dev, link.side_stream)
-        forked = False
-        ev = link.take_acc_zeroed()   # the trainer clears its norm accumulators behind the Adam launches
+        # factor was computed (and kept) by the forward pass for the analytic normals.  It runs when that product is the
+        # table's whole share: not with dL/dx asked for (the density head then forms its data gradient anyway and scatters
+        # it) and not with v (density_head_second_order scatters both orders' shares at once).
+        need = dict(zip(_FIELD_INPUTS, ctx.needs_input_grad))
+        saved = _Saved(*ctx.saved_tensors)
+        c = _FieldCall(ctx.model, saved, ctx.E, _stream("scatter", saved.xn.device, ctx.model.link.side_stream), need=need)
+        ev = c.link.take_acc_zeroed()   # the trainer clears its norm accumulators behind the Adam launches
         if ev is not None:
             ev.wait()
-
-        def on_side(fn):
-            nonlocal forked
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                fn()
-            forked = True
-
-        def table_buffer(enc, table):
-            if enc.grad_buffer is not None:
-                return enc.grad_buffer, None
-            buf = torch.zeros_like(table)
-            return buf, buf
-
-        if v is not None and need[1]:
+        if v is not None and need["x"]:
             raise RuntimeError("second-order normals with sample positions that require a gradient (pose refinement): the "
                                "field's second order has no dL/dx")
-        reuse = d_sig is not None and not need[1]
-        if reuse and need[4] and v is None:
-            d_sig_c = d_sig.contiguous()
-            buf, g_xyz = table_buffer(xe, xyz_table)
-
-            def density_scatter():
-                call("grid_bwd_param_scaled", xe.desc, xn, dsig_dfeat, 128, d_sig_c, n, buf)
-                xe.grad_ready()
-            # Data parallel: the colour table's gradient (77 % of the bytes) goes into its reduce-scatter the moment
-            # its scatter is enqueued, so there the colour scatter leads on the side stream and the density scatter
-            # follows it — the collective then runs under the density scatter and the weight products.
-            density_later = re.grad_ready_is_collective and d_rgb is not None and need[9]
-            # One GPU: the density scatter leads on the side stream and is let loose at once.  It becomes ready together
-            # with the colour branch's data gradient, and whichever reaches the CUs first keeps them (the product takes
-            # 0.15 ms when its 256 large workgroups are placed first, 0.4-0.6 ms behind the scatter's thousands of
-            # small ones).  Holding the scatter back behind the product makes that deterministic and is the slower
-            # schedule: +0.04 ms/step (3 alternations of 100 steps), the scatters are the longer path and every
-            # microsecond they start later is lost.
-            if not density_later:
-                on_side(density_scatter)
-                density_scatter = None
-        else:
-            density_scatter = None
-
-        # ---- colour branch (rgb_net + the two heads): data gradients w.r.t. [grid features | appearance code] first
-        dfeat_rgb = None
-        W_cols = 128 + E
-        stages = []
-        rgb_stage = None
-        if d_rgb is not None:
-            acc_rgbp, g_rgbp = grad_buffer("rgb_p", rgb_p)
-            dfeat_rgb = torch.empty(n, W_cols, dtype=_f32, device=dev)
-            nb_acc = link.norm_acc
-            st = _Mlp2Bwd(rgb_mlp, rgb_mlp.grad_slices(acc_rgbp), (d_rgb.contiguous(), rgb_o, a_r, rgb_in, Kp),
-                          norm_acc=None if nb_acc is None else nb_acc[0:1])
-            st.input_product(dfeat_rgb, W_cols, W_cols, 16, False)
-            stages.append(st)
-            rgb_stage = st
-            if need[2]:
-                # dL/dd: rgb_net's data gradient for the 16 SH columns, then the adjoint of the direction encoding
-                d_sh = torch.empty(n, 16, dtype=_f32, device=dev)
-                st.input_product(d_sh, 16, 16, 0, False)
-                g_d = torch.empty(n, 3, dtype=_f32, device=dev)
-                call("sh_bwd_dirs", ctx.saved_tensors[19], d_sh, 16, n, g_d)
-        for d_o, p, mlp, a_h, out, slot in ((d_np, nrm_p, nrm_mlp, a_n, np_o, "nrm"),
-                                            (d_sem, sem_p, sem_mlp, a_s, sem_o, "sem")):
-            if d_o is None:
-                continue
-            link.bound_spoiled()    # a head adds to the colour features' gradient: outside the norm bound
-            acc_p, g_p = grad_buffer(slot + "_p", p)
-            first = dfeat_rgb is None
-            if first:
-                dfeat_rgb = torch.zeros(n, W_cols, dtype=_f32, device=dev) if E else torch.empty(n, W_cols, dtype=_f32, device=dev)
-            st = _Mlp2Bwd(mlp, mlp.grad_slices(acc_p), (d_o.contiguous(), out, a_h, rgb_in[:, 16:], Kp))
-            st.input_product(dfeat_rgb, W_cols, 128, 0, not first)
-            stages.append(st)
-            if slot == "nrm":
-                g_nrm = g_p
-            else:
-                g_sem = g_p
-
-        if dfeat_rgb is not None and need[9]:
-            buf_c, g_rgbt = table_buffer(re, rgb_table)
-
-            def colour_scatter():
-                call("grid_bwd_param", re.desc, xn, dfeat_rgb, W_cols, n, buf_c)
-                re.grad_ready()
+        reuse = d_sig is not None and not need["x"]
+        scaled = reuse and need["xyz_table"] and v is None
+        if scaled:
+            scatter_args = d_sig.contiguous(), c.sink("xyz_table", saved.xyz_table, c.xe.grad_buffer)
+        # Does the density scatter lead or follow on the side stream?
+        # Data parallel: the colour table's gradient (77 % of the bytes) goes into its reduce-scatter the moment
+        # its scatter is enqueued, so there the colour scatter leads on the side stream and the density scatter
+        # follows it — the collective then runs under the density scatter and the weight products.
+        # One GPU: the density scatter leads on the side stream and is let loose at once.  It becomes ready together
+        # with the colour branch's data gradient, and whichever reaches the CUs first keeps them (the product takes
+        # 0.15 ms when its 256 large workgroups are placed first, 0.4-0.6 ms behind the scatter's thousands of
+        # small ones).  Holding the scatter back behind the product makes that deterministic and is the slower
+        # schedule: +0.04 ms/step (3 alternations of 100 steps), the scatters are the longer path and every
+        # microsecond they start later is lost.
+        follows = scaled and c.re.grad_ready_is_collective and d_rgb is not None and need["rgb_table"]
+        if scaled and not follows:
+            c.fork(c.density_scatter, *scatter_args)
+        stages = ([c.rgb_net_data_grad(d_rgb)] if d_rgb is not None else []) + c.head_data_grads(d_np, d_sem)
+        if c.dfeat_rgb is not None and need["rgb_table"]:
+            buf = c.sink("rgb_table", saved.rgb_table, c.re.grad_buffer)
             if d_sig is not None:
-                on_side(colour_scatter)
+                c.fork(c.colour_scatter, buf)
             else:
-                colour_scatter()
-        if density_scatter is not None:
-            on_side(density_scatter)
-        if dfeat_rgb is not None:
-            if E and need[3] and ctx.ray_codes is not None:
-                # per-image sums of the code columns, one launch: into the trainer's flat gradient when it registered the
-                # table as a sink (autograd then gets None), else into a fresh buffer handed to autograd
-                img_idxs, rays_a = ctx.ray_codes
-                acc_e = sinks.get("embedding_a")
-                if acc_e is None or tuple(acc_e.shape) != ctx.codes_shape:
-                    acc_e = g_emb = torch.zeros(ctx.codes_shape, dtype=_f32, device=dev)
-                call("embed_a_bwd", dfeat_rgb[:, 128:], W_cols, E, img_idxs, rays_a, rays_a.shape[0], ctx.codes_shape[0], acc_e)
-            elif E and need[3]:
-                g_emb = dfeat_rgb[:, 128:]
-            if need[1]:
-                g_x = torch.empty(n, 3, dtype=_f32, device=dev)
-                call("grid_bwd_input", re.desc, rgb_table, xn, dfeat_rgb, W_cols, n, g_x)
-        for st in stages:
-            st.weight_products()
-
-        # ---- density head
+                c.colour_scatter(buf)
+        if follows:
+            c.fork(c.density_scatter, *scatter_args)
+        if c.dfeat_rgb is not None:
+            c.code_and_position_grads(ctx.ray_codes, ctx.codes_shape)
+        c.colour_weight_products(stages)
         if v is not None:
-            # Both orders in one pass (include/ngp_hip.h, D2): v becomes u = dL/d(dfeat) and the table's second-order share
-            # in the grid's double backward, r = u W1^T, and ngp_density_head_bwd2 leaves m (dW1 += m^T u), e1 = dL/dz1 with
-            # the first-order share of d_sig inside it (dW1 += e1^T feat, db1, dL/dfeat = e1 W1) and dW2 / db2.  The
-            # d_sig-scaled scatter and the first-order weight products are not run: each share lands once.
-            link.bound_spoiled()    # the norm bound is not shown to hold for these contributions
-            (acc_W1, g_W1), (acc_W2, g_W2) = grad_buffer("W1", W1), grad_buffer("W2", W2)
-            (acc_b1, g_b1), (acc_b2, g_b2) = grad_buffer("b1", (128,)), grad_buffer("b2", (1,))
-            buf = None
-            if need[4]:
-                buf, g_xyz = table_buffer(xe, xyz_table)
-            u = torch.empty(n, 128, dtype=_f32, device=dev)
-            call("grid_bwd_bwd_input", xe.desc, xyz_table, xn, dsig_dfeat, 128, v.contiguous(), n, buf, u)
-            r = torch.empty(n, 128, dtype=_f32, device=dev)
-            call("linear_fwd", u, 128, W1, 128, None, n, 128, 128, _NONE, r, 128, None)
-            m = torch.empty(n, 128, dtype=_f32, device=dev)
-            call("density_head_bwd2", a1, sig, r, W2, None if d_sig is None else d_sig.contiguous(), n, m, r, acc_W2, acc_b2,
-                 _workspace("density_head_bwd2", dev))
-            call("linear_bwd_weight", m, 128, u, 128, n, 128, 128, acc_W1, 128, None)
-            call("linear_bwd_weight", r, 128, feat, 128, n, 128, 128, acc_W1, 128, acc_b1)      # (r holds e1 now)
-            if buf is not None:
-                call("linear_bwd_input", r, 128, W1, 128, n, 128, 128, m, 128, 0)               # (m is free: dL/dfeat)
-                call("grid_bwd_param", xe.desc, xn, m, 128, n, buf)
-                xe.grad_ready()
+            c.density_head_second_order(d_sig, v)
         elif d_sig is not None:
-            (acc_W1, g_W1), (acc_W2, g_W2) = grad_buffer("W1", W1), grad_buffer("W2", W2)
-            (acc_b1, g_b1), (acc_b2, g_b2) = grad_buffer("b1", (128,)), grad_buffer("b2", (1,))
-            nb_acc = link.norm_acc
-            st = _Mlp2Bwd(density_mlp, (acc_W1, acc_W2, acc_b1, acc_b2), (d_sig.contiguous().view(n, 1), sig, a1, feat, 128),
-                          norm_acc=None if nb_acc is None else nb_acc[1:2])
-            if not reuse:
-                dfeat = torch.empty(n, 128, dtype=_f32, device=dev)
-                st.input_product(dfeat, 128, 128, 0, False)
-            st.weight_products()
-            link.bound_note(st, 1, 1, n)
-            if not reuse:
-                if need[4]:
-                    buf, g_xyz = table_buffer(xe, xyz_table)
-                    call("grid_bwd_param", xe.desc, xn, dfeat, 128, n, buf)
-                    xe.grad_ready()
-                if need[1]:
-                    gx2 = torch.empty(n, 3, dtype=_f32, device=dev)
-                    call("grid_bwd_input", xe.desc, xyz_table, xn, dfeat, 128, n, gx2)
-                    g_x = gx2 if g_x is None else g_x + gx2
+            c.density_head(d_sig, reuse)
         # the norm-bound sums feed the optimizer's clip decision only: behind the weight products, where they fill the
         # wait for the scatters instead of sitting between the data gradient and the weight gradient (67 us there)
-        if rgb_stage is not None:
-            link.bound_note(rgb_stage, 0, 3, rgb_stage.n)
-        if g_x is not None:
-            g_x = g_x / span
-        if forked:
-            main.wait_stream(side)
-        return (None, g_x, g_d, g_emb, g_xyz, g_W1, g_b1, g_W2, g_b2, g_rgbt, g_rgbp, g_nrm, g_sem, None, None)
+        if d_rgb is not None:
+            c.link.bound_note(stages[0], 0, 3, c.n)
+        if "x" in c.grads:
+            c.grads["x"] = c.grads["x"] / c.model._span()
+        c.join()
+        return tuple(c.grads.get(k) for k in _FIELD_INPUTS)
 
 
 _WORKSPACES = {}
@@ -762,8 +826,7 @@ class NGP(nn.Module):
                 call("grid_fwd", self.xyz_encoder.desc, self.xyz_encoder.params, x, n, feat, 128)
                 a1 = torch.empty(n, 128, dtype=_f32, device=x.device)
                 sig = torch.empty(n, 1, dtype=_f32, device=x.device)
-                call("mlp2_fwd", feat, 128, lin1.weight, 128, lin1.bias, _SOFTPLUS, lin2.weight, 128, lin2.bias,
-                     _SOFTPLUS, n, 128, 128, 1, a1, 128, sig, 1)
+                _density_mlp(lin1.weight, lin1.bias, lin2.weight, lin2.bias).forward(feat, 128, n, a1, sig)
                 sigmas = sig[:, 0]
         else:
             sigmas = self._density_head(self.xyz_encoder(x))
