@@ -887,6 +887,71 @@ int ngp_mesh_simplify_faces(const int32_t* faces, int n_faces, int n_verts, cons
                             int32_t* faces_out, int32_t* used, void* stream);
 
 /* ------------------------------------------------------------------------
+ * M4  mesh evaluation: area-weighted surface samples and the exact distance from points to a triangle mesh
+ *     (accuracy / completeness / Chamfer / F-score of an export, mesh.py mesh_distance, tools/eval_mesh.py)
+ * verts (n_verts, 3) f32, faces (n_faces, 3) int32 with every index in [0, n_verts) (the caller checks it).  All f32
+ * arithmetic below is uncontracted, in the order written.
+ * ngp_mesh_sample_surface: sample i of n (n <= 2^30) depends on (seed, i) alone - one thread per sample, no state,
+ * the same bytes from run to run and for any launch shape.  With fmix32 the 32-bit finaliser of MurmurHash3 (h ^= h >>
+ * 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16) and integers mod 2^32: u_k = fmix32(seed +
+ * 0x9E3779B9 * (3 i + k + 1)), k = 0, 1, 2.  cdf (n_faces) f64 is the inclusive running sum of the face areas and
+ * total = cdf[n_faces - 1], both from the caller (total zero, negative or not finite: NGP_EINVAL).  t = ((u_0 + 0.5) *
+ * 2^-32) * total in double; the face is the first f with cdf[f] > t (binary search), clamped to the first f with
+ * cdf[f] >= total (the last face with an area): a face that adds nothing to cdf is never drawn.  r1 = (u_1 >> 8) *
+ * 2^-24, r2 = (u_2 >> 8) * 2^-24 in f32; if r1 + r2 > 1 (f32) then r1 = 1 - r1, r2 = 1 - r2; per axis
+ * p = (v0 + r1 * (v1 - v0)) + r2 * (v2 - v0).  Writes points (n, 3) f32 and face (n) int32.
+ * The grid: dims3[a] cells of edge 1 / inv_cell per axis from origin3 (both HOST arrays; dims3[a] in [1, 1024],
+ * dims3[0] * dims3[1] * dims3[2] <= 2^24), cell (x, y, z) at index (x * dims3[1] + y) * dims3[2] + z.  The cell
+ * coordinate of a position is floorf((p_a - origin3[a]) * inv_cell) per axis, as in M3.  A face is referenced from
+ * every cell of the box [min, max] of its corners' cell coordinates (clamped to the grid; a corner outside the grid
+ * raises error bit 2 - the caller's grid must cover the mesh), except that a face whose f32 cross product
+ * (v1 - v0) x (v2 - v0) = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x) is exactly (0,0,0) is
+ * referenced nowhere, and a face with a non-finite corner raises error bit 1 and is referenced nowhere.
+ * ngp_mesh_grid_count adds each face's references to cell_count (cells, int32, zeroed by the caller; integer
+ * atomicAdd) and leaves totals[0] = references, totals[1] = error bits (2 int64 on the device; it zeroes them first).
+ * The caller forms cell_offset (cells + 1, int32): 0, then the inclusive running sum of cell_count (references <=
+ * 2^28).  ngp_mesh_grid_fill writes face f at cell_faces[cell_offset[cell] + (what an integer atomicAdd on
+ * cell_cursor[cell] returned)] (cell_cursor: cells int32, zeroed by the caller): the order inside a cell is arbitrary.
+ * Within a launch threads learn about each other only through the return values of atomics; the tables are read in
+ * later launches only.
+ * ngp_mesh_closest: one thread per point; d2[i] = the smallest squared distance from points[i] to a face with a
+ * non-zero cross product, face[i] = that face; among equal d2 the smallest face index; candidates are compared with <,
+ * so a NaN or infinite d2 never wins; if the winner's d2 > max_dist * max_dist (one f32 product) or nothing won,
+ * d2[i] = max_dist * max_dist and face[i] = -1 (n_faces == 0: every point).  The squared distance to a triangle
+ * (a, b, c), with dot(x, y) = (x.x * y.x + x.y * y.y) + x.z * y.z and the first region that applies (Ericson, Real-Time
+ * Collision Detection 5.1.5):
+ *   ab = b - a, ac = c - a, ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap);   d1 <= 0 and d2 <= 0: q = a
+ *   bp = p - b, d3 = dot(ab, bp), d4 = dot(ac, bp);                           d3 >= 0 and d4 <= d3: q = b
+ *   vc = d1 * d4 - d3 * d2;       vc <= 0 and d1 >= 0 and d3 <= 0: q = a + ab * (d1 / (d1 - d3))
+ *   cp = p - c, d5 = dot(ab, cp), d6 = dot(ac, cp);                           d6 >= 0 and d5 <= d6: q = c
+ *   vb = d5 * d2 - d1 * d6;       vb <= 0 and d2 >= 0 and d6 <= 0: q = a + ac * (d2 / (d2 - d6))
+ *   va = d3 * d6 - d5 * d4;       va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0:
+ *                                 q = b + (c - b) * ((d4 - d3) / ((d4 - d3) + (d5 - d6)))
+ *   else den = 1 / ((va + vb) + vc), q = (a + ab * (vb * den)) + ac * (vc * den)
+ *   e = p - q, result dot(e, e); every division is IEEE.
+ * The search walks the cells of growing Chebyshev distance r from the point's own (unclamped) cell coordinate and stops
+ * after a whole ring when no face it has not seen can win or tie (a lower bound that allows for the rounding of the
+ * cell coordinates and of the distance itself: mesh_eval_kernels.hip), after ceil(max_dist * inv_cell) + 1 rings (plus
+ * that allowance), or when the grid is exhausted: every loop is bounded before it starts, none waits on another thread,
+ * and the result does not depend on the grid or on the order inside a cell.  No floating-point atomics: the same bytes
+ * from run to run.
+ * n == 0 returns NGP_OK before any pointer is looked at (ngp_mesh_grid_*: n_faces == 0); every pointer and size is
+ * checked (NGP_EINVAL) before any launch; max_dist must be >= 0 (infinity is allowed).
+ * ---------------------------------------------------------------------- */
+int ngp_mesh_sample_surface(const float* verts, int n_verts, const int32_t* faces, int n_faces, const double* cdf,
+                            double total, int64_t n, uint32_t seed, float* points, int32_t* face, void* stream);
+int ngp_mesh_grid_count(const float* verts, int n_verts, const int32_t* faces, int n_faces,
+                        const float* origin3 /* host */, float inv_cell, const int32_t* dims3 /* host */,
+                        int32_t* cell_count, int64_t* totals, void* stream);
+int ngp_mesh_grid_fill(const float* verts, int n_verts, const int32_t* faces, int n_faces,
+                       const float* origin3 /* host */, float inv_cell, const int32_t* dims3 /* host */,
+                       const int32_t* cell_offset, int32_t* cell_cursor, int32_t* cell_faces, void* stream);
+int ngp_mesh_closest(const float* points, int64_t n, const float* verts, int n_verts, const int32_t* faces,
+                     int n_faces, const float* origin3 /* host */, float inv_cell, const int32_t* dims3 /* host */,
+                     const int32_t* cell_offset, const int32_t* cell_faces, float max_dist, float* d2, int32_t* face,
+                     void* stream);
+
+/* ------------------------------------------------------------------------
  * I1  SSIM of rendered images (replaces torchmetrics' StructuralSimilarityIndexMeasure(data_range=1) of the
  *     reference's validation step, train.py:93,353-386; no conv2d / MIOpen on the way)
  * pred, gt: `count` images of H*W rows of 3 floats, row-major, channel-last (what render() returns and the loaders

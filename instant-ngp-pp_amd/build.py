@@ -34,6 +34,7 @@ SOURCES = [
     ("mesh_kernels.hip", ["-ffp-contract=off"]),
     ("mesh_clean_kernels.hip", []),
     ("mesh_simplify_kernels.hip", ["-ffp-contract=off"]),   # cell keys are bit-identical to their numpy restatement
+    ("mesh_eval_kernels.hip", ["-ffp-contract=off"]),   # samples and distances are bit-identical to their restatement
     ("image_kernels.hip", ["-ffp-contract=off"]),   # frame packing is bit-identical to its numpy restatement
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

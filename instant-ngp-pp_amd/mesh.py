@@ -8,6 +8,9 @@ own.
   mesh_components(faces, n_verts)                 -> per-vertex component labels and faces per component (M2)
   clean_mesh(verts, faces, keep_largest=, min_faces=) -> the mesh without its small disconnected pieces (M2)
   simplify_mesh(verts, faces, cell= | target_faces=)  -> a smaller mesh: vertex clustering, quadric placement (M3)
+  face_area_cdf / sample_surface(verts, faces, n, seed) -> n area-weighted surface points and their faces (M4)
+  closest_on_mesh(points, verts, faces, max_dist=)    -> exact distance to the mesh and the closest face (M4)
+  mesh_distance(verts_a, faces_a, verts_b, faces_b)   -> accuracy, completeness, Chamfer, Hausdorff, F-score (M4)
   vertex_colors(model, verts, normals, offset)    -> (V,3) uint8 colours rendered by the test-time marcher
   write_ply(path, verts, faces, normals, colors) / read_ply(path, colors=False)
 
@@ -447,6 +450,271 @@ def simplify_mesh(verts, faces, *, cell=None, target_faces=None, origin=None, pl
     torch.cuda.synchronize(dev)
     info["emit_ms"] = 1e3 * (time.perf_counter() - t0)
     return done(out[0], f_out, out[1:])
+
+
+# ----------------------------------------------------------------------------------------------- evaluation (M4)
+GRID_MAX_DIM = 1024          # cells per axis, cells and references ngp_mesh_grid_* / ngp_mesh_closest take
+GRID_MAX_CELLS = 1 << 24
+GRID_MAX_REFS = 1 << 28
+GRID_MAX_PROBES = 32         # count passes while the references do not fit
+MAX_SAMPLES = 1 << 30
+
+
+def _check_points(points):
+    check_input(points, "points")
+    if points.dtype != _f32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be an (n, 3) float32 tensor, got {tuple(points.shape)} {points.dtype}")
+    if points.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"unsupported number of points: {points.shape[0]}")
+
+
+def face_area_cdf(verts, faces):
+    """-> (F,) float64: the inclusive running sum of the face areas 0.5 |(v1 - v0) x (v2 - v0)|, taken in double"""
+    _check_mesh(verts, faces, None, None)
+    v = verts.double()
+    a, b, c = (v[faces[:, k].long()] for k in range(3))
+    return torch.cumsum(0.5 * torch.linalg.cross(b - a, c - a, dim=1).norm(dim=1), 0)
+
+
+def sample_surface(verts, faces, n, seed=0, cdf=None):
+    """n points on the surface, uniform by area -> (points (n,3) f32, face (n,) int32: the face each lies on).
+
+    Sample i is a function of (seed, i) alone (ngp_mesh_sample_surface, include/ngp_hip.h M4): the same bytes from run
+    to run, and the first n samples of a longer run.  cdf: face_area_cdf(verts, faces) if the caller has it.  Faces
+    without area are never drawn; a mesh without area is refused."""
+    _check_mesh(verts, faces, None, None)
+    n = int(n)
+    if n < 0 or n > MAX_SAMPLES:
+        raise ValueError(f"n must lie in [0, 2^30], got {n}")
+    dev = verts.device
+    points = torch.empty(n, 3, dtype=_f32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return points, face
+    n_faces = faces.shape[0]
+    if cdf is None:
+        cdf = face_area_cdf(verts, faces)
+    check_input(cdf, "cdf")
+    if cdf.dtype != torch.float64 or tuple(cdf.shape) != (n_faces,):
+        raise ValueError(f"cdf must be a ({n_faces},) float64 tensor, got {tuple(cdf.shape)} {cdf.dtype}")
+    total = float(cdf[-1]) if n_faces else 0.0
+    if not (total > 0 and np.isfinite(total)):
+        raise ValueError(f"the mesh has no area to sample (total {total}, {n_faces} faces)")
+    call("mesh_sample_surface", verts, verts.shape[0], faces, n_faces, cdf, total, n, int(seed) & 0xFFFFFFFF, points,
+         face)
+    return points, face
+
+
+class _FaceGrid:
+    """the uniform grid of face references ngp_mesh_closest walks: cells of one size from the mesh's lower corner"""
+
+    def __init__(self, verts, faces, lo, hi):
+        self.verts, self.faces = verts, faces
+        self.lo, self.hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+        self.origin = (C.c_float * 3)(*[float(x) for x in self.lo])
+        self.totals = torch.zeros(2, dtype=torch.int64, device=verts.device)
+        self.probes = 0
+
+    def shape(self, cell):
+        """-> (float32 cell, its float32 inverse, dims): dims[a] = the upper corner's cell coordinate + 1, by the
+        kernels' own f32 expression, so every vertex falls inside"""
+        cell = np.float32(cell)
+        with np.errstate(all="ignore"):
+            inv = np.float32(1) / cell
+            dims = np.floor((self.hi - self.lo) * inv) + 1
+        if not (cell > 0 and np.isfinite(cell) and np.isfinite(inv) and np.isfinite(dims).all()):
+            raise ValueError(f"cell must be a positive float32 with a finite inverse, got {cell}")
+        return float(cell), float(inv), [int(d) for d in dims]
+
+    @staticmethod
+    def fits(dims):
+        return max(dims) <= GRID_MAX_DIM and dims[0] * dims[1] * dims[2] <= GRID_MAX_CELLS
+
+    def count(self, cell):
+        """one count pass at this cell (its dims must fit) -> references; the per-cell counts stay in self.counts"""
+        self.cell, self.inv, self.dims = self.shape(cell)
+        self.dims3 = (C.c_int32 * 3)(*self.dims)
+        self.counts = torch.zeros(self.dims[0] * self.dims[1] * self.dims[2], dtype=torch.int32,
+                                  device=self.verts.device)
+        call("mesh_grid_count", self.verts, self.verts.shape[0], self.faces, self.faces.shape[0], self.origin, self.inv,
+             self.dims3, self.counts, self.totals)
+        self.probes += 1
+        refs, err = self.totals.tolist()
+        if err & 1:
+            raise ValueError("a face has a vertex that is not finite")
+        if err:
+            raise RuntimeError(f"ngp_mesh_grid_count: a face lies outside the grid (cell {self.cell}, dims {self.dims})")
+        return refs
+
+    def fill(self, refs):
+        dev = self.verts.device
+        self.offset = torch.zeros(self.counts.numel() + 1, dtype=torch.int32, device=dev)
+        self.offset[1:] = torch.cumsum(self.counts, 0)
+        self.refs = torch.empty(max(refs, 1), dtype=torch.int32, device=dev)
+        self.counts.zero_()     # now the cursors
+        call("mesh_grid_fill", self.verts, self.verts.shape[0], self.faces, self.faces.shape[0], self.origin, self.inv,
+             self.dims3, self.offset, self.counts, self.refs)
+
+    def keys(self, points):
+        """the index of each point's cell (clamped to the grid): what the points are sorted by, nothing more"""
+        lo = torch.tensor(self.lo, device=points.device)
+        c = torch.nan_to_num(torch.floor((points - lo) * self.inv), nan=0.0)
+        top = torch.tensor([d - 1 for d in self.dims], dtype=_f32, device=points.device)
+        c = torch.minimum(c.clamp_min(0), top).long()
+        return (c[:, 0] * self.dims[1] + c[:, 1]) * self.dims[2] + c[:, 2]
+
+
+def _start_cell(verts, faces, lo, hi, max_dist):
+    """twice the mean edge length: a handful of faces per cell and per face a handful of cells; with a max_dist
+    below that, max_dist itself but no less than one mean edge (the walk ends after ceil(max_dist / cell) + 1 rings
+    anyway, and faces span the cells whatever their size)"""
+    v = verts.double()
+    a, b, c = (v[faces[:, k].long()] for k in range(3))
+    edge = float(((b - a).norm(dim=1) + (c - b).norm(dim=1) + (a - c).norm(dim=1)).mean()) / 3
+    extent = float(np.max(np.asarray(hi, np.float64) - np.asarray(lo, np.float64)))
+    if not (edge > 0 and np.isfinite(edge)):
+        edge = extent / 128 if extent > 0 else 1.0
+    cell = 2 * edge
+    if max_dist is not None and np.isfinite(max_dist):
+        cell = min(cell, max(float(max_dist), edge))
+    return max(cell, extent / GRID_MAX_DIM)
+
+
+def closest_on_mesh(points, verts, faces, max_dist=None, cell=None, stats=None, squared=False):
+    """The distance from each point to the mesh -> (dist (n,) f32, face (n,) int32: the closest face).
+
+    Exact in the sense of include/ngp_hip.h M4: dist = sqrt(d2), d2 the smallest float32 squared distance to any face
+    with a non-zero cross product (Ericson's closest point on a triangle), ties to the smaller face index - what a
+    brute force over all faces gives, bit for bit.  Points farther than max_dist get dist = sqrt(max_dist^2 in f32)
+    and face -1; max_dist=None takes the diagonal of the union bounding box, so nothing is clipped (with no face,
+    everything is).  The faces go into a uniform grid (cell: its size, default _start_cell, doubled while the grid
+    exceeds 1024 cells per axis, 2^24 cells or, found by at most 32 count passes, 2^28 references; a `cell` given
+    by the caller is refused instead), the points are sorted by cell for the query and the outputs put back.
+    squared=True returns d2 itself in place of dist.  A dict passed as `stats` receives cell, dims, references, probes,
+    build_ms and query_ms (host clocks around device synchronisation)."""
+    _check_points(points)
+    _check_mesh(verts, faces, None, None)
+    n, n_faces = points.shape[0], faces.shape[0]
+    dev = points.device
+    info = dict(cell=None, dims=None, references=0, probes=0, build_ms=0.0, query_ms=0.0)
+    if max_dist is not None and not float(max_dist) >= 0:
+        raise ValueError(f"max_dist must be >= 0, got {max_dist}")
+    if cell is not None and not (float(cell) > 0 and np.isfinite(float(cell))):
+        raise ValueError(f"cell must be positive, got {cell}")
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    lo = hi = None
+    if n_faces:
+        used = verts[faces.reshape(-1).long()]
+        lo, hi = (x.cpu().numpy() for x in torch.aminmax(used, dim=0))
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError("a face has a vertex that is not finite")
+    if max_dist is None:
+        boxes = [torch.aminmax(points, dim=0)] if n else []
+        boxes += [(torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev))] if n_faces else []
+        if boxes:
+            span = torch.stack([b[1] for b in boxes]).amax(0).double() - torch.stack([b[0] for b in boxes]).amin(0).double()
+            max_dist = float(span.norm()) * (1 + 2.0 ** -20)     # the float32 square stays above every distance
+        else:
+            max_dist = 0.0
+        if not np.isfinite(max_dist):
+            raise ValueError("the bounding box of points and mesh is not finite: give max_dist")
+    max_dist = float(np.float32(max_dist))
+    grid = None
+    if n_faces:
+        grid = _FaceGrid(verts, faces, lo, hi)
+        if cell is not None:
+            if not grid.fits(grid.shape(cell)[2]):
+                raise ValueError(f"cell {cell} needs a grid of {grid.shape(cell)[2]} cells: more than {GRID_MAX_DIM} "
+                                 f"per axis or {GRID_MAX_CELLS} in all")
+            refs = grid.count(cell)
+            if refs > GRID_MAX_REFS:
+                raise ValueError(f"cell {cell} needs {refs} face references, more than {GRID_MAX_REFS}")
+        else:
+            cell = _start_cell(verts, faces, lo, hi, max_dist)
+            for _ in range(64):                       # sizes alone: no pass over the mesh
+                if grid.fits(grid.shape(cell)[2]):
+                    break
+                cell *= 2
+            for _ in range(GRID_MAX_PROBES):
+                refs = grid.count(cell)
+                if refs <= GRID_MAX_REFS:
+                    break
+                cell *= 2
+            else:
+                raise RuntimeError(f"no cell up to {cell} keeps the face references below {GRID_MAX_REFS}")
+        grid.fill(refs)
+        info.update(cell=grid.cell, dims=grid.dims, references=refs, probes=grid.probes)
+    torch.cuda.synchronize(dev)
+    t1 = time.perf_counter()
+    d2 = torch.empty(n, dtype=_f32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        if grid is None:
+            call("mesh_closest", points, n, None, verts.shape[0], None, 0, None, 1.0, None, None, None, max_dist, d2,
+                 face)
+        else:
+            order = torch.argsort(grid.keys(points))
+            d2_s, face_s = torch.empty_like(d2), torch.empty_like(face)
+            call("mesh_closest", points[order].contiguous(), n, verts, verts.shape[0], faces, n_faces, grid.origin,
+                 grid.inv, grid.dims3, grid.offset, grid.refs, max_dist, d2_s, face_s)
+            d2[order] = d2_s
+            face[order] = face_s
+    torch.cuda.synchronize(dev)
+    info.update(build_ms=1e3 * (t1 - t0), query_ms=1e3 * (time.perf_counter() - t1))
+    if stats is not None:
+        stats.update(info)
+    return (d2 if squared else torch.sqrt(d2)), face
+
+
+def distance_metrics(dist_a, face_a, dist_b, face_b, thresholds=()):
+    """the reductions of mesh_distance over the two directed results (dist, face) of closest_on_mesh, in float64"""
+    da, db = dist_a.double(), dist_b.double()
+    if da.numel() == 0 or db.numel() == 0:
+        raise ValueError("both sides need at least one sample")
+    accuracy, completeness = float(da.mean()), float(db.mean())
+    out = dict(accuracy=accuracy, completeness=completeness, chamfer=0.5 * (accuracy + completeness),
+               hausdorff=max(float(da.max()), float(db.max())),
+               clipped_a=float((face_a < 0).double().mean()), clipped_b=float((face_b < 0).double().mean()),
+               thresholds=[float(t) for t in thresholds], precision=[], recall=[], fscore=[])
+    for t in out["thresholds"]:
+        p, r = float((da <= t).double().mean()), float((db <= t).double().mean())
+        out["precision"].append(p)
+        out["recall"].append(r)
+        out["fscore"].append(2 * p * r / (p + r) if p + r > 0 else 0.0)
+    return out
+
+
+def mesh_distance(verts_a, faces_a, verts_b, faces_b, n_samples=1_000_000, thresholds=(), max_dist=None, seed=0,
+                  stats=None):
+    """How far mesh A (the reconstruction) is from mesh B (the reference) -> a dict of Python floats.
+
+    n_samples points are drawn on each surface (sample_surface, seed for A, seed + 1 for B) and sent to the other mesh
+    (closest_on_mesh): accuracy = the mean distance from A's samples to B, completeness = from B's samples to A,
+    chamfer = their mean, hausdorff = the larger of the two maxima, clipped_a / clipped_b = the share of samples beyond
+    max_dist (they count as max_dist; None: the diagonal of the box around both meshes, nothing is clipped).
+    thresholds / precision / recall / fscore are lists, one entry per threshold t: the share of A's samples within t
+    of B, of B's within t of A, and 2PR / (P + R) (0 when both are 0).  All reductions in float64.  A dict passed as
+    `stats` receives sample_ms and closest_on_mesh's stats of each direction under a_to_b and b_to_a."""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+    if max_dist is None:
+        both = torch.cat([verts_a, verts_b])
+        lo, hi = torch.aminmax(both, dim=0)
+        max_dist = float((hi.double() - lo.double()).norm()) * (1 + 2.0 ** -20)
+    t0 = time.perf_counter()
+    pts_a, _ = sample_surface(verts_a, faces_a, n_samples, seed=seed)
+    pts_b, _ = sample_surface(verts_b, faces_b, n_samples, seed=seed + 1)
+    if pts_a.is_cuda:
+        torch.cuda.synchronize(pts_a.device)
+    sample_ms = 1e3 * (time.perf_counter() - t0)
+    ab, ba = {}, {}
+    dist_a, face_a = closest_on_mesh(pts_a, verts_b, faces_b, max_dist=max_dist, stats=ab)
+    dist_b, face_b = closest_on_mesh(pts_b, verts_a, faces_a, max_dist=max_dist, stats=ba)
+    if stats is not None:
+        stats.update(sample_ms=sample_ms, a_to_b=ab, b_to_a=ba)
+    return distance_metrics(dist_a, face_a, dist_b, face_b, thresholds)
 
 
 # ------------------------------------------------------------------------------------------------- vertex colours

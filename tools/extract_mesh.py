@@ -4,10 +4,13 @@ density on a dense lattice, marching cubes, PLY).  GPU only.  Prints one JSON li
 density pass, marching cubes, the cleaning, the simplification, the normals, the colours, the device->host copy and
 the PLY write (each timed around a device synchronise), what the cleaning found and removed, and what the
 simplification did (cell, k, probes, clusters, V_in, V_out, F_in, F_out, degenerate, duplicate, probe_ms, emit_ms).
+--report_distance adds simplify_distance: how far the simplification moved the surface (mesh.mesh_distance between the
+cleaned and the simplified mesh: accuracy, completeness, hausdorff, each also in cells).
 
   python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --resolution 256 --normals
   python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --keep_largest 1 --colors
   python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --keep_largest 1 --target_faces 100000
+  python tools/extract_mesh.py --ckpt ckpts/lego.ckpt --scale 0.5 --out lego.ply --target_faces 100000 --report_distance
 """
 import argparse
 import json
@@ -25,6 +28,18 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from train_dataset import build_model  # noqa: E402  (the model the checkpoints of tools/train_dataset.py come from)
 
 REFERENCE_CALL = "--bbox -1 -0.3 -1 1 0.15 1 --resolution 512 128 512 --level 10 --reference_spacing"
+
+
+def simplify_distance(cleaned, simplified, cell, n_samples):
+    """accuracy (simplified -> cleaned), completeness (cleaned -> simplified) and hausdorff between the mesh that went
+    into simplify_mesh and the one that came out, each also in units of the chosen cell; None for an empty mesh"""
+    if cell is None or cleaned[1].shape[0] == 0 or simplified[1].shape[0] == 0:
+        return None
+    d = mesh.mesh_distance(*simplified, *cleaned, n_samples=n_samples)
+    out = {k: d[k] for k in ("accuracy", "completeness", "hausdorff")}
+    out.update({k + "_cells": d[k] / cell for k in ("accuracy", "completeness", "hausdorff")})
+    out.update(cell=cell, samples=n_samples)
+    return out
 
 
 def main(argv=None):
@@ -52,6 +67,11 @@ def main(argv=None):
                           help="simplify with the smallest cell found that leaves at most N faces")
     ap.add_argument("--placement", choices=("quadric", "mean"), default="quadric",
                     help="where a merged vertex goes: the quadric minimiser of its faces' planes, or the mean")
+    ap.add_argument("--report_distance", action="store_true",
+                    help="with --simplify_cell / --target_faces: how far the simplification moved the surface "
+                         "(simplify_distance in the JSON line)")
+    ap.add_argument("--distance_samples", type=int, default=1_000_000, metavar="N",
+                    help="surface samples per mesh of --report_distance")
     ap.add_argument("--colors", action="store_true",
                     help="per-vertex RGB rendered from the trained appearance field (PLY red green blue)")
     ap.add_argument("--embed_a", action="store_true",
@@ -68,6 +88,10 @@ def main(argv=None):
         ap.error("--simplify_cell must be positive")
     if args.target_faces is not None and args.target_faces < 0:
         ap.error("--target_faces must be >= 0")
+    if args.report_distance and args.simplify_cell is None and args.target_faces is None:
+        ap.error("--report_distance needs --simplify_cell or --target_faces")
+    if args.distance_samples < 1:
+        ap.error("--distance_samples must be >= 1")
     res = args.resolution[0] if len(args.resolution) == 1 else tuple(args.resolution)
 
     dev = torch.device("cuda", 0)
@@ -99,10 +123,19 @@ def main(argv=None):
     t_c = time.perf_counter()
     simplified = {}
     if args.simplify_cell is not None or args.target_faces is not None:
+        cleaned = (verts, faces)
         verts, faces = mesh.simplify_mesh(verts, faces, cell=args.simplify_cell, target_faces=args.target_faces,
                                           origin=lo, placement=args.placement, stats=simplified)
     torch.cuda.synchronize()
     t_s = time.perf_counter()
+    report = {}
+    t_r = t_s
+    if args.report_distance:     # on a clock of its own: simplify_ms and normals_ms mean what they mean without the flag
+        report["simplify_distance"] = simplify_distance(cleaned, (verts, faces), simplified["cell"],
+                                                        args.distance_samples)
+        torch.cuda.synchronize()
+        t_r = time.perf_counter()
+        report["simplify_distance_ms"] = round(1e3 * (t_r - t_s), 3)
     nrm = mesh.vertex_normals(model, verts, args.chunk) if args.normals or args.colors else None
     torch.cuda.synchronize()
     t_n = time.perf_counter()
@@ -116,14 +149,14 @@ def main(argv=None):
     t3 = time.perf_counter()
     mesh.write_ply(args.out, v, f, nrm, rgb)
     t4 = time.perf_counter()
-    times = {"density_ms": 1e3 * (t1 - t0), "mc_ms": 1e3 * (t2 - t1), "normals_ms": 1e3 * (t_n - t_s),
+    times = {"density_ms": 1e3 * (t1 - t0), "mc_ms": 1e3 * (t2 - t1), "normals_ms": 1e3 * (t_n - t_r),
              "d2h_ms": 1e3 * (t3 - t_k), "ply_ms": 1e3 * (t4 - t3), "clean_ms": 1e3 * (t_c - t2),
              "colors_ms": 1e3 * (t_k - t_n), "simplify_ms": 1e3 * (t_s - t_c)}
     print(json.dumps({"V": int(v.shape[0]), "F": int(f.shape[0]), "lattice": list(vol.shape),
                       **{k: round(x, 3) for k, x in times.items()},
                       **{k: stats[k] for k in ("components", "V_removed", "F_removed")},
                       **{k: round(x, 3) if isinstance(x, float) and k.endswith("_ms") else x
-                         for k, x in simplified.items()}}))
+                         for k, x in simplified.items()}, **report}))
 
 
 if __name__ == "__main__":
