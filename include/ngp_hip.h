@@ -931,7 +931,7 @@ int ngp_mesh_simplify_faces(const int32_t* faces, int n_faces, int n_verts, cons
  *   e = p - q, result dot(e, e); every division is IEEE.
  * The search walks the cells of growing Chebyshev distance r from the point's own (unclamped) cell coordinate and stops
  * after a whole ring when no face it has not seen can win or tie (a lower bound that allows for the rounding of the
- * cell coordinates and of the distance itself: mesh_eval_kernels.hip), after ceil(max_dist * inv_cell) + 1 rings (plus
+ * cell coordinates and of the distance itself: csrc/ring_walk.h), after ceil(max_dist * inv_cell) + 1 rings (plus
  * that allowance), or when the grid is exhausted: every loop is bounded before it starts, none waits on another thread,
  * and the result does not depend on the grid or on the order inside a cell.  No floating-point atomics: the same bytes
  * from run to run.
@@ -950,6 +950,57 @@ int ngp_mesh_closest(const float* points, int64_t n, const float* verts, int n_v
                      int n_faces, const float* origin3 /* host */, float inv_cell, const int32_t* dims3 /* host */,
                      const int32_t* cell_offset, const int32_t* cell_faces, float max_dist, float* d2, int32_t* face,
                      void* stream);
+
+/* ------------------------------------------------------------------------
+ * M5  point clouds: the nearest point of a cloud with the sums of a registration step, and voxel means
+ *     (scores an export against a laser-scan reference: cloud.py nearest_points / icp / voxel_downsample / tnt_score,
+ *     tools/eval_mesh.py --ref_points)
+ * All f32 and f64 arithmetic below is uncontracted, in the order written.
+ * The grid is M4's: dims3[a] cells of edge 1 / inv_cell per axis from origin3 (both HOST arrays; dims3[a] in
+ * [1, 1024], at most 2^24 cells), cell (x, y, z) at index (x * dims3[1] + y) * dims3[2] + z, the cell coordinate of a
+ * position floorf((p_a - origin3[a]) * inv_cell) per axis.  The caller sorts the cloud by cell index (stable) and
+ * passes cloud4 (n_cloud, 4) f32, 16-byte aligned: row k = (x, y, z, the bit pattern of the int32 original index) of
+ * the k-th point in that order, every coordinate finite and inside the grid, and cell_offset (cells + 1, int32): the
+ * rows of cell c are [cell_offset[c], cell_offset[c + 1]) (offsets outside [0, n_cloud] are clamped, never followed).
+ * ngp_cloud_nearest: one thread per query (queries (n, 3) f32, n <= 2^31 - 1; the caller sorts them by cell for speed,
+ * the result does not depend on it).  xform12: a HOST array of 12 floats, row-major 3 x 4 (R | t), or NULL; with it the
+ * query is p'_a = ((R_a0 * x + R_a1 * y) + R_a2 * z) + t_a in f32, without it p' = (x, y, z).  For a point q of the
+ * cloud d2 = (dx * dx + dy * dy) + dz * dz in f32 with d = p' - q; candidates are compared with <, so a NaN or infinite
+ * d2 never wins; among equal d2 the smallest original index wins; if the winner's d2 > max_dist * max_dist (one f32
+ * product) or nothing won (n_cloud == 0: every query; then no grid argument is looked at), d2[i] = max_dist * max_dist
+ * and index[i] = -1, else d2[i] and index[i] = the winner's d2 and original index.  d2 and index may each be NULL.
+ * The search is M4's walk over the rings of cells around the query's unclamped cell coordinate with its stop rule and
+ * ring cap (csrc/ring_walk.h; cloud_kernels.hip says why the bound holds for points): every loop is bounded before it
+ * starts - a query with a NaN coordinate walks the grid's cells once, matches nothing and gets index -1 - and no
+ * thread waits on another.
+ * partials (workgroups x 18 doubles, workgroups = ceil(n / 256); may be NULL; needs centre3, a HOST array of 3 finite
+ * floats): row w holds, over the queries 256 w .. 256 w + 255 with index >= 0, and with p~ = (double)p' -
+ * (double)centre3, q~ = (double)q - (double)centre3 (q the winner):
+ *   [0] the count, [1..3] sum p~, [4..6] sum q~, [7 + 3 a + b] sum p~_a * q~_b, [16] sum (p~_x^2 + p~_y^2) + p~_z^2,
+ *   [17] sum (double)d2.
+ * Each entry is wave_sum<double> (xor butterfly 32 -> 1) over the terms of a wave, zero for a query that did not
+ * match, then the 4 waves added in order.  A workgroup writes its own row and nothing else.
+ * ngp_cloud_sum_partials: sums18[e] = the sum of column e of partials (rows x 18): accumulator g of 14 adds the rows
+ * g, g + 14, g + 28, ... in rising order from 0.0, then the 14 are added in order g = 0 .. 13.  One workgroup, no
+ * atomics: the same 18 * 8 bytes on every run.  rows == 0 writes 18 zeros.
+ * ngp_cloud_voxel_mean: points (n, 3) f32 sorted by voxel (the caller's stable sort, so the original order inside a
+ * voxel) and offsets (n_voxels + 1, int64, DEVICE): voxel v owns the rows [offsets[v], offsets[v + 1]) (clamped to
+ * [0, n]).  One thread per voxel adds its rows in order in double from 0.0 per axis, divides by the count (IEEE, double)
+ * and rounds once to f32 into points_out (n_voxels, 3).  normals (n, 3) f32 -> normals_out likewise (the mean, not
+ * renormalised); colors (n, 3) uint8 -> colors_out = (uint8)floor(sum / count + 0.5) in double (half away from zero).
+ * normals and colors may be NULL (then their outputs are not looked at); an empty run writes zeros.
+ * No entry allocates or synchronises.  ngp_cloud_nearest and ngp_cloud_voxel_mean: n == 0 returns NGP_OK before any
+ * pointer is looked at (n_voxels == 0 likewise); every pointer and size is checked (NGP_EINVAL) before any launch
+ * (n < 0, n_voxels > n, max_dist not >= 0 - infinity is allowed -, partials without centre3, a grid M4 would refuse).
+ * ---------------------------------------------------------------------- */
+int ngp_cloud_nearest(const float* queries, int64_t n, const float* cloud4, int n_cloud,
+                      const float* origin3 /* host */, float inv_cell, const int32_t* dims3 /* host */,
+                      const int32_t* cell_offset, float max_dist, const float* xform12 /* host */,
+                      const float* centre3 /* host */, float* d2, int32_t* index, double* partials, void* stream);
+int ngp_cloud_sum_partials(const double* partials, int64_t rows, double* sums18, void* stream);
+int ngp_cloud_voxel_mean(const float* points, const float* normals, const uint8_t* colors, int64_t n,
+                         const int64_t* offsets, int64_t n_voxels, float* points_out, float* normals_out,
+                         uint8_t* colors_out, void* stream);
 
 /* ------------------------------------------------------------------------
  * I1  SSIM of rendered images (replaces torchmetrics' StructuralSimilarityIndexMeasure(data_range=1) of the

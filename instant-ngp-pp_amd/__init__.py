@@ -12,6 +12,7 @@ Sub-modules (same names / call signatures as zhihao-lin/instant-ngp-pp):
   appearance        — FrameEmbedding (utils.py:97-143) and RayCodes, the per-image appearance codes of the embed_a recipe
   trainer           — the training schedule of train.py (no Lightning)
   mesh              — marching cubes + PLY export (extract_mesh.py)
+  cloud             — point-cloud ground truth: nearest point, voxel down-sampling, ICP, the Tanks-and-Temples F-score
   metrics           — psnr, ssim
   evaluation        — whole frames from a camera, their 8-bit images, PSNR / SSIM of a split (render.py, validation)
 
@@ -20,7 +21,7 @@ Every compute call goes through libngp_hip.so (include/ngp_hip.h); there is no C
 from . import _lib  # noqa: F401  (parses the header; the .so is loaded on first use)
 
 __all__ = ["vren", "tinycudann", "torch_scatter", "custom_functions", "rendering", "networks", "losses",
-           "metrics", "trainer", "synthetic", "ckpt", "mesh", "evaluation", "colormap", "implicit_mask", "appearance",
+           "metrics", "trainer", "synthetic", "ckpt", "mesh", "cloud", "evaluation", "colormap", "implicit_mask", "appearance",
            "install_as_reference_modules"]
 
 

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libngp_hip.so")
 LIB_ID = LIB + ".id"
-HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "grid_index.h", "mlp_act.h", "mlp_tile.h")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "grid_index.h", "mlp_act.h", "mlp_tile.h", "ring_walk.h")] + \
           [os.path.join(HERE, "..", "include", "ngp_hip.h")]
 
 # (source, extra flags).  ray_kernels.hip is compiled without FMA contraction so that the
@@ -35,6 +35,7 @@ SOURCES = [
     ("mesh_clean_kernels.hip", []),
     ("mesh_simplify_kernels.hip", ["-ffp-contract=off"]),   # cell keys are bit-identical to their numpy restatement
     ("mesh_eval_kernels.hip", ["-ffp-contract=off"]),   # samples and distances are bit-identical to their restatement
+    ("cloud_kernels.hip", ["-ffp-contract=off"]),   # distances, sums and voxel means are bit-identical to their restatement
     ("image_kernels.hip", ["-ffp-contract=off"]),   # frame packing is bit-identical to its numpy restatement
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

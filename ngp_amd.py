@@ -17,5 +17,5 @@ for _sub in ("_lib", "build", "vren", "tinycudann", "torch_scatter", "custom_fun
              "losses", "synthetic", "trainer", "ckpt", "mesh", "datasets", "datasets.base", "datasets.ray_utils",
              "datasets.color_utils", "datasets.colmap_utils", "datasets.nerf", "datasets.colmap", "datasets.tnt",
              "datasets.nsvf", "datasets.nerfpp", "datasets.export", "metrics", "colormap", "evaluation", "imaging", "appearance",
-             "link", "implicit_mask", "recipe"):
+             "link", "implicit_mask", "recipe", "cloud"):
     sys.modules[f"{__name__}.{_sub}"] = importlib.import_module(f"{_REAL}.{_sub}")
